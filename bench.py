@@ -12,6 +12,10 @@ The multi-rank path is dynamicsparsearrays.jl_amd/sharding.py (ColumnShard): the
 
 Launch: python bench.py --gpus 1            (default)
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the steps and prints the line (roofline figures derived from the timed region only).  --full adds
+everything else: the per-launch and cold-cache kernel timings, the quoted floors and PMC traffic, the collective schedules (N > 1),
+the extra legs (inserts/s, rebalance, config 5, ...) and the CPU baseline.  --dump-outputs DIR writes y of the last timed step.
 """
 import argparse
 import ctypes as C
@@ -29,6 +33,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 
 M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
+DUMP_MAX_ROWS = 2_000_000  # --dump-outputs: y above this many rows is sampled (values + row indices: 32 MB at most)
 
 
 def splitmix_array(seed, n, start=0):
@@ -166,9 +171,17 @@ def main():
     ap.add_argument("--dump-y", default=None,
                     help="rank 0 writes y = A x of every reduction schedule (after the timed steps) to this .npz file: what a test compares with "
                          "the CPU oracle (tests/test_hip_parity.py::test_bench_two_ranks_on_one_gpu_gloo_rehearsal)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the inserts/s and rebalance legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes y = A x of the LAST timed step to DIR/y.npy (float64); above %d rows a fixed seeded sample of them "
+                         "instead: DIR/y_sample.npy and its 0-based row indices DIR/y_sample_rows.npy (float64)" % DUMP_MAX_ROWS)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything the headline does not need: per-launch and cold kernel timings, quoted floors "
+                         "and PMC traffic, the collective schedules (N > 1), the extra legs and the CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the inserts/s and rebalance legs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -298,11 +311,16 @@ def main():
     gc.enable()
     ms_per_step = elapsed * 1e3 / args.steps
     region_ms = ev_region[0].elapsed_time(ev_region[1]) / args.steps
+    if args.dump_outputs and rank == 0:
+        # y of the last timed step, before anything else writes the buffer (the barrier above drained its reduction)
+        write_outputs(args.dump_outputs, ys[(args.steps - 1) % len(ys)].cpu().numpy())
     # the kernel's average launch duration: at N = 1 the region holds nothing but the K launches, back to back on one stream, so the
     # bracket / K is it (idle gaps between launches, if the host fell behind, are charged to the kernel); at N > 1 the stream also
-    # waits for collectives inside the region, so the launches are timed again right behind it, K of them alone between one pair
+    # waits for collectives inside the region, so the launches are timed again right behind it (--full), K of them alone between one pair
     if world == 1:
         kern_ms = region_ms
+    elif not args.full:
+        kern_ms = None
     else:
         ev_k = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev_k[0].record(stream)
@@ -312,15 +330,17 @@ def main():
         torch.cuda.synchronize()
         kern_ms = ev_k[0].elapsed_time(ev_k[1]) / args.steps
     # cross-check in the old form (a pair of events around single launches, outside the timed region)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 20))]
-    for a, b in ev:
-        a.record(stream); shard.spmv_partial(x, ys[0]); b.record(stream)
-    torch.cuda.synchronize()
-    kern_pair_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    kern_pair_ms = None
+    if args.full:
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 20))]
+        for a, b in ev:
+            a.record(stream); shard.spmv_partial(x, ys[0]); b.record(stream)
+        torch.cuda.synchronize()
+        kern_pair_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     # the same launch COLD: the timed steps run back to back on 2 x 203 MB of slot buffers + 8 MB of x, within reach of the 256 MB
     # Infinity Cache (FETCH_SIZE counts MALL hits as fetches); here every launch follows a 1 GiB device write
     cold_us = None
-    if world == 1:
+    if world == 1 and args.full:
         try:
             cold_us = cold_launch_us(torch, dev, stream, lambda: shard.spmv_partial(x, ys[0]))
         except Exception:
@@ -332,7 +352,12 @@ def main():
     slot_bytes = 16 if (os.environ.get("DSA_KEYS_WIDE") == "1" and os.environ.get("DSA_DEV") == "1") else 12      # int32 keys in HBM while every key fits Int32 (KeyArr)
     physical_bytes = slot_bytes * cap + cap // 8 + 8 * ncl + 8 * m            # what the kernel has to move at least: slots + bitmap + x + y
     value = world * bytes_launch / 1e9 / (ms_per_step / 1e3)
-    achieved = bytes_launch / 1e9 / (kern_ms / 1e3)
+
+    def rnd(v, digits):
+        return None if v is None else round(v, digits)
+
+    def per_kernel(b, peak=1.0):            # GB/s (/ peak) of b bytes in the measured kernel time; None when it was not measured
+        return None if kern_ms is None else b / 1e9 / (kern_ms / 1e3) / peak
     nomemset = A.info(dsa.ROWMAJOR)["stat_spmv_nomemset"] > 0
 
     workload = ("C3: PCSR %dx%d Float64, %d nnz per GPU, dense-x SpMV y=A*x (gather over the rowmajor twin)" % (m, n_total, nnz)) if cfg == "c3" else \
@@ -357,19 +382,20 @@ def main():
                    "physical_slot_bytes": slot_bytes,
                    "collective": ("%s of y (%d f64 = %.0f MB) over %s%s" % (args.schedule, m, 8 * m / 1e6, ("RCCL / xGMI" + (" behind the C ABI (dsa_shard_allreduce_dev)" if abi_comm is not None else "")) if backend == "nccl" else backend,
                                   ", on RCCL's stream, overlapped with the next step's SpMV (two y buffers)" if overlap else "")) if world > 1 else "none"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+        "roofline": {"bound": "hbm", "achieved": rnd(per_kernel(bytes_launch), 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": rnd(per_kernel(bytes_launch, HBM_PEAK_GBS), 4), "traffic": None,
                      "kernel": "dsa::k_spmv_gather" + (" (no memset of y: the kernel zero-fills rows without a partition)" if nomemset else " (+ memset of y)"),
                      "algorithmic_bytes": bytes_launch,
-                     "kernel_ms": round(kern_ms, 5),
+                     "kernel_ms": rnd(kern_ms, 5),
                      "kernel_ms_source": ("one HIP event pair around the %d launches of the timed region / %d" % (args.steps, args.steps)) if world == 1 else
-                                         ("one HIP event pair around %d launches alone, right behind the timed region / %d" % (args.steps, args.steps)),
-                     "kernel_ms_event_pair_per_launch": round(kern_pair_ms, 5),
+                                         ("one HIP event pair around %d launches alone, right behind the timed region / %d" % (args.steps, args.steps)) if args.full else
+                                         "not timed: the launches alone are timed with --full",
+                     "kernel_ms_event_pair_per_launch": rnd(kern_pair_ms, 5),
                      "physical_bytes": physical_bytes,
-                     "physical_gbps": round(physical_bytes / 1e9 / (kern_ms / 1e3), 2),
-                     "physical_frac": round(physical_bytes / 1e9 / (kern_ms / 1e3) / HBM_PEAK_GBS, 4),
+                     "physical_gbps": rnd(per_kernel(physical_bytes), 2),
+                     "physical_frac": rnd(per_kernel(physical_bytes, HBM_PEAK_GBS), 4),
                      "useful_bytes_no_gaps": useful_bytes,
-                     "useful_gbps": round(useful_bytes / 1e9 / (kern_ms / 1e3), 2),
+                     "useful_gbps": rnd(per_kernel(useful_bytes), 2),
                      "note": "achieved / frac divide SURVEY's ALGORITHMIC bytes (16-byte logical slots) by the measured time; physical_* "
                              "count the 12-byte slots + bitmap the kernel actually streams"},
         "nnz_per_s": round(world * nnz / (ms_per_step / 1e3), 1),
@@ -387,7 +413,8 @@ def main():
     # key-driven kernel (no rows, no semaphores, no y) — the floor a single-pass kernel on uniformly random columns has,
     # in the record next to the fraction it explains.  (Rounds 3-4 quoted gatherbench2's 11 M gathers from an 8.4 MB table: 10 % more
     # gathers than the product issues — semaphores do not read x.)
-    if cfg == "c3" and m == 1_000_000 and ncl == 1_000_000 and per == 10:
+    c3_default = cfg == "c3" and m == 1_000_000 and ncl == 1_000_000 and per == 10
+    if args.full and c3_default:
         try:
             with open(os.path.join(ROOT, "profiles", "gather_floor.json")) as f:
                 gf = json.load(f)
@@ -405,16 +432,18 @@ def main():
 
     # HBM-side traffic per launch: only from a committed rocprofv3 PMC summary made from the CURRENT kernel sources
     # (tools/scripts/profile_round.sh: separate --pmc FETCH_SIZE / WRITE_SIZE passes of the same workload); otherwise null
-    pmc_file, pm = committed_pmc()
-    if pm is not None and cfg == "c3" and m == 1_000_000 and ncl == 1_000_000 and per == 10:
+    pmc_file, pm = committed_pmc() if args.full else (None, None)
+    if not args.full:
+        out["roofline"]["traffic_source"] = "not looked up: a run with --full quotes the committed PMC summary"
+    elif pm is not None and c3_default:
         out["roofline"]["traffic"] = pm.get("k_spmv_gather_C3", {}).get("corrected_traffic_total")
         out["roofline"]["traffic_source"] = "%s (rocprofv3 --pmc, corrected; kernel sources %s)" % (pmc_file, pm.get("kernel_source_sha"))
-    elif cfg == "c3" and m == 1_000_000 and ncl == 1_000_000 and per == 10:
+    elif c3_default:
         out["roofline"]["traffic_source"] = "none: no committed PMC summary matches the current kernel sources (%s)" % kernel_source_sha()
     else:
         out["roofline"]["traffic_source"] = "none: the committed PMC passes profile the C3 workload only"
 
-    if world > 1:
+    if world > 1 and args.full:
         # the local product alone and the schedule of the sum of y used above (all three with --all-schedules), timed back to
         # back without overlap (max over ranks): what the collective costs next to the SpMV it follows
         sched = {}
@@ -454,7 +483,7 @@ def main():
             ydump["abi_all_reduce"] = yy.cpu().numpy()
         if rank == 0:
             np.savez(args.dump_y, **ydump)
-    if rank == 0 and world == 1 and not args.no_extras:          # the extra legs and the CPU baseline belong to the N = 1 line
+    if args.full and rank == 0 and world == 1 and not args.no_extras:          # the extra legs and the CPU baseline belong to the N = 1 line
         try:
             out.update(extras(dsa, hip, torch, A, dev))
         except Exception as e:               # an extra leg must never cost the headline line
@@ -462,7 +491,7 @@ def main():
         if pm is not None and "roofline_rebalance" in out:
             out["roofline_rebalance"]["traffic"] = pm.get("k_move_root_2^24", {}).get("corrected_traffic_total") \
                 if out["roofline_rebalance"]["window_slots"] == 16777216 else None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(dsa, m, per)
         except Exception as e:
@@ -472,6 +501,19 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out))
+
+
+def write_outputs(dirname, y):
+    """--dump-outputs: y as DIR/y.npy, or above DUMP_MAX_ROWS rows a fixed sample of it (seed 0, rows ascending) as DIR/y_sample.npy with
+    its 0-based row indices as DIR/y_sample_rows.npy (float64: exact below 2^53)."""
+    os.makedirs(dirname, exist_ok=True)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if len(y) <= DUMP_MAX_ROWS:
+        np.save(os.path.join(dirname, "y.npy"), y)
+        return
+    rows = np.sort(np.random.default_rng(0).choice(len(y), DUMP_MAX_ROWS, replace=False))
+    np.save(os.path.join(dirname, "y_sample.npy"), y[rows])
+    np.save(os.path.join(dirname, "y_sample_rows.npy"), rows.astype(np.float64))
 
 
 def extras(dsa, hip, torch, A, dev):

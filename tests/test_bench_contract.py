@@ -1,5 +1,5 @@
-"""CPU test: the committed bench line (profiles/r03c_final_bench.json, produced by `python bench.py` on an MI355X) carries every field the
-driver's contract names, and its derived numbers are consistent with each other."""
+"""CPU tests: the newest committed bench line (profiles/r*_final_bench.json, a full line as `python bench.py --full` prints it on an MI355X)
+carries every field the driver's contract names, and its derived numbers are consistent with each other; the --dump-outputs writer."""
 import glob
 import json
 import os
@@ -62,3 +62,28 @@ def test_committed_kernel_trace_agrees_with_the_bench_line():
     trace_ms = float(top["AverageNs"]) / 1e6
     bench_ms = d["roofline"]["kernel_ms"]
     assert abs(trace_ms - bench_ms) / bench_ms < 0.04, (trace_ms, bench_ms)
+
+
+def test_dump_outputs_writer_keeps_small_y_whole_and_samples_a_large_one_the_same_way(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: y up to DUMP_MAX_ROWS rows is written whole as float64; a longer y as a fixed sample (the same rows on every
+    run) with its row indices, so that two builds can be compared output for output within the size bound."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    y = np.arange(1, 101, dtype=np.float64) * 0.5
+    bench.write_outputs(str(tmp_path / "small"), y)
+    assert sorted(os.listdir(tmp_path / "small")) == ["y.npy"]
+    got = np.load(str(tmp_path / "small" / "y.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, y)
+    monkeypatch.setattr(bench, "DUMP_MAX_ROWS", 10)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), y)
+        assert sorted(os.listdir(tmp_path / d)) == ["y_sample.npy", "y_sample_rows.npy"]
+    rows = np.load(str(tmp_path / "a" / "y_sample_rows.npy"))
+    vals = np.load(str(tmp_path / "a" / "y_sample.npy"))
+    assert rows.dtype == np.float64 and vals.dtype == np.float64 and len(rows) == len(vals) == 10
+    assert np.all(np.diff(rows) > 0) and np.array_equal(vals, y[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(str(tmp_path / "b" / "y_sample_rows.npy")))
+    monkeypatch.undo()
+    assert 2 * 8 * bench.DUMP_MAX_ROWS < 64 * 10 ** 6          # a sample and its indices stay under the 64 MB bound

@@ -2217,7 +2217,8 @@ def test_bench_two_ranks_on_one_gpu_gloo_rehearsal(dsa, hip, oracle, tmp_path):
     rows, cpg, world = 200_000, 25_000, 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(world), "--config", "c4", "--rows", str(rows),
-           "--cols-per-gpu", str(cpg), "--steps", "3", "--warmup", "1", "--all-schedules", "--dump-y", ydump]
+           "--cols-per-gpu", str(cpg), "--steps", "3", "--warmup", "1", "--full", "--all-schedules", "--dump-y", ydump,
+           "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -2243,6 +2244,40 @@ def test_bench_two_ranks_on_one_gpu_gloo_rehearsal(dsa, hip, oracle, tmp_path):
     assert set(got.files) >= {"all_reduce", "rs_ag", "direct"}
     for name in got.files:
         np.testing.assert_allclose(got[name], ref, rtol=1e-12, atol=0, err_msg=name)
+    # --dump-outputs: y of the last timed step (the overlapped all_reduce schedule), as rank 0 received it
+    y_last = np.load(str(tmp_path / "out" / "y.npy"))
+    assert y_last.dtype == np.float64
+    np.testing.assert_allclose(y_last, ref, rtol=1e-12, atol=0)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_y(dsa, hip, oracle, tmp_path):
+    """A plain `bench.py --gpus 1` (no --full) on a small C3-shaped matrix: one result line with the headline fields, none of the legs
+    that --full adds, and --dump-outputs writes y of the last timed step, equal to the CPU oracle's product on the same inputs."""
+    import subprocess
+    sys.path.insert(0, ROOT)
+    import bench
+    rows, cols = 30_000, 20_000
+    out_dir = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c3", "--rows", str(rows), "--cols-per-gpu", str(cols),
+           "--steps", "4", "--warmup", "1", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "spmv_gbps_10M_nnz_pcsr" and d["unit"] == "GB/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert abs(d["value"] - d["roofline"]["algorithmic_bytes"] / (d["ms_per_step"] * 1e-3) / 1e9) / d["value"] < 0.01
+    for k in ("cpu_baseline", "inserts_per_s", "roofline_rebalance", "c5_streaming", "collective_schedules"):
+        assert k not in d, k
+    assert "cold_kernel_ms" not in d["roofline"] and d["roofline"]["kernel_ms_event_pair_per_launch"] is None
+    assert sorted(os.listdir(out_dir)) == ["y.npy"]
+    y = np.load(str(out_dir / "y.npy"))
+    assert y.dtype == np.float64 and y.shape == (rows,)
+    I, J, V = bench.c3_triplets(rows, cols, 10, 0, seed_rows=5, seed_vals=6)
+    ref = dsa.dynamicsparse(I, J, V, rows, cols, binding=oracle).mul(bench.unit12(7, cols), dense_out=rows)
+    np.testing.assert_allclose(y, ref, rtol=RTOL, atol=0)
 
 
 @pytest.mark.gpu

@@ -12,6 +12,6 @@ grep "mat_apply_sets" $O/c5_time.log | awk 'NR>1{tot+=$5; n++; if(NR<=11){f10+=$
 echo "== bug3 lib must fail in mode 1 on leafmat seeds 9215.."
 DSA_LIBRARY=$C/libdsa_hip_fpcheck_bug3.so DSA_FP_MODE=1 FUZZ_ONLY=leafmat timeout -k 10 300 python tools/fuzz.py 20 9101 > $O/bug3_mode1.log 2>&1; echo "rc=$?"; grep -c DSA_FP_CHECK $O/bug3_mode1.log
 DSA_LIBRARY=$C/libdsa_hip_fpcheck.so DSA_FP_MODE=1 FUZZ_ONLY=leafmat timeout -k 10 300 python tools/fuzz.py 60 9101 > $O/fixed_mode1.log 2>&1; echo "fixed rc=$?"; tail -1 $O/fixed_mode1.log
-python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python3 -c "
+python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python3 -c "
 import json;d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1])
 print('value',d['value'],'frac',d['roofline']['frac']); print('c5',d.get('c5_streaming')); print('c5_per_call',d.get('c5_per_call')); print('ins',d.get('inserts_per_s')); print('ic3',{k:v for k,v in d.get('inserts_on_c3',{}).items() if 'runs' in k or k=='error'}); print('reb',d.get('roofline_rebalance')); print('fill',d.get('buffered_writes')); print('err',d.get('extras_error'))"

@@ -28,7 +28,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -377,19 +376,6 @@ __global__ __launch_bounds__(1024) void k_bf_scan(uint32_t* __restrict__ cnt_c, 
             __hip_atomic_store(host + 7, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);                               // BuildCtl::zeros doubles as the sequence word here
         }
     }
-}
-// waits for k_bf_scan's hand-over (polling the pinned word; the stream is asked now and then so that a failed launch cannot hang the host)
-static hipError_t wait_counts(BuildCtl* hctl, unsigned long long seq, hipStream_t stream) {
-    volatile unsigned long long* w = reinterpret_cast<volatile unsigned long long*>(hctl) + 7;
-    auto next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-    while (__atomic_load_n(w, __ATOMIC_ACQUIRE) != seq) {
-        if (std::chrono::steady_clock::now() < next_query) continue;
-        const hipError_t q = hipStreamQuery(stream);
-        if (q == hipErrorNotReady) { next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2); continue; }
-        if (q != hipSuccess) return q;
-        if (__atomic_load_n(w, __ATOMIC_ACQUIRE) != seq) return hipErrorUnknown;
-    }
-    return hipSuccess;
 }
 static std::atomic<unsigned long long> g_count_seq{0x5eed0000ull};
 
@@ -755,7 +741,6 @@ hipError_t build_prepare(const int64_t* d_part, const int64_t* d_key, const doub
     s.n = nnz; s.stream = stream;
     const size_t n = (size_t)nnz;
     static const bool force_wide = [] { const char* e = dev_env("DSA_BUILD_WIDE"); return e && e[0] == '1'; }();
-    static const bool force_minmax = [] { const char* e = dev_env("DSA_BUILD_MINMAX"); return e && e[0] == '1'; }();      // dev: ignore the caller's ranges
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int64_t nblocks = (nnz + RS_TILE - 1) / RS_TILE;
     BCHK(pinned_ctl_get(&s.h_ctl));
@@ -774,7 +759,7 @@ hipError_t build_prepare(const int64_t* d_part, const int64_t* d_key, const doub
     BuildCtl* dctl = static_cast<BuildCtl*>(s.d_ctl);
     BuildCtl* hctl = static_cast<BuildCtl*>(s.h_ctl);
     // ---- key ranges: how many bits the composite needs
-    if (!key_range.known() || (d_part != nullptr && !part_range.known()) || force_minmax) {
+    if (!key_range.known() || (d_part != nullptr && !part_range.known())) {
         long long* partial = reinterpret_cast<long long*>(s.ghist + 8 * RS_BINS);
         unsigned int* ticket = reinterpret_cast<unsigned int*>(partial + 4 * MM_BLOCKS);
         BCHK(hipMemsetAsync(ticket, 0, 2 * sizeof(unsigned int), stream));
@@ -801,9 +786,8 @@ hipError_t build_prepare(const int64_t* d_part, const int64_t* d_key, const doub
     const size_t lds_bytes = (size_t)RS_TILE * (sizeof(uint64_t) + sizeof(double));
     BCHK(once.run([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }));
     const int total_bits = s.kbits + s.pbits;
-    static const bool idx_sort = [] { const char* e = dev_env("DSA_BUILD_IDXSORT"); return !(e && e[0] == '0'); }();      // dev knob: 0 = always carry the values
     const int ibits_need = std::max(1, bit_width_u64((uint64_t)(nnz - 1)));
-    s.ibits = (idx_sort && total_bits + ibits_need <= 64) ? ibits_need : 0;
+    s.ibits = total_bits + ibits_need <= 64 ? ibits_need : 0;
     if (s.ibits == 0) {
         BCHK(pool_alloc(&s.base_val, 2 * b_comp));
         s.val[0] = static_cast<double*>(s.base_val); s.val[1] = reinterpret_cast<double*>(static_cast<char*>(s.base_val) + b_comp);
@@ -838,7 +822,7 @@ hipError_t build_prepare(const int64_t* d_part, const int64_t* d_key, const doub
     if (while_sorting && *while_sorting) {
         try { (*while_sorting)(); } catch (...) { (void)hipStreamSynchronize(stream); throw; }
     }
-    BCHK(wait_counts(hctl, seq, stream));
+    BCHK(wait_pinned_seq(&hctl->zeros, seq, stream));       // k_bf_scan's hand-over (the word it writes last)
     counts[0] = (int64_t)hctl->ncells; counts[1] = (int64_t)hctl->nparts;
     return hipGetLastError();
 }
@@ -899,7 +883,7 @@ hipError_t build_derived_sort(BuildScratch& s, int64_t counts[2], hipStream_t st
     if (while_sorting && *while_sorting) {
         try { (*while_sorting)(); } catch (...) { (void)hipStreamSynchronize(stream); throw; }
     }
-    BCHK(wait_counts(hctl, seq, stream));
+    BCHK(wait_pinned_seq(&hctl->zeros, seq, stream));       // k_bf_scan's hand-over (the word it writes last)
     counts[0] = (int64_t)hctl->ncells; counts[1] = (int64_t)hctl->nparts;
     return hipGetLastError();
 }

@@ -235,6 +235,12 @@ void set_last_error(const char* msg);
 // DSA_RCCL_LIB, DSA_WAIT_POLICY, DSA_ROCTX.
 const char* dev_env(const char* name);      // text behind dsa_last_error_message() for entry points outside dsa_host.hip
 
+// Hand-over of a launch's result through pinned memory: the last kernel writes its results into pinned host memory and then a
+// sequence number into `word`; the host polls the word instead of issuing device-to-host copies and synchronising the stream.
+// Waits until (*word & mask) == want, asking `s` every 2 ms so that a failed launch or a faulted kernel cannot hang the host.
+// Returns hipSuccess, the stream's error, or hipErrorUnknown when the stream finished without publishing (dsa_host.hip).
+hipError_t wait_pinned_seq(const volatile void* word, uint64_t want, hipStream_t s, uint64_t mask = ~0ull);
+
 // one-time kernel attribute setup (hipFuncSetAttribute is per device): thread-safe — the two orientations of a matrix are driven
 // from two host threads (dsa_host.hip: mat_apply_sets) — and repeated for every device a process uses
 struct PerDeviceOnce {
@@ -433,7 +439,7 @@ struct RoundState {
 struct PendOp { int64_t op; int32_t zlo, zhi; };
 // where a burst leaves its result for the host: the pinned mirrors of the round state and of the control block, and the word the
 // host polls (the burst number) — written by k_publish, the last kernel of a burst, with system-scope stores: no copy commands, no
-// stream synchronisation on the host side (nullptr: the host copies and synchronises itself)
+// stream synchronisation on the host side
 struct BurstPublish { RoundState* host_rs; Ctl* host_ctl; unsigned long long* host_seq; };
 // footprint-check build (parbatch.hip, -DDSA_FP_CHECK): bits of RoundState::tight that select the check, and the bytes per op the
 // plan array carries behind the plans for the recorded read / touch sets and the final footprints

@@ -88,36 +88,22 @@ std::atomic<bool> g_models_off{false};      // an append-replay model kernel cou
 // ---- the one table of development switches (dsa_dev.h: dev_env) --------------------------------------------------------------------
 namespace dsa {
 static const char* const k_dev_switches[] = {
-    "DSA_APPEND_RUNS",    // 0: no append runs (per-op sequencer)
-    "DSA_BARRIER_CHUNK",  // n: first sequencer chunk after a stop at an op that cannot be planned
-    "DSA_BUILD_IDXSORT",  // 0: K-build always carries the values through the sort
-    "DSA_BUILD_MINMAX",   // 1: key ranges by the device scan even when the host knows them
-    "DSA_BUILD_TWIN",     // 0: the two orientations of a matrix are built independently from the triples
     "DSA_BUILD_WIDE",     // 1: K-build through the general (> 64-bit composite) path
-    "DSA_BURST_GRAPH",    // 0: rounds as eager launches instead of a cached graph
     "DSA_COUNT_MODEL",    // 0: bitmap-only append replay (no model v2)
-    "DSA_DBG_BURST", "DSA_DBG_RUN", "DSA_DBG_SPLIT", "DSA_DBG_SPMV", "DSA_DBG_SPMV_META", "DSA_DBG_TIME",      // timing / trace prints
+    "DSA_DBG_RUN", "DSA_DBG_SPLIT", "DSA_DBG_TIME",      // timing / trace prints
     "DSA_DBG_MOVE2",      // ablations of the rebalance kernel (wrong results, timed)
     "DSA_FAIL_BUILD",     // 1: fails the next bulk build (fault injection, tests)
     "DSA_FP_MODE",        // footprint-check build (-DDSA_FP_CHECK): 1 recorded read / write sets, 2 sequential shadow re-plan (parbatch.hip)
     "DSA_KEYS_WIDE",      // 1: 64-bit physical keys everywhere
     "DSA_LOCAL_ROUNDS",   // 0: no local rounds (grid rounds only)
-    "DSA_META_BLOCKS",    // workgroups of k_spmv_meta
     "DSA_MODEL3",         // 0: no count-only append replay
     "DSA_MODEL5",         // 0: no typed multi-level replay of 8-slot-segment append runs
-    "DSA_MOVE2_BLOCK", "DSA_MOVE2_TILE",      // workgroup / tile size of k_move2
     "DSA_PARBATCH",       // 0: no batch-parallel rounds
     "DSA_POS_WIDE",       // 1: 64-bit positions in the append replay
-    "DSA_PUBLISH",        // 0: device-to-host copies + stream synchronisation instead of the pinned hand-overs
     "DSA_RUN_AHEAD",      // 0: the rounds apply the conflict-free PREFIX only (rounds 2-5)
-    "DSA_SEQ_CHUNK",      // n: first sequencer chunk after a stop by short prefixes
-    "DSA_SMALL_BUILD",    // 0: small vectors through the general builder
-    "DSA_SMALL_ROUNDS",   // 0: small matrix batches on two sequencers
-    "DSA_SPMV_SHARE", "DSA_SPMV_STREAM", "DSA_SPMV_ZFILL", "DSA_SPMV_COMPACT",     // variants of the gather kernel
+    "DSA_SPMV_SHARE", "DSA_SPMV_STREAM",      // variants of the gather kernel
     "DSA_SPX_XDRIVEN",    // 0 / 1: the sparse-x product always through the gather kernel / always driven by x's entries
     "DSA_TIGHT",          // 0..3: tight footprints of leaf-accepted ops
-    "DSA_TOMBSTONE_PAR",  // 0: orientations one after the other whenever tombstones exist
-    "DSA_TWIN_ROUNDS",    // 0: the twin's deletes of deletecolumn! on a second sequencer
 };
 const char* dev_env(const char* name) {
 #ifndef NDEBUG
@@ -131,13 +117,25 @@ const char* dev_env(const char* name) {
 #endif
     return getenv(name);
 }
+
+hipError_t wait_pinned_seq(const volatile void* word, uint64_t want, hipStream_t s, uint64_t mask) {
+    const volatile unsigned long long* w = static_cast<const volatile unsigned long long*>(word);
+    auto published = [&] { return (__atomic_load_n(w, __ATOMIC_ACQUIRE) & mask) == want; };
+    auto next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
+    while (!published()) {
+        if (std::chrono::steady_clock::now() < next_query) continue;
+        const hipError_t q = hipStreamQuery(s);
+        if (q == hipErrorNotReady) { next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2); continue; }
+        if (q != hipSuccess) return q;
+        if (!published()) return hipErrorUnknown;
+    }
+    return hipSuccess;
+}
 }  // namespace dsa
 
 namespace {
-// dev knob: DSA_APPEND_RUNS=0 sends ascending append runs through the per-op sequencer path (A/B measurements)
 // default of Pma::wait_policy (DSA_WAIT_POLICY=1: yield-friendly waits for every new handle)
 const int g_wait_policy_default = [] { const char* e = getenv("DSA_WAIT_POLICY"); return (e && e[0] == '1') ? 1 : 0; }();
-const bool g_append_runs = [] { const char* e = dev_env("DSA_APPEND_RUNS"); return !(e && e[0] == '0'); }();
 
 // capacity = 2^ceil(Int, log2(ceil(n / t_h)))   src/pma.jl:64,81,88 (Float64 arithmetic, App. A.1)
 int64_t capacity_for(int64_t n) {
@@ -587,7 +585,7 @@ void upload_batch(Pma& P, const OpBatch& B) {
 // upload.  Vectors and MappedPackedCSC only — a plain PackedCSC has no runs
 void enqueue_op_breaks(Pma& P, int64_t n) {
     P.breaks_valid = false;
-    if (!g_append_runs || P.occ_old == nullptr || n < 64 || (P.has_sems && !P.has_cols)) return;
+    if (P.occ_old == nullptr || n < 64 || (P.has_sems && !P.has_cols)) return;
     hipError_t e = launch_op_breaks(P.d_ops, n, P.has_cols ? 1 : 0, P.d_breaks, P.stream);
     if (e != hipSuccess) fail(DSA_EHIP, std::string("op breaks launch: ") + hipGetErrorString(e));
     P.breaks_valid = true;
@@ -679,8 +677,7 @@ struct SeqRun {
 
 // Hand-over of a launch's result through pinned memory (parbatch.hip: k_publish; the sequencer does it in its own epilogue): the last kernel of the launch
 // writes the control block (and the round state) into the host's pinned mirrors and then a number into P.h_pub; the host polls for
-// that number instead of issuing device-to-host copies and synchronising the stream.  DSA_PUBLISH=0: copies + synchronisation.
-bool publish_enabled() { static const bool on = [] { const char* e = dev_env("DSA_PUBLISH"); return !(e && e[0] == '0'); }(); return on; }
+// that number instead of issuing device-to-host copies and synchronising the stream (dsa_dev.h: wait_pinned_seq).
 unsigned int next_publish_seq(Pma& P) {
     if (++P.pub_seq == 0) P.pub_seq = 1;
     return P.pub_seq;
@@ -692,19 +689,15 @@ unsigned int next_publish_seq(Pma& P) {
 void wait_policy_block(Pma& P) {
     if (P.wait_policy == 1) HIPCHK(hipStreamSynchronize(P.stream));
 }
-void wait_published(Pma& P) {
+// waits (after the policy's block) for the number `want` in the pinned `word` of a launch on P's stream; `what` names the operation in the error
+void wait_handover(Pma& P, const volatile void* word, uint64_t want, const char* what, uint64_t mask = ~0ull) {
     wait_policy_block(P);
-    // the stream is asked now and then so that a failed launch or a faulted kernel cannot hang the host
-    volatile unsigned long long* seqp = P.h_pub;
-    auto next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-    while ((unsigned int)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != P.pub_seq) {
-        if (std::chrono::steady_clock::now() < next_query) continue;
-        const hipError_t q = hipStreamQuery(P.stream);
-        if (q == hipErrorNotReady) { next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2); continue; }
-        if (q != hipSuccess) fail(DSA_EHIP, std::string("device work failed: ") + hipGetErrorString(q));
-        if ((unsigned int)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != P.pub_seq) fail(DSA_EHIP, "device work finished without publishing its state");
-    }
+    const hipError_t e = wait_pinned_seq(word, want, P.stream, mask);
+    if (e == hipErrorUnknown) fail(DSA_EHIP, std::string(what) + ": finished without publishing its result");
+    if (e != hipSuccess) fail(DSA_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+// the burst number k_publish / the sequencer's epilogue write is the low 32 bits of P.h_pub
+void wait_published(Pma& P) { wait_handover(P, P.h_pub, P.pub_seq, "device work", 0xffffffffull); }
 
 static thread_local double g_seq_launch_ms = 0;
 void seq_launch(SeqRun& r, bool upload = true) {
@@ -714,14 +707,11 @@ void seq_launch(SeqRun& r, bool upload = true) {
     // pinned h_ctl: H2D, kernel and D2H are stream-ordered; the host does not touch h_ctl until the next synchronize
     if (upload) HIPCHK(hipMemcpyAsync(P.d_ctl, P.h_ctl, sizeof(Ctl), hipMemcpyHostToDevice, P.stream));
     ++P.layout_epoch;
-    const bool publish = publish_enabled();
-    const unsigned int seq = publish ? next_publish_seq(P) : 0u;       // the sequencer hands its control block back itself
+    const unsigned int seq = next_publish_seq(P);       // the sequencer hands its control block back itself
     hipError_t e = launch_sequencer(P.K(), P.V(), P.O(), P.has_sems ? P.sems : nullptr, P.has_cols ? P.col_keys : nullptr,
                                     P.has_cols ? P.col_live : nullptr, P.d_ctl, P.d_ops, r.n, std::max(r.n, r.n_avail),
-                                    g_append_runs && P.occ_old != nullptr, P.breaks_valid ? P.d_breaks : nullptr,
-                                    publish ? P.h_ctl : nullptr, publish ? P.h_pub : nullptr, seq, P.stream);
+                                    P.occ_old != nullptr, P.breaks_valid ? P.d_breaks : nullptr, P.h_ctl, P.h_pub, seq, P.stream);
     if (e != hipSuccess) fail(DSA_EHIP, std::string("sequencer launch: ") + hipGetErrorString(e));
-    if (!publish) HIPCHK(hipMemcpyAsync(P.h_ctl, P.d_ctl, sizeof(Ctl), hipMemcpyDeviceToHost, P.stream));
 }
 
 void seq_start(SeqRun& r, Pma& P, const std::vector<Op>& ops) {
@@ -750,7 +740,7 @@ bool seq_step(SeqRun& r) {
     Pma& P = *r.P;
     {
         const auto tw0 = std::chrono::steady_clock::now();
-        if (publish_enabled()) wait_published(P); else HIPCHK(hipStreamSynchronize(P.stream));
+        wait_published(P);
         g_seq_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
     }
     Ctl& c = *P.h_ctl;
@@ -917,8 +907,7 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
     }
     P.h_ctl->next_op = 0; P.h_ctl->status = 0; P.h_ctl->err = 0; P.h_ctl->no_run_at = -1;
     upload_ctl(P);
-    static const int64_t SEQ_CHUNK0 = [] { const char* e = dev_env("DSA_SEQ_CHUNK"); return e ? (int64_t)atoi(e) : (int64_t)8; }();
-    static const int64_t BARRIER_CHUNK0 = [] { const char* e = dev_env("DSA_BARRIER_CHUNK"); return e ? (int64_t)atoi(e) : (int64_t)1; }();
+    constexpr int64_t SEQ_CHUNK0 = 8, BARRIER_CHUNK0 = 1;
     int64_t i = 0, seq_chunk = SEQ_CHUNK0;
     // run-ahead (parbatch.hip): a round applies every op that conflicts with no earlier one, the deferred ones wait in a pending list in
     // front of the fresh ops.  Only where no op can fail (a failing op must find exactly the ops in front of it applied): no tombstones,
@@ -946,7 +935,7 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
     // sequencer first, which detects the run (or, when the keys are not above the last cell after all, applies a few ops and hands
     // back to the rounds): a burst of rounds on ascending appends plans and applies one op per round (0.37 ms for nothing at 100 k ops)
     bool seq_first = false;
-    if (g_append_runs && P.occ_old != nullptr && n >= 64 && (!P.has_sems || P.has_cols)) {
+    if (P.occ_old != nullptr && n >= 64 && (!P.has_sems || P.has_cols)) {
         const int64_t probe = std::min<int64_t>(n, 256);
         seq_first = true;
         for (int64_t j = 0; j < probe && seq_first; ++j) {
@@ -974,11 +963,9 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
             rs.tight |= fp_mode == 2 ? FP_MODE_SHADOW : (fp_mode == 1 ? FP_MODE_SETS : 0);
         }
 #endif
-        // the burst hands its result back through pinned memory (k_publish) and the host polls for the burst number; DSA_PUBLISH=0: two
-        // device-to-host copies and a stream synchronisation instead
-        const bool publish = publish_enabled();
+        // the burst hands its result back through pinned memory (k_publish) and the host polls for the burst number
         rs.seq = (int32_t)next_publish_seq(P);
-        const BurstPublish pub = publish ? BurstPublish{P.h_rs, P.h_ctl, P.h_pub} : BurstPublish{nullptr, nullptr, nullptr};
+        const BurstPublish pub{P.h_rs, P.h_ctl, P.h_pub};
         HIPCHK(hipMemcpyAsync(P.d_rs, P.h_rs, sizeof(RoundState), hipMemcpyHostToDevice, P.stream));
         {
             ++P.layout_epoch;
@@ -995,24 +982,13 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
                                                     burst_rounds, burst_rounds == ROUNDS_PER_SYNC ? &P.burst : &P.burst_short, pub, P.stream);
             if (e != hipSuccess) fail(DSA_EHIP, std::string("burst launch: ") + hipGetErrorString(e));
         }
-        if (publish) {
-            wait_published(P);
-        } else {
-            HIPCHK(hipMemcpyAsync(P.h_rs, P.d_rs, sizeof(RoundState), hipMemcpyDeviceToHost, P.stream));
-            HIPCHK(hipMemcpyAsync(P.h_ctl, P.d_ctl, sizeof(Ctl), hipMemcpyDeviceToHost, P.stream));      // table_len, n_pending, counts of the burst
-            HIPCHK(hipStreamSynchronize(P.stream));
-        }
+        wait_published(P);
         t_burst += ms(tb0, now()); ++n_burst;
         if (use_local) { t_local += ms(tb0, now()); ++n_local; r_local += rs.rounds; o_local += rs.par_ops; }
         // the prefix of the last round of the burst has been applied but is folded into the cursor only by the next round's resolve step
         if (rs.pad >= 10) fail(DSA_EASSERT, "DSA_FP_CHECK: a round of the batch-parallel writes is not equivalent to the sequential order (code " + std::to_string(rs.pad) + ", details on stdout)");
         if (rs.pad == 9) fail(DSA_EASSERT, "batch-parallel writes: a deferred op left the zone it was sealed in (internal invariant of the run-ahead rounds)");
         if (rs.pad != 0) fail(DSA_EASSERT, "batch-parallel column creation left its footprint (internal invariant)");
-        static const bool dbg_burst = dev_env("DSA_DBG_BURST") != nullptr;
-        if (dbg_burst)
-            fprintf(stderr, "    burst%s: rounds %lld ops %lld (+ last prefix %d) stop %d G %d ema %.1f pending %lld table %lld/%lld cap %lld\n", use_local ? " (local)" : "",
-                    (long long)rs.rounds, (long long)rs.par_ops, rs.d, rs.stop, rs.G, rs.ema / 16.0, (long long)P.h_ctl->n_pending,
-                    (long long)P.h_ctl->table_len, (long long)P.h_ctl->table_cap, (long long)P.h_ctl->capacity);
         // what the sequencer takes after a stop: the op that cannot be planned alone when the rounds were otherwise making progress
         // (the ops behind it are cheaper in a round: ~1 us each against 5-15 us), a chunk of SEQ_CHUNK0 ops when short prefixes
         // stopped them (the ops around the cursor collide); doubled while the rounds apply fewer than two ops each
@@ -1205,23 +1181,14 @@ void ensure_q(Pma& P, int64_t n) {
 // batched getindex on the device; mode as in launch_get_batch
 void get_batch(Pma& P, int mode, const int64_t* qa, const int64_t* qb, int64_t n, double* out) {
     if (n <= 0) return;
-    if (n <= 64 && publish_enabled()) {
+    if (n <= 64) {
         // a scalar getindex or a handful of them: one launch that reads its queries from, and writes its answers to, pinned memory
         for (int64_t i = 0; i < n; ++i) { P.h_get[i] = qa[i]; P.h_get[64 + i] = qb ? qb[i] : 0; }
         const unsigned long long seq = ++P.get_seq;
         __atomic_thread_fence(__ATOMIC_RELEASE);
         hipError_t e = launch_get_small(mode, P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, P.h_get, (int)n, seq, P.stream);
         if (e != hipSuccess) fail(DSA_EHIP, std::string("get launch: ") + hipGetErrorString(e));
-        wait_policy_block(P);
-        volatile int64_t* seqp = P.h_get + 193;
-        auto next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-        while ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) {
-            if (std::chrono::steady_clock::now() < next_query) continue;
-            const hipError_t q = hipStreamQuery(P.stream);
-            if (q == hipErrorNotReady) { next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2); continue; }
-            if (q != hipSuccess) fail(DSA_EHIP, std::string("get: ") + hipGetErrorString(q));
-            if ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) fail(DSA_EHIP, "lookup kernel finished without publishing its result");
-        }
+        wait_handover(P, P.h_get + 193, seq, "get");
         std::memcpy(out, P.h_get + 128, (size_t)n * sizeof(double));
         const int32_t err = (int32_t)P.h_get[192];
         if (err) fail(err, err == DSA_EBOUNDS ? "partition index out of range" : "partition has no semaphore");
@@ -1246,7 +1213,7 @@ void get_batch(Pma& P, int mode, const int64_t* qa, const int64_t* qb, int64_t n
 
 // stored cells of the slot range [from, to] in slot order: K-pack on the device into the alternate buffer (free between
 // rebalances), then only the packed cells cross PCIe
-// the pinned landing area of views, small packs and small builds: 8 header words (meta [0..4], sequence number [5]) + 2 x 1024 cells
+// the pinned landing area of views, small packs and small builds: 8 header words (meta [0..4], sequence number [5], written last) + 2 x 1024 cells
 constexpr int64_t VIEW_AREA_CELLS = 1024;
 void ensure_view_area(Pma& P) {
     if (P.h_view) return;
@@ -1265,26 +1232,13 @@ struct ViewAreaLease {
         pinned_free(P.h_view); P.h_view = nullptr;
     }
 };
-// polls word [5] of the landing area for `seq` (the stream is asked now and then: a failed launch cannot hang the host)
-void wait_view_seq(Pma& P, unsigned long long seq, const char* what) {
-    wait_policy_block(P);
-    volatile int64_t* seqp = P.h_view + 5;
-    auto next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-    while ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) {
-        if (std::chrono::steady_clock::now() < next_query) continue;
-        const hipError_t q = hipStreamQuery(P.stream);
-        if (q == hipErrorNotReady) { next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2); continue; }
-        if (q != hipSuccess) fail(DSA_EHIP, std::string(what) + ": " + hipGetErrorString(q));
-        if ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) fail(DSA_EHIP, std::string(what) + ": kernel finished without publishing its result");
-    }
-}
 
 void view_small(Pma& P, int64_t col, int64_t range_from, int64_t range_to, std::vector<int64_t>& ks, std::vector<double>& vs);
 void read_range_general(Pma& P, int64_t from, int64_t to, std::vector<int64_t>& ks, std::vector<double>& vs);
 void read_range(Pma& P, int64_t from, int64_t to, std::vector<int64_t>& ks, std::vector<double>& vs) {
     // up to VIEW_SMALL_SLOTS slots (iteration over a small vector, a short slice): one launch that packs the cells and hands the first 512 to the
     // host through pinned memory (nonzeros() of a 100-entry vector: 80 -> 25 us); longer ranges: tile counts + scan + K-pack
-    if (to >= from && from >= 1 && to - from + 1 <= VIEW_SMALL_SLOTS && to - from + 1 <= P.cap_alloc && publish_enabled()) { view_small(P, 0, from, to, ks, vs); return; }
+    if (to >= from && from >= 1 && to - from + 1 <= VIEW_SMALL_SLOTS && to - from + 1 <= P.cap_alloc) { view_small(P, 0, from, to, ks, vs); return; }
     read_range_general(P, from, to, ks, vs);
 }
 void read_range_general(Pma& P, int64_t from, int64_t to, std::vector<int64_t>& ks, std::vector<double>& vs) {
@@ -1520,10 +1474,9 @@ bool mat_build_both_dev(Pma& A, Pma& B, const int64_t* d_part, const int64_t* d_
 // uploads host arrays (any of them may be nullptr) and runs the device builder
 void pma_build_from_host(Pma& P, const int64_t* part, const int64_t* key, const double* val, int64_t nnz, int32_t combine,
                          int mode, int64_t nparts_explicit) {
-    static const bool small_build = [] { const char* e = dev_env("DSA_SMALL_BUILD"); return !(e && e[0] == '0'); }();
-    if (small_build && mode == 1 && part == nullptr && nnz >= 1 && nnz <= VIEW_AREA_CELLS && publish_enabled() && dev_env("DSA_FAIL_BUILD") == nullptr) {
+    if (mode == 1 && part == nullptr && nnz >= 1 && nnz <= VIEW_AREA_CELLS && dev_env("DSA_FAIL_BUILD") == nullptr) {
         // a small vector: ONE launch sorts, folds and packs the caller's pairs (read from the pinned landing area) in front of the slot
-        // buffers and hands the entry count back; then the spread.  130 -> ~45 us for 50 entries (DSA_SMALL_BUILD=0: the general builder)
+        // buffers and hands the entry count back; then the spread (the general builder: 130 us for 50 entries, this path ~45)
         KeyScan ks; ks.add(key, nnz);
         P.wide = !ks.fit32();
         ViewAreaLease lease(P);
@@ -1534,7 +1487,7 @@ void pma_build_from_host(Pma& P, const int64_t* part, const int64_t* key, const 
         __atomic_thread_fence(__ATOMIC_RELEASE);
         hipError_t e = launch_build_small_vec(P.h_view, (int)nnz, (int)VIEW_AREA_CELLS, combine, P.K(), P.V(), seq, P.stream);
         if (e != hipSuccess) fail(DSA_EHIP, std::string("small build launch: ") + hipGetErrorString(e));
-        wait_view_seq(P, seq, "small build");
+        wait_handover(P, P.h_view + 5, seq, "small build");
         const int64_t n = P.h_view[0];
         if (n < 1 || n > nnz) fail(DSA_EASSERT, "small build returned an impossible entry count");
         const int64_t capacity = capacity_for(n);
@@ -1677,10 +1630,9 @@ void mat_build_major_dev(dsa_mat* h, const int64_t* dI, const int64_t* dJ, const
         if (dbg_time) fprintf(stderr, "[mat_build_major] handles (streams, control blocks) %.2f ms\n", std::chrono::duration<double, std::milli>(tb0 - ti0).count());
         // the two orientations are independent structures on their own streams and both only read the triples: built side by side
         // (the rowmajor one on a helper thread; each build waits once for its cell / partition counts)
-        // large builds: ONE sort of the triples, the rowmajor orientation from the cells colmajor's emit leaves behind (mat_build_both_dev).
-        // DSA_BUILD_TWIN=0: two independent builds side by side, as in rounds 3-5 (A/B, coverage)
-        static const bool twin = [] { const char* e = dev_env("DSA_BUILD_TWIN"); return !(e && e[0] == '0'); }();
-        if (twin && nnz >= (1 << 16) && h->col.stream != h->row.stream && dev_env("DSA_FAIL_BUILD") == nullptr) {
+        // large builds: ONE sort of the triples, the rowmajor orientation from the cells colmajor's emit leaves behind (mat_build_both_dev);
+        // smaller ones, a shared stream or an injected failure: two independent builds side by side
+        if (nnz >= (1 << 16) && h->col.stream != h->row.stream && dev_env("DSA_FAIL_BUILD") == nullptr) {
             const bool both = mat_build_both_dev(h->col, h->row, dJ, dI, dV, nnz, wide_rows, wide_cols, cols, rows);
             if (!both) pma_build_dev(h->row, dI, dJ, dV, nnz, DSA_COMBINE_ADD, 0, 0, wide_cols, rows, cols);
             if (dbg_time) fprintf(stderr, "[mat_build_major] nnz=%lld both orientations (%s) %.1f ms\n", (long long)nnz, both ? "twin derived" : "general path",
@@ -1860,8 +1812,7 @@ void mat_apply_sets(dsa_mat* h, const int64_t* I, const int64_t* J, const double
         for (int64_t k = 0; k < n; ++k) { if (part_keys_of_ops[k] < running) return false; running = part_keys_of_ops[k]; }
         return true;
     };
-    static const bool tomb_par = [] { const char* e = dev_env("DSA_TOMBSTONE_PAR"); return !(e && e[0] == '0'); }();
-    const bool side_by_side_ok = no_tombstones || (tomb_par && n >= 128 && cannot_fail(h->col, J) && cannot_fail(h->row, I));
+    const bool side_by_side_ok = no_tombstones || (n >= 128 && cannot_fail(h->col, J) && cannot_fail(h->row, I));
     if (par && side_by_side_ok && n >= 128) {
         // batch-parallel rounds per orientation (writes to existing columns with disjoint footprints run concurrently; new
         // columns and anything else fall back to the sequential sequencer inside run_ops_parallel)
@@ -1918,8 +1869,7 @@ void mat_apply_sets(dsa_mat* h, const int64_t* I, const int64_t* J, const double
         // A small batch (a column or a few that arrive together, a row): the orientation in which its writes fall into MANY
         // partitions takes the local rounds (one wave per op: k_local_rounds), the one in which they share a few partitions — writes
         // into one column are ordered by nature — its sequencer, side by side.  16 writes of a new column: 218 -> ~120 us.
-        static const bool small_rounds = [] { const char* e = dev_env("DSA_SMALL_ROUNDS"); return !(e && e[0] == '0'); }();
-        if (small_rounds && par && n >= 8) {
+        if (par && n >= 8) {
             std::vector<int64_t> di(I, I + n), dj(J, J + n);
             std::sort(di.begin(), di.end()); std::sort(dj.begin(), dj.end());
             const int64_t ni = std::unique(di.begin(), di.end()) - di.begin(), nj = std::unique(dj.begin(), dj.end()) - dj.begin();
@@ -2009,38 +1959,21 @@ void view_small(Pma& P, int64_t col, int64_t range_from, int64_t range_to, std::
     const int64_t out_cap = std::min<int64_t>(P.cap_alloc, VIEW_SMALL_SLOTS);
     const int64_t spec = std::min<int64_t>(SPEC, out_cap);
     int64_t r[5] = {0, 0, 0, 0, 0};
-    if (publish_enabled()) {
+    {
         // the kernel writes the meta words and the first SPEC cells straight into a pinned landing area and then a sequence number: the host
-        // polls for it — no copy command, no stream synchronisation (60 -> 20 us per view; DSA_PUBLISH=0 = copies + synchronisation)
+        // polls for it — no copy command, no stream synchronisation (60 -> 20 us per view)
         ViewAreaLease lease(P);
         const unsigned long long seq = ++P.view_seq;
         hipError_t e = launch_view_small(P.K(), P.V(), P.O(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, P.capacity(), col,
                                          P.KA(alt), P.vals[alt], out_cap, P.d_small, P.h_view, SPEC, seq, range_from, range_to, P.stream);
         if (e != hipSuccess) fail(DSA_EHIP, std::string("view launch: ") + hipGetErrorString(e));
-        wait_policy_block(P);
-        volatile int64_t* seqp = P.h_view + 5;
-        auto next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-        while ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) {
-            if (std::chrono::steady_clock::now() < next_query) continue;
-            const hipError_t q = hipStreamQuery(P.stream);
-            if (q == hipErrorNotReady) { next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2); continue; }
-            if (q != hipSuccess) fail(DSA_EHIP, std::string("view: ") + hipGetErrorString(q));
-            if ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) fail(DSA_EHIP, "view kernel finished without publishing its result");
-        }
+        wait_handover(P, P.h_view + 5, seq, "view");
         for (int q = 0; q < 5; ++q) r[q] = P.h_view[q];
         const int64_t have = std::max<int64_t>(0, std::min<int64_t>(r[4], spec));
         ks.assign(P.h_view + 8, P.h_view + 8 + have);
         vs.resize((size_t)have);
         std::memcpy(vs.data(), P.h_view + 8 + SPEC, (size_t)have * sizeof(double));
         ks.resize((size_t)spec); vs.resize((size_t)spec);
-    } else {
-        hipError_t e = launch_view_small(P.K(), P.V(), P.O(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, P.capacity(), col,
-                                         P.KA(alt), P.vals[alt], out_cap, P.d_small, nullptr, 0, 0ull, range_from, range_to, P.stream);
-        if (e != hipSuccess) fail(DSA_EHIP, std::string("view launch: ") + hipGetErrorString(e));
-        ks.resize((size_t)spec); vs.resize((size_t)spec);
-        HIPCHK(hipMemcpyAsync(r, P.d_small, sizeof(r), hipMemcpyDeviceToHost, P.stream));
-        HIPCHK(hipMemcpyAsync(vs.data(), P.vals[alt], (size_t)spec * sizeof(double), hipMemcpyDeviceToHost, P.stream));
-        download_keys(P, ks.data(), P.keys[alt], spec);       // synchronises
     }
     if (r[2] != 0) { ks.clear(); vs.clear(); fail((int32_t)r[2], "partition has no semaphore"); }
     if (r[0] == 0) { ks.clear(); vs.clear(); return; }       // empty view: the column does not exist (src/views.jl:17,24)
@@ -2064,22 +1997,15 @@ DevView view_dev(Pma& P, int64_t col) {
     const int alt = 1 - P.cur;
     const int64_t out_cap = std::min<int64_t>(P.cap_alloc, VIEW_SMALL_SLOTS);
     int64_t r[6] = {0, 0, 0, 0, 0, 0};
-    if (publish_enabled()) {
+    {   // (the landing area is leased for the hand-over only)
         ViewAreaLease lease(P);
         const unsigned long long seq = ++P.view_seq;
         hipError_t e = launch_view_small(P.K(), P.V(), P.O(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, P.capacity(), col,
                                          P.KA(alt), P.vals[alt], out_cap, P.d_small, P.h_view, 0, seq, 0, 0, P.stream);
         if (e != hipSuccess) fail(DSA_EHIP, std::string("view launch: ") + hipGetErrorString(e));
-        wait_view_seq(P, seq, "view");
+        wait_handover(P, P.h_view + 5, seq, "view");
         for (int q = 0; q < 5; ++q) r[q] = P.h_view[q];
         r[5] = P.h_view[6];
-    } else {
-        hipError_t e = launch_view_small(P.K(), P.V(), P.O(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, P.capacity(), col,
-                                         P.KA(alt), P.vals[alt], out_cap, P.d_small, nullptr, 0, 0ull, 0, 0, P.stream);
-        if (e != hipSuccess) fail(DSA_EHIP, std::string("view launch: ") + hipGetErrorString(e));
-        HIPCHK(hipMemcpyAsync(P.h_small, P.d_small, sizeof(r), hipMemcpyDeviceToHost, P.stream));
-        HIPCHK(hipStreamSynchronize(P.stream));
-        for (int q = 0; q < 6; ++q) r[q] = P.h_small[q];
     }
     if (r[2] != 0) fail((int32_t)r[2], "partition has no semaphore");
     if (r[0] == 0) return dv;                                  // the column does not exist (src/views.jl:17,24)
@@ -2124,8 +2050,6 @@ void prefetch_spmv_meta(Pma& P) {
         std::memset(P.h_meta, 0, 8 * sizeof(int64_t));
         P.meta_seq = 0;
     }
-    { static const char* dbg = dev_env("DSA_DBG_SPMV_META"); if (dbg) fprintf(stderr, "prefetch_spmv_meta: launch for epoch %lld (cached %lld, in flight %lld)\n",
-                                                                               (long long)P.layout_epoch, (long long)P.spmv_meta.epoch, (long long)P.meta_inflight_epoch); }
     // the kernel writes its five words and then the sequence number straight into pinned host memory
     hipError_t e = launch_spmv_meta(P.sems, P.col_keys, P.h_ctl->table_len, P.h_ctl->capacity, P.d_meta,
                                     reinterpret_cast<unsigned long long*>(P.h_meta), ++P.meta_seq, P.stream);
@@ -2137,13 +2061,7 @@ const Pma::SpmvMeta& spmv_meta(Pma& P) {
     if (M.epoch == P.layout_epoch) return M;
     M = Pma::SpmvMeta();
     M.epoch = P.layout_epoch;
-    static const char* dbg = dev_env("DSA_DBG_SPMV_META");
-    if (!spmv_meta_applicable(P)) {     // tombstones: memset path
-        const Ctl& c = *P.h_ctl;
-        if (dbg) fprintf(stderr, "spmv_meta: has_cols %d table_len %lld nb_partitions %lld n_pending %lld\n", (int)P.has_cols, (long long)c.table_len,
-                         (long long)c.nb_partitions, (long long)c.n_pending);
-        return M;
-    }
+    if (!spmv_meta_applicable(P)) return M;     // tombstones: memset path
     M.epoch = -1;
     prefetch_spmv_meta(P);                      // no-op when the write batch has already enqueued it
     // wait for the sequence number: normally there already (the kernel was enqueued behind the write batch); a stream wait if it
@@ -2160,8 +2078,6 @@ const Pma::SpmvMeta& spmv_meta(Pma& P) {
     const int64_t* r = P.h_meta;
     M.ordered = r[4] == 0;
     M.max_extent = r[0]; M.max_gap = r[1]; M.first_key = r[2]; M.last_key = r[3];
-    if (dbg) fprintf(stderr, "spmv_meta: table_len %lld ordered %d max_extent %lld max_gap %lld first %lld last %lld\n", (long long)P.h_ctl->table_len,
-                     (int)M.ordered, (long long)M.max_extent, (long long)M.max_gap, (long long)M.first_key, (long long)M.last_key);
     return M;
 }
 
@@ -2323,21 +2239,12 @@ int32_t dsa_vec_nonzeros(dsa_vec_t* h, int64_t* keys, double* vals, int64_t cap,
 // K-pack of up to VIEW_SMALL_SLOTS slots by ONE launch, the count handed back through the pinned landing area of `P` (no tile counts, no scan, no
 // copy, no stream synchronisation: 50 -> 15 us); returns -1 when the range does not qualify
 static int64_t pack_small(Pma& P, KeyArr k, const double* v, const uint64_t* occ, int64_t from, int64_t to, KeyArr ok, double* ov, int64_t out_cap) {
-    if (!publish_enabled() || to < from || from < 1 || to - from + 1 > VIEW_SMALL_SLOTS || to - from + 1 > out_cap) return -1;
+    if (to < from || from < 1 || to - from + 1 > VIEW_SMALL_SLOTS || to - from + 1 > out_cap) return -1;
     ViewAreaLease lease(P);
     const unsigned long long seq = ++P.view_seq;
     hipError_t e = launch_view_small(k, v, occ, nullptr, nullptr, nullptr, 0, to, 0, ok, ov, out_cap, P.d_small, P.h_view, 0, seq, from, to, P.stream);
     if (e != hipSuccess) fail(DSA_EHIP, std::string("pack launch: ") + hipGetErrorString(e));
-    wait_policy_block(P);
-    volatile int64_t* seqp = P.h_view + 5;
-    auto next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-    while ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) {
-        if (std::chrono::steady_clock::now() < next_query) continue;
-        const hipError_t q = hipStreamQuery(P.stream);
-        if (q == hipErrorNotReady) { next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2); continue; }
-        if (q != hipSuccess) fail(DSA_EHIP, std::string("pack: ") + hipGetErrorString(q));
-        if ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) fail(DSA_EHIP, "pack kernel finished without publishing its result");
-    }
+    wait_handover(P, P.h_view + 5, seq, "pack");
     return P.h_view[4];
 }
 static int64_t vec_pack_alt(dsa_vec_t* h) {
@@ -2861,8 +2768,7 @@ int32_t dsa_mat_deletecolumn(dsa_mat_t* h, int64_t col) {      // src/matrix.jl:
     // the element deletes of the twin cannot fail and touch the other structure: the deletepartition! of the own orientation is launched
     // on its sequencer, the twin's deletes — different partitions, mostly disjoint footprints — go through the local rounds meanwhile
     // (one wave per op instead of one op after the other: 105 -> 60 us for a column of 16)
-    static const bool twin_rounds = [] { const char* e = dev_env("DSA_TWIN_ROUNDS"); return !(e && e[0] == '0'); }();
-    if (h->col.stream != h->row.stream && twin_rounds && !ops.empty()) {
+    if (h->col.stream != h->row.stream && !ops.empty()) {
         SeqRun rc;
         seq_start(rc, h->col, del);
         int32_t er = 0;
@@ -2893,8 +2799,7 @@ int32_t dsa_mat_deleterow(dsa_mat_t* h, int64_t row) {         // src/matrix.jl:
     std::vector<Op> ops;
     for (int64_t c : cols) ops.push_back(make_op(OP_MPCSC_SET, row, c, 0.0));     // colmajor[row, col] = 0
     std::vector<Op> del{make_op(OP_MPCSC_DELETECOLUMN, 0, row, 0.0)};
-    static const bool twin_rounds = [] { const char* e = dev_env("DSA_TWIN_ROUNDS"); return !(e && e[0] == '0'); }();
-    if (h->col.stream != h->row.stream && twin_rounds && !ops.empty()) {       // (as in deletecolumn!)
+    if (h->col.stream != h->row.stream && !ops.empty()) {       // (as in deletecolumn!)
         SeqRun rr;
         seq_start(rr, h->row, del);
         int32_t ec = 0;
@@ -3276,17 +3181,8 @@ int32_t dsa_mat_spmv_sparse_begin(dsa_mat_t* h, int32_t transpose, const int64_t
     spx_enqueue(h, transpose, xdriven, d_xi, d_xv, nx, ny, ncols, x.oi, x.ov, x.out_cap, x.d_count, x.pin, seq);
     x.res_stream = s;
     tq("enqueued");
-    // the count (and a short result) arrive in the landing area: poll, asking the stream now and then (a failed launch cannot hang the host)
-    wait_policy_block(P);
-    volatile long long* seqp = x.pin + 1;
-    auto next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-    while ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) {
-        if (std::chrono::steady_clock::now() < next_query) continue;
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipErrorNotReady) { next_query = std::chrono::steady_clock::now() + std::chrono::milliseconds(2); continue; }
-        if (q != hipSuccess) fail(DSA_EHIP, std::string("sparse-x product: ") + hipGetErrorString(q));
-        if ((unsigned long long)__atomic_load_n(seqp, __ATOMIC_ACQUIRE) != seq) fail(DSA_EHIP, "sparse-x product finished without publishing its result");
-    }
+    // the count (and a short result) arrive in the landing area (s is P's stream)
+    wait_handover(P, x.pin + 1, seq, "sparse-x product");
     x.res_count = x.pin[0];
     *n_out = x.res_count;
     tq("count back");

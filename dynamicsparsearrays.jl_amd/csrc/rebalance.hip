@@ -151,8 +151,7 @@ __global__ __launch_bounds__(1024) void k_tile_scan(const uint32_t* __restrict__
 // No count kernel, no scan kernel, no interpolation search: the time does not depend on how the cells are distributed
 // over the source window (uniform after a spread, packed to the left after appends, anything in between).
 // PACKED sources (K-build, pack! + _shrink!: cells are the first m slots) have closed-form prefixes and skip 1-3.
-constexpr int M2_TILE_BIG = 2048;      // source slots per workgroup (M2_TILE_SMALL: dev knob, see launch_rebalance)
-constexpr int M2_TILE_SMALL = 1024;
+constexpr int M2_TILE_BIG = 2048;      // source slots per workgroup (smaller and larger tiles: see launch_rebalance)
 
 struct Move2Args {
     KeyArr src_keys; const double* src_vals; const uint64_t* src_occ;
@@ -742,8 +741,7 @@ hipError_t launch_rebalance(KeyArr src_keys, const double* src_vals, const uint6
             a.ntiles = std::max<int64_t>(1, (m + M2_TILE_BIG - 1) / M2_TILE_BIG);
             a.status = nullptr; a.gen = 0; a.fault = nullptr;
             // (512 threads up to 8192 tiles like the general source)
-            static const int force_block_p = [] { const char* e = dev_env("DSA_MOVE2_BLOCK"); return e ? atoi(e) : 0; }();
-            const int block = force_block_p ? force_block_p : (a.ntiles <= 8192 ? 512 : 256);
+            const int block = a.ntiles <= 8192 ? 512 : 256;
             if (block == 512) {
                 if (a.src_keys.wide) hipLaunchKernelGGL((k_move2<true, true, 512, M2_TILE_BIG>), dim3((unsigned)a.ntiles), dim3(512), 0, stream, a);
                 else hipLaunchKernelGGL((k_move2<true, false, 512, M2_TILE_BIG>), dim3((unsigned)a.ntiles), dim3(512), 0, stream, a);
@@ -755,13 +753,10 @@ hipError_t launch_rebalance(KeyArr src_keys, const double* src_vals, const uint6
         }
         const int64_t Ws = src_we - src_ws + 1;
         // up to 2^24 slots: 8 waves per tile; above: 4.
-        // Tiles of 1024 slots (twice the workgroups, half the write phase each; DSA_MOVE2_TILE=1024) were measured in round 3 and LOSE:
+        // Tiles of 1024 slots (twice the workgroups, half the write phase each) were measured in round 3 and LOSE:
         // 2^20 slots 11.1 vs 10.1 us, 2^21 18.0 vs 15.0, 2^22 26.1 vs 25.2, 2^24 76.7 vs 77.7 — more status words to publish and poll.  Tiles of
         // 4096 slots (half the per-tile fixed work) bought nothing either: 8.6 vs 8.2 us at 2^20 with 512 threads, 8.0 with 1024 (and 72.6 vs 69 at 2^24)
-        static const int force_block = [] { const char* e = dev_env("DSA_MOVE2_BLOCK"); return e ? atoi(e) : 0; }();
-        static const int force_tile = [] { const char* e = dev_env("DSA_MOVE2_TILE"); return e ? atoi(e) : 0; }();
-        const int tile = force_tile == M2_TILE_SMALL ? M2_TILE_SMALL : M2_TILE_BIG;
-        a.ntiles = (Ws + tile - 1) / tile;
+        a.ntiles = (Ws + M2_TILE_BIG - 1) / M2_TILE_BIG;
         if (a.ntiles + (a.ntiles >> 6) + 2 > work->status_cap || work->status == nullptr) return hipErrorInvalidValue;
         if (++work->gen >= (1ull << 30)) {          // generation wrap: start over on a zeroed table
             hipError_t e = hipMemsetAsync(work->status, 0, (size_t)work->status_cap * sizeof(unsigned long long), stream);
@@ -772,17 +767,14 @@ hipError_t launch_rebalance(KeyArr src_keys, const double* src_vals, const uint6
         a.fault = work->status + work->status_cap - 1;              // the last word of the table is not a status word (alloc_work)
         // measured, 512 vs 256 threads (after the write phase lost two thirds of its instructions): 2^20 8.8 vs 10.4 us, 2^22 22.7 vs 25.0,
         // 2^23 38.5 vs 41.4, 2^24 69.2-70.8 vs 72.6-75.3, 2^25 135-141 vs 136-139, 2^26 285-296 vs 270-281 (1024 threads lose everywhere)
-        const int block = force_block ? force_block : (a.ntiles <= 8192 ? 512 : 256);
-#define DSA_MOVE2_LAUNCH(W_, B_, T_) hipLaunchKernelGGL((k_move2<false, W_, B_, T_>), dim3((unsigned)a.ntiles), dim3(B_), 0, stream, a)
-        const bool wide = a.src_keys.wide != 0;
-        if (tile == M2_TILE_SMALL) {
-            if (block == 512) { if (wide) DSA_MOVE2_LAUNCH(true, 512, M2_TILE_SMALL); else DSA_MOVE2_LAUNCH(false, 512, M2_TILE_SMALL); }
-            else { if (wide) DSA_MOVE2_LAUNCH(true, 256, M2_TILE_SMALL); else DSA_MOVE2_LAUNCH(false, 256, M2_TILE_SMALL); }
+        const int block = a.ntiles <= 8192 ? 512 : 256;
+        if (block == 512) {
+            if (a.src_keys.wide) hipLaunchKernelGGL((k_move2<false, true, 512, M2_TILE_BIG>), dim3((unsigned)a.ntiles), dim3(512), 0, stream, a);
+            else hipLaunchKernelGGL((k_move2<false, false, 512, M2_TILE_BIG>), dim3((unsigned)a.ntiles), dim3(512), 0, stream, a);
         } else {
-            if (block == 512) { if (wide) DSA_MOVE2_LAUNCH(true, 512, M2_TILE_BIG); else DSA_MOVE2_LAUNCH(false, 512, M2_TILE_BIG); }
-            else { if (wide) DSA_MOVE2_LAUNCH(true, 256, M2_TILE_BIG); else DSA_MOVE2_LAUNCH(false, 256, M2_TILE_BIG); }
+            if (a.src_keys.wide) hipLaunchKernelGGL((k_move2<false, true, 256, M2_TILE_BIG>), dim3((unsigned)a.ntiles), dim3(256), 0, stream, a);
+            else hipLaunchKernelGGL((k_move2<false, false, 256, M2_TILE_BIG>), dim3((unsigned)a.ntiles), dim3(256), 0, stream, a);
         }
-#undef DSA_MOVE2_LAUNCH
         return hipGetLastError();
     }
 }

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spmv_scatter(KeyArr keys, const do
     // matrix with any band / block structure gathers x from a range that its XCD already holds.
     const int64_t ntiles = (capacity + SP_TILE - 1) / SP_TILE;
     int64_t tile = blockIdx.x;
-    if (ntiles >= 64 && !(pattern & 4)) {                 // (pattern bit 2: dev knob DSA_DBG_SPMV=4 keeps the identity map)
+    if (ntiles >= 64 && !(pattern & 4)) {                 // (pattern bit 2 would keep the identity map; the host passes 0)
                                                           // grid = 8 * ceil(ntiles / 8): (xcd, i) -> xcd * per + i is onto [0, ntiles)
         const int64_t per = (ntiles + 7) / 8;
         tile = (int64_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
@@ -603,7 +603,6 @@ hipError_t launch_spmv_meta(const int64_t* sems, const int64_t* part_keys, int64
     // x 4 steps 12-15 us, 977 x 1 step 18-20 us, 64 x 16 steps 26-33 us: every workgroup costs a partial + a ticket at device scope)
     int64_t blocks = (table_len + 1023) / 1024;
     if (blocks > 256) blocks = std::max<int64_t>(256, std::min<int64_t>(SPMV_META_BLOCKS, table_len >> 12));
-    { static const char* e = dev_env("DSA_META_BLOCKS"); if (e && atoi(e) > 0 && blocks > atoi(e)) blocks = atoi(e); }
     hipLaunchKernelGGL(k_spmv_meta, dim3((unsigned)blocks), dim3(256), 0, stream, sems, part_keys, table_len, capacity, scratch, out6_pinned, seq);
     return hipGetLastError();
 }
@@ -630,9 +629,7 @@ static void launch_gather_t(int64_t grid, hipStream_t stream, KeyArr keys, const
 static hipError_t launch_spmv(bool scatter, int pattern, int mode, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
                               const int64_t* sems, const int64_t* part_keys, int64_t table_len, const double* x, int64_t nx,
                               double* y, int64_t ny, hipStream_t stream) {
-    { static const char* dbg = dev_env("DSA_DBG_SPMV"); if (dbg && pattern == 0) pattern = atoi(dbg) & 4; }
-    {   // dev knobs: DSA_SPMV_ZFILL=0 keeps the memset, DSA_SPMV_STREAM=nt|plain forces the stream policy
-        static const char* z = dev_env("DSA_SPMV_ZFILL"); if (z && z[0] == '0') mode &= ~1;
+    {   // dev knob: DSA_SPMV_STREAM=nt|plain forces the stream policy
         static const char* st = dev_env("DSA_SPMV_STREAM"); if (st) mode = (mode & ~2) | (st[0] == 'p' ? 2 : 0);
     }
     if (scatter) mode = 0;

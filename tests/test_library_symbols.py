@@ -206,7 +206,7 @@ def test_development_switches_are_one_table_and_off_by_default(dsa):
             used_dev |= set(re.findall(r'dev_env\("([A-Z0-9_]+)"\)', txt))
             used_plain |= set(re.findall(r'(?<![a-z_])getenv\("([A-Z0-9_]+)"\)', txt))
     assert used_plain <= config, used_plain - config
-    assert used_dev <= set(names), used_dev - set(names)
+    assert used_dev == set(names), used_dev ^ set(names)
     assert not (set(names) & config)
     # a child process without DSA_DEV reports the switches as ignored, one with DSA_DEV=1 as honoured
     code = ("import sys; sys.path.insert(0, %r); import dsa_loader; d = dsa_loader.load(); print(d.dev_switches(d.product())[1])" % ROOT)

@@ -509,6 +509,30 @@ constexpr int SPMV_META_WORDS = 3 * SPMV_META_BLOCKS + 1;     // its device scra
 // out6_pinned: six words of PINNED host memory — the five results, then `seq` (written last, system scope: the host polls for it)
 hipError_t launch_spmv_meta(const int64_t* sems, const int64_t* part_keys, int64_t table_len, int64_t capacity,
                             unsigned long long* scratch, unsigned long long* out6_pinned, unsigned long long seq, hipStream_t stream);
+// ---- column-swept plan of the gather orientation (spmv.hip: k_plan_pass, k_plan_scan, k_spmv_plan) ---------------------
+// Groups of PLAN_GROUP_SLOTS slots own the rows whose semaphore lies in them; slices of at most 65 536 columns.  Per (group, slice)
+// the group's cells of that slice in (row, column) order: (row index within the group << 16 | column - slice base), the value apart.
+constexpr int PLAN_GROUP_SHIFT = 12;
+constexpr int64_t PLAN_GROUP_SLOTS = int64_t(1) << PLAN_GROUP_SHIFT;
+constexpr int PLAN_ROWS = 1024;               // rows (partitions) per group the product kernel accumulates in LDS
+constexpr int PLAN_MAX_SLICES = 63;           // offsets of a group (slices + 1) are held one per lane
+constexpr int64_t PLAN_MAX_GROUPS = 4096;     // every group resident at once: 16 waves per CU
+struct PlanDev {
+    uint32_t* cell; double* val;              // cap_cells entries each
+    uint32_t* off;                            // groups x (slices + 1)
+    uint32_t* cnt;                            // groups x slices: cells per (group, slice)
+    uint32_t* gbase;                          // groups: first cell of the group
+    uint32_t* pfirst;                         // groups + 1: first partition (0-based id) of the group
+    uint32_t* nsem;                           // groups: partitions of the group
+    int64_t groups, width, cap_cells;
+    int32_t slices, pad_;
+};
+// count pass + scan + scatter (three launches on `stream`, no host wait); the scan writes {ok, cells} and then `seq` to out3_pinned
+hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t table_len, int64_t nx,
+                                  const PlanDev& pl, unsigned long long* out3_pinned, unsigned long long seq, hipStream_t stream);
+// y = P x from the plan (every row of [1, ny] written once, as the ZFILL gather does)
+hipError_t launch_spmv_plan(const PlanDev& pl, const int64_t* part_keys, int64_t table_len, const double* x, double* y, int64_t ny,
+                            hipStream_t stream);
 // y[key] += x[part_key[p]] * val, scatter form with fp64 atomics (the literal _mul loop nest)
 hipError_t launch_spmv_scatter(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
                                const int64_t* sems, const int64_t* part_keys, const uint8_t* part_live, int64_t table_len,

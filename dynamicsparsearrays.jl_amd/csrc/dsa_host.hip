@@ -101,6 +101,7 @@ static const char* const k_dev_switches[] = {
     "DSA_PARBATCH",       // 0: no batch-parallel rounds
     "DSA_POS_WIDE",       // 1: 64-bit positions in the append replay
     "DSA_RUN_AHEAD",      // 0: the rounds apply the conflict-free PREFIX only (rounds 2-5)
+    "DSA_SPMV_PLAN",      // 0: never build or use the column-swept SpMV plan
     "DSA_SPMV_SHARE", "DSA_SPMV_STREAM",      // variants of the gather kernel
     "DSA_SPX_XDRIVEN",    // 0 / 1: the sparse-x product always through the gather kernel / always driven by x's entries
     "DSA_TIGHT",          // 0..3: tight footprints of leaf-accepted ops
@@ -194,6 +195,19 @@ struct Pma {
                                  // second Python thread calls in with whatever device its thread last selected)
     int64_t layout_epoch = 0;
     int64_t stat_spmv_nomemset = 0;
+    // bumped by every C-ABI entry that can change a value or a slot (layout_epoch misses value-only overwrites): the SpMV plan's key
+    int64_t content_epoch = 0;
+    int64_t stat_spmv_plan = 0, stat_spmv_plan_builds = 0;
+    // column-swept SpMV plan of this orientation (spmv.hip: k_spmv_plan), keyed on (content epoch, layout epoch, nx, ny); built on the
+    // second product at one key, its usability handed over through h_meta[6..8] (ok, cells, sequence number)
+    struct SpmvPlan {
+        enum State { NONE, PENDING, USABLE, UNUSABLE } state = NONE;
+        int64_t content_epoch = -1, layout_epoch = -1, nx = -1, ny = -1, products = 0;
+        PlanDev dev{};
+        void* mem[2] = {nullptr, nullptr};      // cells + values, offsets + scratch
+        int64_t bytes = 0;
+        unsigned long long seq = 0;
+    } plan;
     struct SpmvMeta { int64_t epoch = -1; bool ordered = false; int64_t max_extent = 0, max_gap = 0, first_key = 0, last_key = 0; } spmv_meta;
     // its device side: scratch of k_spmv_meta, pinned landing area of the 5 result words, and the epoch a prefetch (enqueued behind
     // the write batch that changed the layout) is in flight for
@@ -222,6 +236,18 @@ void pma_free_buffers(Pma& P) {
     P.occ_old = nullptr;
 }
 
+// returns the plan's memory to the pool (after the work in flight on the stream that may still read it)
+void spmv_plan_drop(Pma& P) {
+    Pma::SpmvPlan& L = P.plan;
+    if (L.mem[0] || L.mem[1]) {
+        if (P.stream) (void)hipStreamSynchronize(P.stream);
+        pool_free(L.mem[0]); pool_free(L.mem[1]);
+    }
+    const unsigned long long seq = L.seq;
+    L = Pma::SpmvPlan();
+    L.seq = seq;
+}
+
 void pma_destroy(Pma& P) {
     if (P.stream) hipStreamSynchronize(P.stream);
     pma_free_buffers(P);
@@ -243,6 +269,7 @@ void pma_destroy(Pma& P) {
     pinned_free(P.h_small);
     pinned_free(P.h_view);
     if (P.ev_handoff) (void)hipEventDestroy(P.ev_handoff);
+    spmv_plan_drop(P);
     if (P.d_meta) hipFree(P.d_meta);
     pinned_free(P.h_meta);
     if (P.tmerge.sems2) hipFree(P.tmerge.sems2);
@@ -1113,10 +1140,13 @@ void pma_info(Pma& P, int64_t nb_partitions_or_len, int64_t* info) {
     info[11] = P.stat_par_rounds; info[12] = P.stat_par_ops; info[13] = P.stat_seq_ops;
     info[DSA_INFO_STAT_SPMV_NOMEMSET] = P.stat_spmv_nomemset;
     info[DSA_INFO_STAT_GRID_REBALANCES] = P.stat_grid_rebalances;
+    info[DSA_INFO_STAT_SPMV_PLAN] = P.stat_spmv_plan;
+    info[DSA_INFO_STAT_SPMV_PLAN_BUILDS] = P.stat_spmv_plan_builds;
     // HBM held by the structure: both slot buffers (keys, values, bitmap), the saved bitmap of append runs, the tables and the merge scratch
     info[DSA_INFO_HBM_BYTES] = 2 * (P.cap_alloc * (int64_t)(P.kb() + sizeof(double)) + P.occ_words * 8) + (P.occ_old ? P.occ_words * 8 : 0) +
                                (P.has_sems ? c.table_cap * 8 : 0) + (P.has_cols ? c.table_cap * 9 : 0) + 2 * P.tmerge_cap * 8 +
-                               (P.d_ops ? P.ops_cap * (int64_t)sizeof(Op) + (P.ops_cap / 64 + 8) * 8 : 0) + (P.d_opsrc ? P.opsrc_cap * 24 : 0);      // op array, run-break bitmap, batch columns
+                               (P.d_ops ? P.ops_cap * (int64_t)sizeof(Op) + (P.ops_cap / 64 + 8) * 8 : 0) + (P.d_opsrc ? P.opsrc_cap * 24 : 0) +      // op array, run-break bitmap, batch columns
+                               P.plan.bytes;      // the SpMV plan: 12 B per stored cell + offsets
 }
 
 void export_slots(Pma& P, int64_t* keys, double* vals, uint8_t* occ, int64_t cap) {
@@ -2046,8 +2076,9 @@ void prefetch_spmv_meta(Pma& P) {
     if (!P.d_meta) {
         HIPCHK(hipMalloc(&P.d_meta, SPMV_META_WORDS * sizeof(unsigned long long)));
         HIPCHK(hipMemsetAsync(P.d_meta, 0, SPMV_META_WORDS * sizeof(unsigned long long), P.stream));
-        HIPCHK(pinned_alloc(reinterpret_cast<void**>(&P.h_meta), 8 * sizeof(int64_t)));
-        std::memset(P.h_meta, 0, 8 * sizeof(int64_t));
+        // words 0..5: k_spmv_meta's results + sequence number; 6..8: the SpMV plan build's (ok, cells, sequence number)
+        HIPCHK(pinned_alloc(reinterpret_cast<void**>(&P.h_meta), 16 * sizeof(int64_t)));
+        std::memset(P.h_meta, 0, 16 * sizeof(int64_t));
         P.meta_seq = 0;
     }
     // the kernel writes its five words and then the sequence number straight into pinned host memory
@@ -2087,6 +2118,74 @@ void mat_prefetch_spmv_meta(dsa_mat* h) {
     prefetch_spmv_meta(h->col);
 }
 
+// ---- the column-swept plan (spmv.hip: k_spmv_plan) ----------------------------------------------------------------------------
+// Taken by a dense product over the gather orientation when x does not fit an XCD's L2 (the gathers of k_spmv_gather miss there) and
+// the ZFILL conditions hold (every row is written once).  Built on the SECOND product at one (content epoch, layout epoch, nx, ny) —
+// a caller who writes between every two products never pays for it —, as three kernels on the product's stream; the build reports
+// whether the plan is usable (rows per group within the LDS accumulators) through h_meta[6..8], read by the product after it.
+bool spmv_plan_on() { static const bool on = [] { const char* e = dev_env("DSA_SPMV_PLAN"); return !(e && e[0] == '0'); }(); return on; }
+
+int plan_slices(int64_t nx) { return (int)std::max<int64_t>(16, (nx + 65535) / 65536); }
+
+bool spmv_plan_shape_ok(const Pma& P, int64_t nx) {
+    const int64_t groups = (P.capacity() + PLAN_GROUP_SLOTS - 1) / PLAN_GROUP_SLOTS;
+    return groups <= PLAN_MAX_GROUPS && plan_slices(nx) <= PLAN_MAX_SLICES && P.h_ctl->nb_elements < ((int64_t)1 << 31);
+}
+
+void spmv_plan_build(Pma& P, int64_t nx, hipStream_t s) {
+    Pma::SpmvPlan& L = P.plan;
+    PlanDev& d = L.dev;
+    d.groups = (P.capacity() + PLAN_GROUP_SLOTS - 1) / PLAN_GROUP_SLOTS;
+    d.slices = plan_slices(nx);
+    d.width = (nx + d.slices - 1) / d.slices;
+    d.cap_cells = std::max<int64_t>(1, P.h_ctl->nb_elements - P.h_ctl->table_len);      // every stored entry but the semaphores
+    const int64_t G = d.groups, S = d.slices;
+    const int64_t words = G * (S + 1) + G * S + G + (G + 1) + G;                          // off, cnt, gbase, pfirst, nsem (uint32)
+    HIPCHK(pool_alloc(&L.mem[0], (size_t)d.cap_cells * (sizeof(uint32_t) + sizeof(double))));
+    HIPCHK(pool_alloc(&L.mem[1], (size_t)words * sizeof(uint32_t)));
+    L.bytes = d.cap_cells * 12 + words * 4;
+    d.val = static_cast<double*>(L.mem[0]);
+    d.cell = reinterpret_cast<uint32_t*>(d.val + d.cap_cells);
+    d.off = static_cast<uint32_t*>(L.mem[1]);
+    d.cnt = d.off + G * (S + 1);
+    d.gbase = d.cnt + G * S;
+    d.pfirst = d.gbase + G;
+    d.nsem = d.pfirst + G + 1;
+    unsigned long long* out = reinterpret_cast<unsigned long long*>(P.h_meta + 6);
+    hipError_t e = launch_spmv_plan_build(P.K(), P.V(), P.O(), P.capacity(), P.h_ctl->table_len, nx, d, out, ++L.seq, s);
+    if (e != hipSuccess) fail(DSA_EHIP, std::string("spmv plan build: ") + hipGetErrorString(e));
+    L.state = Pma::SpmvPlan::PENDING;
+    ++P.stat_spmv_plan_builds;
+}
+
+// true when the product was computed from the plan; otherwise counts the product and builds the plan on the second one
+bool spmv_plan_product(Pma& P, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s) {
+    Pma::SpmvPlan& L = P.plan;
+    if (L.content_epoch != P.content_epoch || L.layout_epoch != P.layout_epoch || L.nx != nx || L.ny != ny) {
+        spmv_plan_drop(P);
+        L.content_epoch = P.content_epoch; L.layout_epoch = P.layout_epoch; L.nx = nx; L.ny = ny;
+    }
+    ++L.products;
+    if (L.state == Pma::SpmvPlan::PENDING) {
+        HIPCHK(wait_pinned_seq(P.h_meta + 8, L.seq, s));
+        const bool ok = __atomic_load_n(P.h_meta + 6, __ATOMIC_ACQUIRE) == 1;
+        if (ok) L.state = Pma::SpmvPlan::USABLE;
+        else {      // the rows of a group do not fit the accumulators: k_spmv_gather at this key from now on
+            const int64_t ce = L.content_epoch, le = L.layout_epoch, pr = L.products;
+            spmv_plan_drop(P);
+            L.content_epoch = ce; L.layout_epoch = le; L.nx = nx; L.ny = ny; L.products = pr;
+            L.state = Pma::SpmvPlan::UNUSABLE;
+        }
+    }
+    if (L.state == Pma::SpmvPlan::USABLE) {
+        hipError_t e = launch_spmv_plan(L.dev, P.col_keys, P.h_ctl->table_len, d_x, d_y, ny, s);
+        if (e != hipSuccess) fail(DSA_EHIP, std::string("spmv plan launch: ") + hipGetErrorString(e));
+        ++P.stat_spmv_plan;
+        return true;
+    }
+    return false;
+}
+
 void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s,
               int pattern = 0) {
     if (!h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
@@ -2102,7 +2201,11 @@ void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, in
             ny - M.last_key <= MAX_FILL)
             { mode |= SPMV_ZFILL; ++P.stat_spmv_nomemset; }
         if (nx * (int64_t)sizeof(double) <= (3 << 20)) mode |= SPMV_PLAIN_STREAM;      // x stays in an XCD's 4 MB L2 beside the stream
+        const bool plan = spmv_plan_on() && pattern == 0 && (mode & SPMV_ZFILL) && !(mode & SPMV_PLAIN_STREAM) && s == P.stream &&
+                          nx > 0 && spmv_plan_shape_ok(P, nx);
+        if (plan && spmv_plan_product(P, d_x, nx, d_y, ny, s)) return;
         e = launch_spmv_gather(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, d_x, nx, d_y, ny, pattern, mode, s);
+        if (e == hipSuccess && plan && P.plan.state == Pma::SpmvPlan::NONE && P.plan.products == 2) spmv_plan_build(P, nx, s);
     } else if (algo == 1) {
         Pma& P = transpose ? h->row : h->col;
         e = launch_spmv_scatter(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, d_x, nx, d_y, ny, s);
@@ -2640,6 +2743,11 @@ static void fill_append(FillBuffer& b, const int64_t* I, const int64_t* J, const
     b.length += n;
 }
 
+// every C-ABI entry that can change a value or a slot of the matrix: the SpMV plans of both orientations are stale from here on
+static void mat_content_changed(dsa_mat_t* h) {
+    for (Pma* P : {&h->col, &h->row}) { ++P->content_epoch; spmv_plan_drop(*P); }
+}
+
 static void mat_flush(dsa_mat_t* h) {
     if (h->has_major) bind_device(h->col);
     if (h->pi.empty()) return;
@@ -2657,6 +2765,7 @@ int32_t dsa_mat_set(dsa_mat_t* h, double val, int64_t row, int64_t col) {
         fill_row_test_and_set(h->buf, row);
         fill_append(h->buf, &row, &col, &val, 1);
     } else {
+        mat_content_changed(h);
         h->pi.push_back(row); h->pj.push_back(col); h->pv.push_back(val);
         // with tombstones a write can hit the reference's assert / bounds paths: apply it now so the error surfaces here
         const bool tombstones = h->col.h_ctl->nb_partitions != h->col.h_ctl->table_len ||
@@ -2677,6 +2786,7 @@ int32_t dsa_mat_set_batch(dsa_mat_t* h, const int64_t* I, const int64_t* J, cons
         }
         fill_append(h->buf, I, J, V, n);
     } else {
+        mat_content_changed(h);
         mat_apply_sets(h, I, J, V, n);
         mat_prefetch_spmv_meta(h);
     }
@@ -2703,6 +2813,7 @@ int32_t dsa_mat_addrow(dsa_mat_t* h, int64_t row, const int64_t* colids, const d
         std::vector<int64_t> rows((size_t)n, row);       // (the reference stores the column ids of the row sorted: only its buffer views see that)
         fill_append(b, rows.data(), colids, vals, n);
     } else {               // src/matrix.jl:119-121
+        mat_content_changed(h);
         std::vector<int64_t> rows((size_t)n, row);
         mat_apply_sets(h, rows.data(), colids, vals, n);
         mat_prefetch_spmv_meta(h);
@@ -2714,6 +2825,7 @@ int32_t dsa_mat_closefillmode(dsa_mat_t* h) {     // closefillmode!  src/matrix.
     API_TRY
     mat_flush(h);
     if (!h->fillmode) fail(DSA_EMODE, "Cannot close fill mode because matrix is not in fill mode.");
+    mat_content_changed(h);
     // get_rowids_colids_vals (src/buffer.jl:33-50) is a no-op here: the triples already sit in HBM; only the last partial
     // chunk is still in pinned memory
     FillBuffer& b = h->buf;
@@ -2755,6 +2867,7 @@ int32_t dsa_mat_deletecolumn(dsa_mat_t* h, int64_t col) {      // src/matrix.jl:
     API_TRY
     mat_flush(h);
     if (h->fillmode) fail(DSA_EMODE, "Cannot delete a column in fill mode");
+    mat_content_changed(h);
     static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
     const auto td0 = std::chrono::steady_clock::now();
     std::vector<int64_t> rows; std::vector<double> vals;
@@ -2794,6 +2907,7 @@ int32_t dsa_mat_deleterow(dsa_mat_t* h, int64_t row) {         // src/matrix.jl:
     API_TRY
     mat_flush(h);
     if (h->fillmode) fail(DSA_EMODE, "Cannot delete a row in fill mode");
+    mat_content_changed(h);
     std::vector<int64_t> cols; std::vector<double> vals;
     col_view_of(h->row, row, cols, vals);
     std::vector<Op> ops;
@@ -2947,6 +3061,7 @@ int32_t dsa_mat_export_layout(dsa_mat_t* h, int32_t o, int64_t* keys, double* va
 int32_t dsa_mat_rebalance_root(dsa_mat_t* h, int32_t o) {
     API_TRY
     mat_flush(h);
+    mat_content_changed(h);
     Pma& P = orient(h, o);
     if (P.capacity() != P.h_ctl->segment_capacity) {
         P.h_ctl->stat_rebalances += 1; P.h_ctl->stat_window_slots += P.capacity();

@@ -661,6 +661,252 @@ static hipError_t launch_spmv(bool scatter, int pattern, int mode, KeyArr keys, 
     return hipGetLastError();
 }
 
+// ---- column-swept plan --------------------------------------------------------------------------------------------
+// With x larger than an XCD's L2, half of k_spmv_gather's gathers are 64-byte fabric misses.  The plan is a read-only copy of the
+// orientation, built on the device once per content epoch: group g (the rows whose semaphore lies in slots [g * 4096, (g + 1) * 4096))
+// keeps, per column slice s, its cells of that slice in (row, column) order.  k_spmv_plan gives each group to one wave; all waves are
+// resident and walk the slices in the same order, so an XCD gathers from one or two 0.5 MB slices at a time: L2 hits.
+// Build: k_plan_pass<false> counts per (group, slice), k_plan_scan places the groups, k_plan_pass<true> scatters in slot order (stable).
+constexpr uint32_t PLAN_NONE = 0xffffffffu;
+
+// one wave per group: its 64 words, then — for the row that is open at the group's end — the cells up to the next semaphore
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void k_plan_pass(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ,
+                                                   int64_t capacity, int64_t nx, PlanDev pl) {
+    __shared__ uint32_t sPos[SP_WAVES][PLAN_MAX_SLICES + 1];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t g = (int64_t)blockIdx.x * SP_WAVES + wv;
+    if (g >= pl.groups) return;                       // (whole waves: nothing below waits for another wave)
+    uint32_t* pos = sPos[wv];
+    const int P = pl.slices;
+    const uint32_t W = (uint32_t)pl.width;
+    if (SCATTER) {
+        const uint32_t c = lane < P ? pl.cnt[g * P + lane] : 0u;
+        // exclusive prefix of the slice counts across the lanes (P <= 63)
+        uint32_t incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+        const uint32_t start = pl.gbase[g] + incl - c;
+        if (lane <= P) { pos[lane] = start; pl.off[g * (P + 1) + lane] = start; }
+    } else {
+        pos[lane] = 0u;
+    }
+    __builtin_amdgcn_wave_barrier();
+    const int64_t nwords = (capacity + 63) >> 6;
+    const int64_t wg0 = g << (PLAN_GROUP_SHIFT - 6);
+    const int64_t wg1 = wg0 + (PLAN_GROUP_SLOTS >> 6) < nwords ? wg0 + (PLAN_GROUP_SLOTS >> 6) : nwords;
+    const uint64_t le = mask_lt(lane) | (1ull << lane);
+    int nsem = 0;
+    for (int64_t w = wg0; w < nwords; ++w) {
+        const bool tail = w >= wg1;
+        if (tail && nsem == 0) break;                 // no row of this group is open
+        const uint64_t word = occ[w];
+        const bool bit = (word >> lane) & 1ull;
+        int64_t key = -1;
+        double v = 0.0;
+        if (bit) { key = keys[(w << 6) + lane]; if (SCATTER) v = vals[(w << 6) + lane]; }
+        const uint64_t sm = __ballot(bit && key == SEM_KEY);
+        int row;
+        bool cell;
+        if (!tail) {
+            row = nsem + popc64(sm & le) - 1;         // the last semaphore at or in front of this slot, counted within the group
+            cell = bit && key != SEM_KEY && row >= 0;  // (row -1: the cells of a row that an earlier group owns)
+            nsem += popc64(sm);
+        } else {
+            const int lim = sm ? __ffsll((unsigned long long)sm) - 1 : 64;
+            row = nsem - 1;
+            cell = bit && lane < lim;
+        }
+        cell = cell && key >= 1 && key <= nx;        // a column outside x adds nothing to a row in k_spmv_gather either
+        const uint32_t col0 = cell ? (uint32_t)(key - 1) : 0u;
+        const uint32_t s = col0 / W;
+        uint64_t todo = __ballot(cell);
+        while (todo) {
+            const int leader = __ffsll((unsigned long long)todo) - 1;
+            const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane((int)s, leader);
+            const bool mine = cell && s == s0;
+            const uint64_t m = __ballot(mine);
+            const uint32_t base = pos[s0];
+            if (SCATTER && mine) {
+                const uint32_t idx = base + (uint32_t)popc64(m & mask_lt(lane));
+                if ((int64_t)idx < pl.cap_cells) {
+                    __builtin_nontemporal_store(((uint32_t)row << 16) | (col0 - s0 * W), pl.cell + idx);
+                    __builtin_nontemporal_store(v, pl.val + idx);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (lane == 0) pos[s0] = base + (uint32_t)popc64(m);
+            __builtin_amdgcn_wave_barrier();
+            todo &= ~m;
+        }
+        if (tail && sm) break;
+    }
+    if (!SCATTER) {
+        if (lane < P) pl.cnt[g * P + lane] = pos[lane];
+        if (lane == 0) pl.nsem[g] = (uint32_t)nsem;
+    }
+}
+
+// one workgroup: first cell and first partition of every group; {ok, cells} + sequence number to pinned memory
+constexpr int PLAN_SCAN_THREADS = 1024;
+__global__ __launch_bounds__(PLAN_SCAN_THREADS) void k_plan_scan(PlanDev pl, int64_t table_len, unsigned long long* __restrict__ out,
+                                                                 unsigned long long seq) {
+    constexpr int PER = PLAN_MAX_GROUPS / PLAN_SCAN_THREADS;
+    __shared__ unsigned long long sTot[PLAN_SCAN_THREADS], sSem[PLAN_SCAN_THREADS];
+    __shared__ unsigned int sBad;
+    const int t = threadIdx.x;
+    const int P = pl.slices;
+    if (t == 0) sBad = 0u;
+    unsigned long long tot[PER], sem[PER], ts = 0, ss = 0;
+    bool bad = false;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int64_t g = (int64_t)t * PER + q;
+        tot[q] = 0; sem[q] = 0;
+        if (g < pl.groups) {
+            for (int s = 0; s < P; ++s) tot[q] += pl.cnt[g * P + s];
+            sem[q] = pl.nsem[g];
+            bad = bad || sem[q] > (unsigned long long)PLAN_ROWS;
+        }
+        ts += tot[q]; ss += sem[q];
+    }
+    sTot[t] = ts; sSem[t] = ss;
+    __syncthreads();
+    if (bad) atomicOr(&sBad, 1u);
+    for (int o = 1; o < PLAN_SCAN_THREADS; o <<= 1) {             // inclusive scan (Hillis-Steele)
+        const unsigned long long a = t >= o ? sTot[t - o] : 0ull, b = t >= o ? sSem[t - o] : 0ull;
+        __syncthreads();
+        sTot[t] += a; sSem[t] += b;
+        __syncthreads();
+    }
+    unsigned long long rt = sTot[t] - ts, rs = sSem[t] - ss;
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+        const int64_t g = (int64_t)t * PER + q;
+        if (g < pl.groups) { pl.gbase[g] = (uint32_t)rt; pl.pfirst[g] = (uint32_t)rs; }
+        rt += tot[q]; rs += sem[q];
+    }
+    if (t == PLAN_SCAN_THREADS - 1) {
+        const unsigned long long cells = sTot[t], parts = sSem[t];
+        pl.pfirst[pl.groups] = (uint32_t)parts;
+        // usable: every group's rows fit the LDS accumulators, the cells fit the arrays, every partition was found by its semaphore
+        const bool ok = sBad == 0u && (long long)cells <= pl.cap_cells && (long long)parts == table_len && cells < 0xffffffffull;
+        __hip_atomic_store(out + 0, ok ? 1ull : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(out + 1, cells, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __atomic_thread_fence(__ATOMIC_RELEASE);
+        __hip_atomic_store(out + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t table_len, int64_t nx,
+                                  const PlanDev& pl, unsigned long long* out3_pinned, unsigned long long seq, hipStream_t stream) {
+    if (pl.groups <= 0 || pl.groups > PLAN_MAX_GROUPS || pl.slices <= 0 || pl.slices > PLAN_MAX_SLICES || pl.width <= 0 || pl.width > 65536)
+        return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((pl.groups + SP_WAVES - 1) / SP_WAVES);
+    hipLaunchKernelGGL(k_plan_pass<false>, dim3(grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, nx, pl);
+    hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(PLAN_SCAN_THREADS), 0, stream, pl, table_len, out3_pinned, seq);
+    hipLaunchKernelGGL(k_plan_pass<true>, dim3(grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, nx, pl);
+    return hipGetLastError();
+}
+
+// The product.  One wave per group, 4 independent waves per workgroup, all groups resident (<= 4096 groups, 32 KB of LDS per
+// workgroup).  Per slice the wave streams its cells 256 at a time (non-temporal: read once), gathers x, and adds each product to its
+// row's LDS accumulator.  A row's cells in a chunk of 64 lie on consecutive lanes; they are added one rank after the other, so every
+// row is 0.0 + its products in ascending column order — what k_spmv_gather computes for a row that one lane sums.  The first round of
+// slice s + 1 is requested behind the gathers of slice s.  At the end every row of the group is stored once, and the rows without a
+// partition in front of each row (behind the last one: up to ny) are zeroed, as the ZFILL gather does.  No atomics, no barriers.
+constexpr int PLAN_U = 4;          // chunks of 64 cells per round
+__global__ __launch_bounds__(SP_BLOCK) void k_spmv_plan(PlanDev pl, const int64_t* __restrict__ part_keys, int64_t table_len,
+                                                        const double* __restrict__ x, double* __restrict__ y, int64_t ny) {
+    __shared__ double sAcc[SP_WAVES][PLAN_ROWS];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t g = (int64_t)blockIdx.x * SP_WAVES + wv;
+    if (g >= pl.groups) return;
+    double* acc = sAcc[wv];
+    const uint32_t p0 = pl.pfirst[g];
+    const int np = (int)(pl.pfirst[g + 1] - p0);      // <= PLAN_ROWS (checked by the build)
+    for (int i = lane; i < np; i += 64) acc[i] = 0.0;
+    const int P = pl.slices;
+    const uint32_t W = (uint32_t)pl.width;
+    const uint32_t myoff = lane <= P ? pl.off[g * (P + 1) + lane] : 0u;
+    const uint32_t* __restrict__ cp = pl.cell;
+    const double* __restrict__ vp = pl.val;
+    __builtin_amdgcn_wave_barrier();
+
+    auto load_round = [&](uint32_t b, uint32_t e, uint32_t (&c)[PLAN_U], double (&v)[PLAN_U]) {
+#pragma unroll
+        for (int u = 0; u < PLAN_U; ++u) {
+            const uint32_t i = b + u * 64 + lane;
+            c[u] = PLAN_NONE; v[u] = 0.0;
+            if (i < e) { c[u] = __builtin_nontemporal_load(cp + i); v[u] = __builtin_nontemporal_load(vp + i); }
+        }
+    };
+    auto gather = [&](uint32_t base, const uint32_t (&c)[PLAN_U], double (&xq)[PLAN_U]) {      // (idle lanes read x[0])
+#pragma unroll
+        for (int u = 0; u < PLAN_U; ++u) xq[u] = x[c[u] != PLAN_NONE ? base + (c[u] & 0xffffu) : 0u];
+    };
+    auto apply = [&](const uint32_t (&c)[PLAN_U], const double (&v)[PLAN_U], const double (&xq)[PLAN_U]) {
+#pragma unroll
+        for (int u = 0; u < PLAN_U; ++u) {
+            const bool valid = c[u] != PLAN_NONE;
+            if (__ballot(valid) == 0ull) break;
+            const uint32_t row = c[u] >> 16;
+            const double p = v[u] * xq[u];
+            const uint32_t prow = (uint32_t)__shfl_up((int)row, 1, 64);
+            const uint64_t heads = __ballot(valid && (lane == 0 || prow != row));
+            const int rank = lane - (63 - __clzll(heads & (mask_lt(lane) | (1ull << lane))));
+            // the adds of one row in rank (= column) order; rows are distinct within one rank
+            for (int r = 0;; ++r) {
+                if (valid && rank == r && row < (uint32_t)PLAN_ROWS) acc[row] = acc[row] + p;
+                __builtin_amdgcn_wave_barrier();
+                if (__ballot(valid && rank > r) == 0ull) break;
+            }
+        }
+    };
+
+    uint32_t cA[PLAN_U], cB[PLAN_U];
+    double vA[PLAN_U], vB[PLAN_U], xq[PLAN_U];
+#pragma unroll
+    for (int u = 0; u < PLAN_U; ++u) { cB[u] = PLAN_NONE; vB[u] = 0.0; }
+    uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)myoff, 0), e = (uint32_t)__builtin_amdgcn_readlane((int)myoff, 1);
+    load_round(b, e, cA, vA);
+    for (int s = 0; s < P; ++s) {
+        const uint32_t xbase = (uint32_t)s * W;      // < nx <= 63 * 65536
+        gather(xbase, cA, xq);
+        uint32_t nb = 0, ne = 0;
+        if (s + 1 < P) {
+            nb = (uint32_t)__builtin_amdgcn_readlane((int)myoff, s + 1);
+            ne = (uint32_t)__builtin_amdgcn_readlane((int)myoff, s + 2);
+            load_round(nb, ne, cB, vB);
+        }
+        apply(cA, vA, xq);
+        for (uint32_t r = b + PLAN_U * 64; r < e; r += PLAN_U * 64) {      // (long slices: the rest of the slice, round by round)
+            load_round(r, e, cA, vA);
+            gather(xbase, cA, xq);
+            apply(cA, vA, xq);
+        }
+#pragma unroll
+        for (int u = 0; u < PLAN_U; ++u) { cA[u] = cB[u]; vA[u] = vB[u]; }
+        b = nb; e = ne;
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (int i = lane; i < np; i += 64) {
+        const uint32_t id = p0 + (uint32_t)i;
+        const int64_t row = part_keys[id];
+        const int64_t prev = id > 0 ? part_keys[id - 1] : 0;
+        zero_fill_front(y, ny, prev, row, (int64_t)id + 1 == table_len);
+        if (row >= 1 && row <= ny) y[row - 1] = acc[i];
+    }
+}
+
+hipError_t launch_spmv_plan(const PlanDev& pl, const int64_t* part_keys, int64_t table_len, const double* x, double* y, int64_t ny,
+                            hipStream_t stream) {
+    if (pl.groups <= 0 || pl.groups > PLAN_MAX_GROUPS) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((pl.groups + SP_WAVES - 1) / SP_WAVES);
+    hipLaunchKernelGGL(k_spmv_plan, dim3(grid), dim3(SP_BLOCK), 0, stream, pl, part_keys, table_len, x, y, ny);
+    return hipGetLastError();
+}
+
 hipError_t launch_spmv_gather(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
                               const int64_t* sems, const int64_t* part_keys, const uint8_t*, int64_t table_len,
                               const double* x, int64_t nx, double* y, int64_t ny, int pattern, int mode, hipStream_t stream) {

@@ -63,11 +63,14 @@ enum {
     DSA_INFO_STAT_PAR_OPS = 12,
     DSA_INFO_STAT_SEQ_OPS = 13,
     DSA_INFO_STAT_SPMV_NOMEMSET = 14, /* instrumentation: gather SpMV launches over this orientation that needed no memset of y */
-    DSA_INFO_HBM_BYTES = 15,          /* bytes of HBM the structure holds (slot buffers x 2, bitmaps, tables, merge scratch) */
+    DSA_INFO_HBM_BYTES = 15,          /* bytes of HBM the structure holds (slot buffers x 2, bitmaps, tables, merge scratch, SpMV plan) */
     DSA_INFO_STAT_GRID_REBALANCES = 16, /* instrumentation: launches of the grid-wide pack/spread kernel (windows above 8192 slots, root, _extend!, _shrink!).
                                          * Windows an append run rebalances are replayed on the bitmap (csrc/appendmodel.hip) and moved by ONE K-permute
                                          * at the end of the run, whatever their size: they count in STAT_REBALANCES / STAT_WINDOW_SLOTS, not here. */
-    DSA_INFO_COUNT = 17
+    DSA_INFO_STAT_SPMV_PLAN = 17,       /* instrumentation: dense products over this orientation computed from its column-swept plan */
+    DSA_INFO_STAT_SPMV_PLAN_BUILDS = 18,/* instrumentation: builds of that plan (one per content epoch, nx, ny at most; DSA_INFO_HBM_BYTES
+                                         * counts the plan while it is held: 12 B per stored cell + a small offset table) */
+    DSA_INFO_COUNT = 19
 };
 
 typedef struct dsa_vec dsa_vec_t;    /* DynamicSparseVector   src/vector.jl:1-4   */

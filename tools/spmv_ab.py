@@ -2,7 +2,8 @@
 """A/B of the gather kernel (dev tool): time y = A x on the three shapes bench.py reports — config 3 (uniformly random columns, x = 8 MB),
 the banded extra (every gather an L2 hit), the final config-5 matrix (2^21 slots, x = 400 KB) — with HIP events around N launches, and
 print y's bytes as a sha256 so that two variants of the kernel (run this tool once per library — DSA_DEV=1 DSA_LIBRARY=<another build of csrc/> —
-or per setting of the development switches, e.g. DSA_DEV=1 DSA_SPMV_SHARE=0) can be compared bit for bit (the banded shape has two
+or per setting of the development switches, e.g. DSA_DEV=1 DSA_SPMV_SHARE=0, or DSA_DEV=1 DSA_SPMV_PLAN=0: the gather kernel where the
+column-swept plan would run) can be compared bit for bit (the banded shape has two
 rows longer than a span: their sums are joined by atomics and may differ in the last bits from run to run).  usage: python3 tools/spmv_ab.py [c3] [banded] [c4] [c5]"""
 import ctypes as C
 import hashlib
@@ -32,7 +33,17 @@ def run(name, A, nx, ny, x, reps=40):
     xd = torch.from_numpy(x).to(dev)
     yd = torch.zeros(ny, dtype=torch.float64, device=dev)
     fn = lambda: hip.call("mat_spmv_dense_dev", A.h, 0, 0, C.c_void_p(xd.data_ptr()), nx, C.c_void_p(yd.data_ptr()), ny)  # noqa: E731
-    for _ in range(5):
+    # the first two products, each timed alone: the second one carries the plan's build where the plan applies
+    first = []
+    for _ in range(2):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        fn()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        first.append(round(e0.elapsed_time(e1) * 1e3, 2))
+    for _ in range(3):
         fn()
     torch.cuda.synchronize()
     best = []
@@ -46,7 +57,8 @@ def run(name, A, nx, ny, x, reps=40):
         best.append(e0.elapsed_time(e1) * 1e3 / reps)
     y = yd.cpu().numpy()
     out[name] = {"us_median": round(float(np.median(best)), 2), "us_min": round(float(min(best)), 2), "capacity": A.info(dsa.ROWMAJOR)["capacity"],
-                 "y_sha256": hashlib.sha256(y.tobytes()).hexdigest()[:16], "y_sum": float(y.sum())}
+                 "y_sha256": hashlib.sha256(y.tobytes()).hexdigest()[:16], "y_sum": float(y.sum()), "first_two_products_us": first,
+                 "plan_products": A.info(dsa.ROWMAJOR)["stat_spmv_plan"], "plan_builds": A.info(dsa.ROWMAJOR)["stat_spmv_plan_builds"]}
 
 
 if "c3" in which:

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Summarises rocprofv3 output directories into profiles/: usage
-   summarize_prof.py <tag> <kernel-trace dir> <fetch dir> <write dir>"""
+   summarize_prof.py <tag> <kernel-trace dir> <fetch dir> <write dir> [<plan fetch dir> <plan write dir> <plan TCC hit/miss dir>]
+The first three come from tools/prof_kernels.py (with DSA_DEV=1 DSA_SPMV_PLAN=0 where the column-swept plan exists: its dispatch order is
+the gather kernel's); the optional three from `tools/spmv_ab.py c3`, whose headline product is k_spmv_plan (PMC per dispatch of it)."""
 import collections
 import csv
 import glob
@@ -54,6 +56,22 @@ if mv:
                                "corrected_fetch": round(2 * sum(f) / 3 * KB),
                                "corrected_traffic_total": round(2 * sum(f) / 3 * KB + sum(w) / 3 * KB),
                                "algorithmic_bytes": 32 * 16777216}
+if len(sys.argv) >= 8:
+    PF, PW, PT = per_kernel(sys.argv[5]), per_kernel(sys.argv[6]), None
+    tcc = collections.defaultdict(lambda: collections.defaultdict(list))
+    for f in glob.glob(os.path.join(sys.argv[7], "**", "*counter_collection.csv"), recursive=True):
+        for r in csv.DictReader(open(f)):
+            tcc[r["Kernel_Name"].split("(")[0]][r["Counter_Name"]].append(float(r["Counter_Value"]))
+    for name, tag_ in (("k_spmv_plan", "k_spmv_plan_C3"), ("k_spmv_gather", "k_spmv_gather_C3_in_plan_run")):
+        ks = [k for k in PF if name in k]
+        if not ks:
+            continue
+        f, w = PF[ks[0]], PW.get(ks[0], [])
+        t = next((v for k, v in tcc.items() if name in k), {})
+        hit, miss = sum(t.get("TCC_HIT_sum", [0.0])), sum(t.get("TCC_MISS_sum", [0.0]))
+        res[tag_] = {"dispatches": len(f), "FETCH_SIZE_mean": round(sum(f) / len(f) * KB),
+                     "WRITE_SIZE_mean": round(sum(w) / len(w) * KB) if w else None,
+                     "TCC_hit_rate": round(hit / (hit + miss), 4) if hit + miss > 0 else None}
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402  (kernel_source_sha: bench.py quotes this file only while the kernel sources are unchanged)
 res["kernel_source_sha"] = bench.kernel_source_sha()

@@ -425,6 +425,77 @@ class DynamicSparseMatrix(_Handle):
     def rebalance_root(self, orientation):
         self.b.call("mat_rebalance_root", self.h, orientation)
 
+    # ---- compressed export (include/dsa.h: dsa_mat_to_compressed[_dev]; HIP library only) ----------------------------------------
+    def _require_export(self):
+        if not self.b.has("mat_to_compressed"):
+            raise B.DsaArgumentError(B.EARG, "compressed export needs the HIP product library")
+
+    def _compressed(self, orientation, base):
+        self._require_export()
+        m, n = self.size()
+        outer = m if orientation == ROWMAJOR else n
+        cap = self.nnz()
+        ptr = np.empty(outer + 1, dtype=np.int64)
+        idx = np.empty(max(cap, 1), dtype=np.int64)
+        val = np.empty(max(cap, 1), dtype=np.float64)
+        got = C.c_int64()
+        self.b.call("mat_to_compressed", self.h, orientation, int(base), ptr.ctypes.data_as(P_I64), idx.ctypes.data_as(P_I64),
+                    val.ctypes.data_as(P_F64), cap, C.byref(got))
+        return ptr, idx[:got.value], val[:got.value]
+
+    def to_csr(self, base=0):
+        """scipy-style (indptr, indices, data) of the rows 1..m, int64 indices counted from `base` (0 or 1)"""
+        return self._compressed(ROWMAJOR, base)
+
+    def to_csc(self, base=0):
+        """scipy-style (indptr, indices, data) of the columns 1..n, int64 indices counted from `base` (0 or 1)"""
+        return self._compressed(COLMAJOR, base)
+
+    def findnz(self):
+        """findnz(m): 1-based (I, J, V) of the stored entries in column-major order (SparseArrays.findnz)"""
+        ptr, rows, vals = self.to_csc(base=1)
+        cols = np.repeat(np.arange(1, len(ptr), dtype=np.int64), np.diff(ptr))
+        return rows, cols, vals
+
+    def to_compressed_dev(self, orientation, d_ptr, d_idx, d_vals, cap, index_bits=64, base=0):
+        """the compressed form into device memory (device addresses, e.g. tensor.data_ptr()); enqueued on the orientation's stream
+        (sync()); returns nnz"""
+        self._require_export()
+        got = C.c_int64()
+        self.b.call("mat_to_compressed_dev", self.h, int(orientation), int(index_bits), int(base), C.c_void_p(int(d_ptr)),
+                    C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)), int(cap), C.byref(got))
+        return got.value
+
+    def to_torch(self, layout, index_dtype=None):
+        """torch.sparse_csr_tensor (layout torch.sparse_csr, from rowmajor) or torch.sparse_csc_tensor (torch.sparse_csc, from
+        colmajor) of size(m) on the current device; the arrays never leave HBM"""
+        import torch
+        self._require_export()
+        if index_dtype is None:
+            index_dtype = torch.int64
+        if layout not in (torch.sparse_csr, torch.sparse_csc):
+            raise B.DsaArgumentError(B.EARG, "layout must be torch.sparse_csr or torch.sparse_csc")
+        if index_dtype not in (torch.int32, torch.int64):
+            raise B.DsaArgumentError(B.EARG, "index_dtype must be torch.int32 or torch.int64")
+        orientation = ROWMAJOR if layout == torch.sparse_csr else COLMAJOR
+        m, n = self.size()
+        outer = m if orientation == ROWMAJOR else n
+        nnz = self.nnz()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        ptr = torch.empty(outer + 1, dtype=index_dtype, device=dev)
+        idx = torch.empty(max(nnz, 1), dtype=index_dtype, device=dev)
+        val = torch.empty(max(nnz, 1), dtype=torch.float64, device=dev)
+        # the library writes on the orientation's stream: the fresh blocks must be free of torch's pending work first, and torch's
+        # consumers of the result must start after the export has finished
+        torch.cuda.current_stream(dev).synchronize()
+        got = self.to_compressed_dev(orientation, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nnz,
+                                     index_bits=32 if index_dtype == torch.int32 else 64)
+        self.sync()
+        idx, val = idx[:got], val[:got]
+        if orientation == ROWMAJOR:
+            return torch.sparse_csr_tensor(ptr, idx, val, size=(m, n))
+        return torch.sparse_csc_tensor(ptr, idx, val, size=(m, n))
+
     def check(self, orientation):
         """device-side invariant checker (HIP library only): report[2..6] must be 0."""
         r = np.zeros(8, dtype=np.int64)

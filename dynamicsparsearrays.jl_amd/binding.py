@@ -155,6 +155,14 @@ _DEVICE_SIGS = {
 }
 
 
+# entry points bound for the product library only (PREFIX "dsa").  Kept out of SIGNATURES, which a harness binding another library with
+# the same call shapes filters by a fixed list of names: a name added there would be looked up in that library too.
+_PRODUCT_ONLY_SIGS = {
+    "mat_to_compressed_dev": [VP, I32, I32, I32, VP, VP, VP, I64, P_I64],
+    "mat_to_compressed": [VP, I32, I32, P_I64, P_I64, P_F64, I64, P_I64],
+}
+
+
 def _i64(a):
     a = np.ascontiguousarray(a, dtype=np.int64)
     return a, a.ctypes.data_as(P_I64)
@@ -171,12 +179,16 @@ SIGNATURES = {**_SIGS, **_DEVICE_SIGS}
 class Binding:
     PREFIX = "dsa"
     SIGNATURES = SIGNATURES
+    PRODUCT_SIGNATURES = _PRODUCT_ONLY_SIGS
 
     def __init__(self, path: str):
         self.path = path
         self.prefix = self.PREFIX
         self.lib = C.CDLL(path)
-        for name, argtypes in self.SIGNATURES.items():
+        sigs = dict(self.SIGNATURES)
+        if self.prefix == Binding.PREFIX:
+            sigs.update(self.PRODUCT_SIGNATURES)
+        for name, argtypes in sigs.items():
             fn = getattr(self.lib, f"{self.prefix}_{name}")   # AttributeError if the symbol is missing
             fn.argtypes = argtypes
             fn.restype = I32
@@ -187,7 +199,11 @@ class Binding:
 
     @classmethod
     def declared_symbols(cls):
-        return list(cls.SIGNATURES) + ["last_error_message"]
+        return list(cls.SIGNATURES) + list(cls.PRODUCT_SIGNATURES) + ["last_error_message"]
+
+    def has(self, name):
+        """whether this binding bound the entry point `name` (the product-only ones exist on the product library alone)"""
+        return hasattr(self, "_" + name)
 
     def call(self, name, *args):
         rc = getattr(self, "_" + name)(*args)

@@ -1,0 +1,300 @@
+// csrc/compress.hip — K-compress: the stored entries of one orientation in compressed form (CSC from colmajor, CSR from rowmajor).
+//
+// A cell at slot s belongs to the partition of the last semaphore in front of it, and the k-th semaphore in slot order is the k-th
+// live partition (the tables are in key order at every API boundary).  With O(s) = occupied slots in front of s and R(s) = semaphores
+// at or in front of s, the cell goes to position O(s) - R(s) of idx / val, and the partition whose semaphore sits at s starts at
+// O(s) - R(s) + 1.  Three launches, no host wait in between:
+//   k_cx_count  one wave per 2048-slot tile: occupied slots (a popcount of the tile's 32 bitmap words); the table: live semaphores per tile
+//   k_cx_scan   one workgroup: exclusive prefixes of both counts, the totals checked against the host's counts, ptr behind the last
+//               live partition
+//   k_cx_emit   one wave per tile: keys and values streamed once (non-temporal), cells to idx / val, and at every semaphore the ptr run
+//               from the previous live key up to its own (as zero_fill_front does for the rows of y); the last workgroup hands the
+//               error word to pinned memory
+// The slot arrays, the tables and both epochs stay untouched.  Bytes: (kb + 8) * capacity + capacity / 8 (+ the bitmap once more in
+// k_cx_count) + 17 * table_len in, (ib + 8) * nnz + ib * (dim + 1) out.
+#include "compress.h"
+#include <climits>
+#include <type_traits>
+
+namespace dsa {
+
+constexpr int CX_TILE_SHIFT = 11;                        // 2048 slots = 32 bitmap words: one wave (8192 waves for 2^24 slots)
+constexpr int64_t CX_TILE = int64_t(1) << CX_TILE_SHIFT;
+constexpr int CX_WORDS = (int)(CX_TILE >> 6);
+constexpr int CX_U = 8;                                  // bitmap words whose keys and values a wave requests at once
+constexpr int CX_SCAN_THREADS = 1024;
+
+// scratch: the four per-tile arrays, then the error word and the ticket of the emit (the memset covers sem_cnt .. ticket)
+struct CxScratch {
+    int64_t* occ_off; int64_t* sem_off;                  // exclusive prefixes (k_cx_scan)
+    uint32_t* occ_cnt; uint32_t* sem_cnt;                // per tile
+    uint32_t* err; uint32_t* ticket;
+    int64_t tiles;
+};
+static CxScratch cx_carve(void* base, int64_t tiles) {
+    CxScratch s;
+    s.occ_off = static_cast<int64_t*>(base);
+    s.sem_off = s.occ_off + tiles;
+    s.occ_cnt = reinterpret_cast<uint32_t*>(s.sem_off + tiles);
+    s.sem_cnt = s.occ_cnt + tiles;
+    s.err = s.sem_cnt + tiles;
+    s.ticket = s.err + 1;
+    s.tiles = tiles;
+    return s;
+}
+static int64_t cx_tiles(int64_t capacity) { return capacity > 0 ? (capacity + CX_TILE - 1) >> CX_TILE_SHIFT : 1; }
+size_t compress_scratch_bytes(int64_t capacity) { return (size_t)cx_tiles(capacity) * 24 + 8; }
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
+    return v;
+}
+
+// blocks [0, tile_blocks): four tiles each; the rest: 256 table entries each.  Live semaphores ascend with the id, so the entries of
+// a wave fall into few tiles: one atomic per (wave, tile).
+__global__ __launch_bounds__(256) void k_cx_count(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
+                                                  const uint8_t* __restrict__ col_live, int64_t table_len, int64_t tile_blocks, CxScratch s) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if ((int64_t)blockIdx.x < tile_blocks) {
+        const int64_t t = (int64_t)blockIdx.x * 4 + wv;
+        if (t >= s.tiles) return;
+        const int64_t w = t * CX_WORDS + lane, nwords = (capacity + 63) >> 6;
+        int c = lane < CX_WORDS && w < nwords ? popc64(__builtin_nontemporal_load(occ + w)) : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if (lane == 0) s.occ_cnt[t] = (uint32_t)c;
+        return;
+    }
+    const int64_t i = ((int64_t)blockIdx.x - tile_blocks) * 256 + threadIdx.x;
+    int64_t tile = -1;
+    uint32_t bad = 0;
+    if (i < table_len) {
+        const int64_t sp = sems[i];
+        const bool live = col_live == nullptr || col_live[i] != 0;
+        if ((sp != 0) != live || sp < 0 || sp > capacity) bad = 2;          // tables out of step with each other or with the slots
+        else if (sp != 0) tile = (sp - 1) >> CX_TILE_SHIFT;
+    }
+    uint64_t todo = __ballot(tile >= 0);
+    while (todo) {
+        const int leader = __ffsll((unsigned long long)todo) - 1;
+        const int64_t t0 = (int64_t)readlane64((uint64_t)tile, leader);
+        const uint64_t m = __ballot(tile == t0);
+        if (lane == leader) atomicAdd(s.sem_cnt + t0, (uint32_t)popc64(m));
+        todo &= ~m;
+    }
+    bad = wave_or(bad);
+    if (lane == 0 && bad) atomicOr(s.err, bad);
+}
+
+// one workgroup: occ_off / sem_off; totals against the host's counts; ptr[k] = base + nnz for k from the last live key to dim_out
+template <typename IT>
+__global__ __launch_bounds__(CX_SCAN_THREADS) void k_cx_scan(CxScratch s, const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
+                                                             int64_t table_len, int64_t nparts, int64_t nnz, int64_t dim_out, int64_t base,
+                                                             IT* __restrict__ ptr) {
+    __shared__ unsigned long long sO[CX_SCAN_THREADS], sS[CX_SCAN_THREADS];
+    __shared__ long long sLast;
+    const int t = threadIdx.x;
+    constexpr int PER = 8;
+    unsigned long long carry_o = 0, carry_s = 0;
+    for (int64_t c0 = 0; c0 < s.tiles; c0 += (int64_t)CX_SCAN_THREADS * PER) {
+        unsigned long long vo[PER], vs[PER], to = 0, ts = 0;
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const int64_t i = c0 + (int64_t)t * PER + q;
+            vo[q] = i < s.tiles ? s.occ_cnt[i] : 0u;
+            vs[q] = i < s.tiles ? s.sem_cnt[i] : 0u;
+            to += vo[q]; ts += vs[q];
+        }
+        sO[t] = to; sS[t] = ts;
+        __syncthreads();
+        for (int o = 1; o < CX_SCAN_THREADS; o <<= 1) {          // inclusive scan (Hillis-Steele)
+            const unsigned long long a = t >= o ? sO[t - o] : 0ull, b = t >= o ? sS[t - o] : 0ull;
+            __syncthreads();
+            sO[t] += a; sS[t] += b;
+            __syncthreads();
+        }
+        unsigned long long ro = carry_o + sO[t] - to, rs = carry_s + sS[t] - ts;
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const int64_t i = c0 + (int64_t)t * PER + q;
+            if (i < s.tiles) { s.occ_off[i] = (int64_t)ro; s.sem_off[i] = (int64_t)rs; }
+            ro += vo[q]; rs += vs[q];
+        }
+        carry_o += sO[CX_SCAN_THREADS - 1]; carry_s += sS[CX_SCAN_THREADS - 1];
+        __syncthreads();
+    }
+    // the last live partition (tombstones at the end of the tables are skipped, 1024 entries per step)
+    if (t == 0) sLast = -1;
+    __syncthreads();
+    for (int64_t hi = table_len - 1; hi >= 0; hi -= CX_SCAN_THREADS) {
+        const int64_t i = hi - t;
+        if (i >= 0 && sems[i] != 0) atomicMax(&sLast, (long long)i);
+        __syncthreads();
+        const bool found = sLast >= 0;
+        __syncthreads();
+        if (found) break;
+    }
+    const int64_t c_last = sLast >= 0 ? col_keys[sLast] : INT64_MIN;
+    if (t == 0) {
+        uint32_t e = 0;
+        if ((int64_t)carry_s != nparts || (int64_t)(carry_o - carry_s) != nnz) e |= 2u;
+        if (c_last <= 0 && nnz > 0) e |= 1u;                    // every stored entry lies in a partition whose key is below 1
+        if (e) atomicOr(s.err, e);
+    }
+    const IT v = (IT)(base + nnz);
+    for (int64_t k = (c_last > 0 ? c_last : 0) + t; k <= dim_out; k += CX_SCAN_THREADS) __builtin_nontemporal_store(v, ptr + k);
+}
+
+struct CxArgs {
+    void* ptr; void* idx; double* val;
+    int64_t dim_out, dim_in, nnz, base;
+    unsigned long long* pinned;         // {error word, sequence number}
+    unsigned long long seq;
+};
+
+// one wave per tile.  Error bits: 1 a stored entry outside size(m), 2 slots and tables disagree.
+template <bool WIDE, typename IT>
+__global__ __launch_bounds__(256) void k_cx_emit(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ,
+                                                 int64_t capacity, const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
+                                                 int64_t table_len, CxScratch s, CxArgs a) {
+    typedef typename std::conditional<WIDE, int64_t, int32_t>::type key_t;
+    const key_t* __restrict__ kp = static_cast<const key_t*>(keys.p);
+    IT* __restrict__ ptr = static_cast<IT*>(a.ptr);
+    IT* __restrict__ idx = static_cast<IT*>(a.idx);
+    __shared__ uint32_t sErr[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t t = (int64_t)blockIdx.x * 4 + wv;
+    const uint64_t below = mask_lt(lane);
+    uint32_t err = 0;
+    if (t < s.tiles) {
+        const int64_t w0 = t * CX_WORDS, nwords = (capacity + 63) >> 6;
+        const uint64_t myword = lane < CX_WORDS && w0 + lane < nwords ? __builtin_nontemporal_load(occ + w0 + lane) : 0ull;
+        int64_t run_o = s.occ_off[t], run_r = s.sem_off[t];
+        int64_t c_run = 0;
+        bool have_prev = false;          // c_run holds the key of the last semaphore seen in this tile
+        for (int q = 0; q < CX_WORDS; q += CX_U) {
+            uint64_t wd[CX_U];
+            int64_t k[CX_U], ck[CX_U];
+            double v[CX_U];
+#pragma unroll
+            for (int u = 0; u < CX_U; ++u) {
+                wd[u] = readlane64(myword, q + u);
+                const int64_t i = ((w0 + q + u) << 6) + lane;
+                k[u] = -1; v[u] = 0.0;
+                if ((wd[u] >> lane) & 1ull) { k[u] = (int64_t)__builtin_nontemporal_load(kp + i); v[u] = __builtin_nontemporal_load(vals + i); }
+            }
+#pragma unroll
+            for (int u = 0; u < CX_U; ++u) {        // keys of the partitions whose semaphores these words hold (semaphore value = id)
+                ck[u] = 0;
+                if (k[u] == SEM_KEY) {
+                    const int64_t p = (int64_t)v[u];
+                    if (p >= 1 && p <= table_len) ck[u] = col_keys[p - 1]; else err |= 2u;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < CX_U; ++u) {
+                const bool bit = (wd[u] >> lane) & 1ull;
+                const bool sem = bit && k[u] == SEM_KEY;
+                const uint64_t sb = __ballot(sem);
+                const int64_t o = run_o + popc64(wd[u] & below);                  // occupied slots in front of this one
+                const int64_t r = run_r + popc64(sb & below) + (sem ? 1 : 0);     // semaphores up to this one
+                if (bit && !sem) {
+                    const int64_t pos = o - r;
+                    if (pos >= 0 && pos < a.nnz) {
+                        __builtin_nontemporal_store((IT)(k[u] - 1 + a.base), idx + pos);
+                        __builtin_nontemporal_store(v[u], a.val + pos);
+                    } else {
+                        err |= 2u;
+                    }
+                    if (k[u] < 1 || k[u] > a.dim_in) err |= 1u;
+                }
+                if (sb) {
+                    // key of the previous live partition: the semaphore in front in this word, the last one of an earlier word of this
+                    // tile, or (first semaphore of the tile) the table, skipping tombstones
+                    const uint64_t pm = sb & below;
+                    const int src = pm ? 63 - __clzll(pm) : 0;
+                    const int64_t c_sh = __shfl(ck[u], src, 64);
+                    if (sem) {
+                        int64_t c_prev;
+                        if (pm) c_prev = c_sh;
+                        else if (have_prev) c_prev = c_run;
+                        else {
+                            int64_t j = (int64_t)v[u] - 2;
+                            while (j >= 0 && sems[j] == 0) --j;
+                            c_prev = j >= 0 ? col_keys[j] : INT64_MIN;
+                        }
+                        const int64_t st = o - r + 1;                 // cells of the partitions in front of this one
+                        const int64_t c = ck[u];
+                        if (c_prev <= 0 && c >= 1 && st != 0) err |= 1u;                          // cells in partitions keyed below 1
+                        if (c_prev <= a.dim_out && c > a.dim_out && st != a.nnz) err |= 1u;     // ... or above dim_out
+                        const int64_t lo = c_prev > 0 ? c_prev : 0, hi = c - 1 < a.dim_out ? c - 1 : a.dim_out;
+                        const IT pv = (IT)(a.base + st);
+                        for (int64_t kk = lo; kk <= hi; ++kk) __builtin_nontemporal_store(pv, ptr + kk);
+                    }
+                    c_run = __shfl(ck[u], 63 - __clzll(sb), 64);
+                    have_prev = true;
+                }
+                run_o += popc64(wd[u]);
+                run_r += popc64(sb);
+            }
+        }
+    }
+    err = wave_or(err);
+    if (lane == 0) sErr[wv] = err;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    err = sErr[0] | sErr[1] | sErr[2] | sErr[3];
+    if (err) __hip_atomic_fetch_or(s.err, err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_amdgcn_s_waitcnt(0);
+    const uint32_t tk = __hip_atomic_fetch_add(s.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tk != gridDim.x - 1) return;
+    // the last workgroup: every other one has added its bits before taking its ticket
+    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a.pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    __hip_atomic_store(a.pinned + 1, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+template <bool WIDE, typename IT>
+static void launch_emit_t(unsigned grid, hipStream_t stream, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
+                          const int64_t* sems, const int64_t* col_keys, int64_t table_len, const CxScratch& s, const CxArgs& a) {
+    hipLaunchKernelGGL((k_cx_emit<WIDE, IT>), dim3(grid), dim3(256), 0, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
+}
+
+hipError_t launch_to_compressed(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems,
+                                const int64_t* col_keys, const uint8_t* col_live, int64_t table_len, int64_t nparts, int64_t nnz,
+                                int64_t dim_out, int64_t dim_in, int32_t index_bits, int64_t base, void* d_ptr, void* d_idx, double* d_vals,
+                                void* scratch, unsigned long long* out2_pinned, unsigned long long seq, hipStream_t stream) {
+    if (capacity < 0 || table_len < 0 || dim_out < 0 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
+    const int64_t tiles = cx_tiles(capacity);
+    const CxScratch s = cx_carve(scratch, tiles);
+    hipError_t e = hipMemsetAsync(s.sem_cnt, 0, (size_t)tiles * sizeof(uint32_t) + 8, stream);
+    if (e != hipSuccess) return e;
+    const int64_t tile_blocks = (tiles + 3) / 4, table_blocks = (table_len + 255) / 256;
+    hipLaunchKernelGGL(k_cx_count, dim3((unsigned)(tile_blocks + table_blocks)), dim3(256), 0, stream, occ, capacity, sems, col_live,
+                       table_len, tile_blocks, s);
+    if (index_bits == 32)
+        hipLaunchKernelGGL(k_cx_scan<int32_t>, dim3(1), dim3(CX_SCAN_THREADS), 0, stream, s, sems, col_keys, table_len, nparts, nnz, dim_out,
+                           base, static_cast<int32_t*>(d_ptr));
+    else
+        hipLaunchKernelGGL(k_cx_scan<int64_t>, dim3(1), dim3(CX_SCAN_THREADS), 0, stream, s, sems, col_keys, table_len, nparts, nnz, dim_out,
+                           base, static_cast<int64_t*>(d_ptr));
+    CxArgs a{d_ptr, d_idx, d_vals, dim_out, dim_in, nnz, base, out2_pinned, seq};
+    const unsigned grid = (unsigned)tile_blocks;
+    if (keys.wide) {
+        if (index_bits == 32) launch_emit_t<true, int32_t>(grid, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
+        else launch_emit_t<true, int64_t>(grid, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
+    } else {
+        if (index_bits == 32) launch_emit_t<false, int32_t>(grid, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
+        else launch_emit_t<false, int64_t>(grid, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace dsa

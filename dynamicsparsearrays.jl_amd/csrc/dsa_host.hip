@@ -9,6 +9,7 @@
 // There is no CPU fallback for any slot operation.
 #include "../../include/dsa.h"
 #include "dsa_dev.h"
+#include "compress.h"
 
 #include <dlfcn.h>
 #include <sys/mman.h>
@@ -212,6 +213,8 @@ struct Pma {
     // its device side: scratch of k_spmv_meta, pinned landing area of the 5 result words, and the epoch a prefetch (enqueued behind
     // the write batch that changed the layout) is in flight for
     unsigned long long* d_meta = nullptr; int64_t* h_meta = nullptr; unsigned long long meta_seq = 0; int64_t meta_inflight_epoch = -1;
+    // compressed export (compress.hip): per-tile counts and prefixes (pooled, grown on demand), pinned {error word, sequence number}
+    void* cx_scratch = nullptr; size_t cx_bytes = 0; unsigned long long* h_cx = nullptr; unsigned long long cx_seq = 0;
     // thresholds  src/pma.jl:58,70,87
     double t_h = 0.7, t_0 = 0.92, p_h = 0.3, p_0 = 0.08, t_d = 0.0, p_d = 0.0;
 
@@ -272,6 +275,8 @@ void pma_destroy(Pma& P) {
     spmv_plan_drop(P);
     if (P.d_meta) hipFree(P.d_meta);
     pinned_free(P.h_meta);
+    pool_free(P.cx_scratch);
+    pinned_free(P.h_cx);
     if (P.tmerge.sems2) hipFree(P.tmerge.sems2);
     if (P.tmerge.keys2) hipFree(P.tmerge.keys2);
     if (P.tmerge.pkey) hipFree(P.tmerge.pkey);
@@ -3067,6 +3072,79 @@ int32_t dsa_mat_rebalance_root(dsa_mat_t* h, int32_t o) {
         P.h_ctl->stat_rebalances += 1; P.h_ctl->stat_window_slots += P.capacity();
         root_rebalance(P, P.capacity(), P.capacity(), P.h_ctl->nb_elements, false);
     }
+    API_CATCH
+}
+
+// ---- compressed export (compress.hip): CSC from colmajor, CSR from rowmajor; read-only (no epoch moves, a cached SpMV plan survives)
+static void to_compressed_dev(dsa_mat_t* h, int32_t o, int32_t index_bits, int32_t index_base, void* d_ptr, void* d_idx, double* d_vals,
+                              int64_t cap, int64_t* nnz_out) {
+    mat_flush(h);
+    if (h->fillmode || !h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
+    Pma& P = orient(h, o);
+    if (!nnz_out) fail(DSA_EARG, "nnz_out is NULL");
+    if (index_bits != 32 && index_bits != 64) fail(DSA_EARG, "index_bits must be 32 or 64");
+    if (index_base != 0 && index_base != 1) fail(DSA_EARG, "index_base must be 0 or 1");
+    const int64_t parts = P.h_ctl->nb_partitions, nnz = P.h_ctl->nb_elements - parts;
+    const int64_t dim_out = o == DSA_ROWMAJOR ? h->m : h->n, dim_in = o == DSA_ROWMAJOR ? h->n : h->m;
+    *nnz_out = nnz;
+    if (index_bits == 32 && (dim_out > INT32_MAX || dim_in > INT32_MAX || nnz + index_base > INT32_MAX))
+        fail(DSA_EARG, "a dimension or nnz does not fit 32-bit indices");
+    if (cap < nnz) fail(DSA_ECAP, "output buffers too small");
+    if (!d_ptr || (nnz > 0 && (!d_idx || !d_vals))) fail(DSA_EARG, "output pointer is NULL");
+    const size_t need = compress_scratch_bytes(P.capacity());
+    if (P.cx_bytes < need) {
+        if (P.cx_scratch) { HIPCHK(hipStreamSynchronize(P.stream)); pool_free(P.cx_scratch); P.cx_scratch = nullptr; P.cx_bytes = 0; }
+        HIPCHK(pool_alloc(&P.cx_scratch, need));
+        P.cx_bytes = need;
+    }
+    if (!P.h_cx) {
+        HIPCHK(pinned_alloc(reinterpret_cast<void**>(&P.h_cx), 2 * sizeof(unsigned long long)));
+        std::memset(P.h_cx, 0, 2 * sizeof(unsigned long long));
+        P.cx_seq = 0;
+    }
+    const unsigned long long seq = ++P.cx_seq;
+    hipError_t e = launch_to_compressed(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, parts, nnz,
+                                        dim_out, dim_in, index_bits, index_base, d_ptr, d_idx, d_vals, P.cx_scratch, P.h_cx, seq, P.stream);
+    if (e != hipSuccess) fail(DSA_EHIP, std::string("compressed export launch: ") + hipGetErrorString(e));
+    wait_handover(P, P.h_cx + 1, seq, "compressed export");
+    const unsigned long long err = __atomic_load_n(P.h_cx, __ATOMIC_ACQUIRE);
+    if (err & 2u) fail(DSA_EASSERT, "compressed export: slot array and partition tables disagree");
+    if (err & 1u) fail(DSA_EBOUNDS, "a stored entry lies outside size(m)");
+}
+int32_t dsa_mat_to_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t index_bits, int32_t index_base,
+                                  void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out) {
+    API_TRY
+    to_compressed_dev(h, orientation, index_bits, index_base, d_ptr, d_idx, d_vals, cap, nnz_out);
+    API_CATCH
+}
+int32_t dsa_mat_to_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_base,
+                              int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out) {
+    API_TRY
+    mat_flush(h);
+    if (h->fillmode || !h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
+    Pma& P = orient(h, orientation);
+    if (!ptr || !nnz_out) fail(DSA_EARG, "output pointer is NULL");
+    const int64_t nnz = P.h_ctl->nb_elements - P.h_ctl->nb_partitions;
+    const int64_t dim_out = orientation == DSA_ROWMAJOR ? h->m : h->n;
+    *nnz_out = nnz;
+    if (cap < nnz) fail(DSA_ECAP, "output buffers too small");
+    if (nnz > 0 && (!idx || !vals)) fail(DSA_EARG, "output pointer is NULL");
+    struct Bufs {      // device staging; released once the stream has drained (also on an error after the launch)
+        hipStream_t s; void* p[3] = {nullptr, nullptr, nullptr};
+        ~Bufs() { if (p[0] || p[1] || p[2]) { (void)hipStreamSynchronize(s); for (void* q : p) pool_free(q); } }
+    } b{P.stream};
+    const size_t pb = (size_t)(dim_out + 1) * sizeof(int64_t), cb = (size_t)std::max<int64_t>(nnz, 1) * sizeof(int64_t);
+    HIPCHK(pool_alloc(&b.p[0], pb));
+    HIPCHK(pool_alloc(&b.p[1], cb));
+    HIPCHK(pool_alloc(&b.p[2], cb));
+    int64_t n = 0;
+    to_compressed_dev(h, orientation, 64, index_base, b.p[0], b.p[1], static_cast<double*>(b.p[2]), nnz, &n);
+    HIPCHK(hipMemcpyAsync(ptr, b.p[0], pb, hipMemcpyDeviceToHost, P.stream));
+    if (n > 0) {
+        HIPCHK(hipMemcpyAsync(idx, b.p[1], (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, P.stream));
+        HIPCHK(hipMemcpyAsync(vals, b.p[2], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, P.stream));
+    }
+    HIPCHK(hipStreamSynchronize(P.stream));
     API_CATCH
 }
 

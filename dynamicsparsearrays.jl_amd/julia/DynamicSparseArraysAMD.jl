@@ -293,6 +293,30 @@ function _size_int(a::DynamicSparseMatrix)
     m = Ref{Int64}(0); n = Ref{Int64}(0)
     _check(ccall((:dsa_mat_size, libdsa), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), a.h, m, n)); (m[], n[])
 end
+# the stored entries in CSC form, 1-based (dsa_mat_to_compressed over colmajor): integer keys only, as they index 1..size(a)
+function _csc_int(a::DynamicSparseMatrix{K,L}) where {K,L}
+    (K <: Integer && L <: Integer) || throw(ArgumentError("compressed export needs integer row and column keys, got $(K), $(L)"))
+    m, n = _size_int(a)
+    cap = nnz(a)
+    colptr = Vector{Int64}(undef, n + 1); rowval = Vector{Int64}(undef, cap); nzval = Vector{Float64}(undef, cap)
+    got = Ref{Int64}(0)
+    GC.@preserve colptr rowval nzval _check(ccall((:dsa_mat_to_compressed, libdsa), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ref{Int64}), a.h, Int32(0), Int32(1), colptr, rowval, nzval, cap, got))
+    return m, n, colptr, rowval[1:got[]], nzval[1:got[]]
+end
+function SparseArrays.findnz(a::DynamicSparseMatrix)
+    _, n, colptr, rowval, nzval = _csc_int(a)
+    J = Vector{Int64}(undef, length(rowval))
+    for j in 1:n, p in colptr[j]:colptr[j + 1] - 1
+        J[p] = j
+    end
+    return rowval, J, nzval
+end
+function SparseArrays.SparseMatrixCSC(a::DynamicSparseMatrix)
+    m, n, colptr, rowval, nzval = _csc_int(a)
+    return SparseMatrixCSC(m, n, colptr, rowval, nzval)
+end
+
 function nbpartitions(a::DynamicSparseMatrix, orientation::Integer)     # 0 = colmajor, 1 = rowmajor
     out = Ref{Int64}(0); _check(ccall((:dsa_mat_nbpartitions, libdsa), Int32, (Ptr{Cvoid}, Int32, Ref{Int64}), a.h, orientation, out)); out[]
 end

@@ -197,6 +197,17 @@ int32_t dsa_mat_export_layout(dsa_mat_t* h, int32_t orientation, int64_t* keys, 
                               uint8_t* col_live, int64_t table_cap);
 /* _even_rebalance!(pcsc, 1, capacity, nb_elements) of one orientation  src/pcsr.jl:88-97 */
 int32_t dsa_mat_rebalance_root(dsa_mat_t* h, int32_t orientation);
+/* The stored entries of the matrix in compressed form.  orientation DSA_COLMAJOR: CSC, outer = columns 1..n, inner = rows;
+ * DSA_ROWMAJOR: CSR, outer = rows 1..m, inner = columns; (m, n) = dsa_mat_size at the call.  ptr has outer + 1 entries, idx / vals
+ * cap entries; *nnz_out = nnz(m) on return, also with DSA_ECAP (cap < nnz, nothing launched).  index_bits 32 | 64 (32: DSA_EARG when
+ * a dimension or nnz + base does not fit), index_base 0 | 1.  DSA_EMODE in fill mode; DSA_EBOUNDS when a stored entry lies outside
+ * size(m).  Enqueued on the orientation's stream (dsa_mat_set_stream / dsa_mat_sync); waits only for the bounds word.  Stored zeros
+ * are exported as stored; idx ascends within every outer index (findnz(m) order for CSC). */
+int32_t dsa_mat_to_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t index_bits, int32_t index_base,
+                                  void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out);
+/* the same into host arrays, int64 indices (findnz / SparseMatrixCSC / scipy) */
+int32_t dsa_mat_to_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_base,
+                              int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out);
 
 /* ---- SpMV:  mat * v, transpose(mat) * v   src/operations.jl:14-60 -> _mul :107-135 ---- */
 /* dense x (every index of x is a stored entry), dense y of length ny; rows never touched are 0.

@@ -1,0 +1,300 @@
+// csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
+// checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
+// unit boundary, and the handle structs.  Host units only: a kernel unit (rebalance.hip, spmv.hip, sequencer.hip, ...) never
+// includes it.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
+// dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
+#pragma once
+#include "../../include/dsa.h"
+#include "dsa_dev.h"
+
+#include <cstdint>
+#include <exception>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+namespace dsa {
+namespace host {
+
+struct Fail { int32_t code; std::string msg; };
+[[noreturn]] inline void fail(int32_t code, const std::string& msg) { throw Fail{code, msg}; }
+
+#define HIPCHK(expr)                                                                               \
+    do {                                                                                           \
+        hipError_t _e = (expr);                                                                    \
+        if (_e != hipSuccess) fail(DSA_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
+    } while (0)
+
+// the one check behind a launch_* call: throws Fail{DSA_EHIP, text + hipGetErrorString}
+inline void launch_check(hipError_t e, const char* text) {
+    if (e != hipSuccess) fail(DSA_EHIP, std::string(text) + hipGetErrorString(e));
+}
+#define LAUNCH(what, call) launch_check((call), what " launch: ")
+
+// roctx ranges around every ABI entry point; the loader (DSA_ROCTX=1) is in dsa_host.hip
+struct Roctx {
+    int (*push)(const char*) = nullptr;
+    int (*pop)() = nullptr;
+    Roctx();
+};
+const Roctx& roctx();
+struct ApiRange {
+    bool on;
+    explicit ApiRange(const char* name) : on(roctx().push != nullptr) { if (on) roctx().push(name); }
+    ~ApiRange() { if (on) roctx().pop(); }
+};
+
+#define API_TRY ApiRange _api_range(__func__); try {
+#define API_CATCH                                                              \
+    } catch (const Fail& f) { ::dsa::set_last_error(f.msg.c_str()); return f.code;    \
+    } catch (const std::bad_alloc&) { ::dsa::set_last_error("host allocation failed"); return DSA_EHIP; \
+    } catch (const std::exception& e) { ::dsa::set_last_error(e.what()); return DSA_EASSERT; } \
+    return DSA_OK;
+
+extern int g_device;                      // the device new handles are created on (dsa_set_device)
+extern const int g_wait_policy_default;   // default of Pma::wait_policy (DSA_WAIT_POLICY=1: yield-friendly waits for every new handle)
+extern const bool g_force_wide;           // dev knob: DSA_KEYS_WIDE=1 keeps every structure in 64-bit keys
+
+// ------------------------------------------------------------------------------------------------
+// One packed-memory array resident in HBM, optionally with PackedCSC / MappedPackedCSC tables
+// ------------------------------------------------------------------------------------------------
+struct Pma {
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    void* keys[2] = {nullptr, nullptr};      // physical key arrays: int32_t unless `wide` (KeyArr, dsa_dev.h)
+    bool wide = false;
+    double* vals[2] = {nullptr, nullptr};
+    uint64_t* occ[2] = {nullptr, nullptr};
+    int cur = 0;
+    int64_t stat_why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t cap_alloc = 0;        // slots allocated per buffer
+    int64_t occ_words = 0;        // words allocated per bitmap (whole 64-word tiles)
+    int64_t occ_dirty[2] = {0, 0}; // high-water mark: words >= occ_dirty[b] of bitmap b are known to be zero
+    bool has_sems = false, has_cols = false;
+    int64_t* sems = nullptr; int64_t* col_keys = nullptr; uint8_t* col_live = nullptr;
+    Ctl* d_ctl = nullptr;
+    Ctl* h_ctl = nullptr;         // pinned host mirror
+    RebalanceWork work{nullptr, nullptr, 0};
+    RebalanceWork work2{nullptr, nullptr, 0};   // second prefix table of K-permute (old and new bitmap)
+    uint64_t* occ_old = nullptr;                // bitmap saved by the sequencer at the start of an append run
+    Op* run_cells = nullptr; uint64_t* run_flags = nullptr; int64_t* run_out = nullptr; int64_t run_cap = 0;   // cell stream of a MappedPackedCSC append run
+    uint64_t* run_memo = nullptr;               // the append replay's memo between runs (sequencer.hip: k_append_run)
+    Op* d_ops = nullptr; int64_t ops_cap = 0;
+    int wait_policy = g_wait_policy_default;      // how blocking calls wait for a hand-over: 0 spin on the pinned word, 1 block in hipStreamSynchronize first (dsa_*_set_wait_policy)
+    uint64_t* d_breaks = nullptr; bool breaks_valid = false;      // run-break bitmap of the ops in d_ops (sequencer.hip: k_op_breaks)
+    int64_t* d_opsrc = nullptr; int64_t opsrc_cap = 0;            // the caller's columns of a batch (a, b, v: 3 x opsrc_cap x 8 B) before k_make_ops expands them
+    double* d_q = nullptr; int64_t q_cap = 0;      // scratch for lookups (3 arrays of q_cap)
+    int32_t* d_err = nullptr;
+    int64_t stat_par_rounds = 0, stat_par_ops = 0, stat_seq_ops = 0, stat_seq_launches = 0;      // batch-parallel instrumentation
+    int64_t stat_deferred = 0;              // ops a run-ahead round deferred behind a conflict (each is planned again in a later round)
+    BurstGraph burst, burst_short;      // cached graphs of a full burst of rounds and of a short one (conflict-heavy phases)
+    Plan* d_plans = nullptr; RoundState* d_rs = nullptr; RoundState* h_rs = nullptr;   // batch-parallel writes
+    PendOp* d_pend = nullptr;                   // the pending lists of the rounds (2 x ROUND_GMAX: ops deferred behind a conflict, parbatch.hip)
+    unsigned long long* h_pub = nullptr; unsigned int pub_seq = 0;      // pinned word k_publish writes the burst number to, and the last number handed out
+    DevBufs* d_bufs = nullptr; DevBufs* h_bufs = nullptr;      // the arrays the rounds work on, read from device memory (pinned mirror)
+    TableMerge tmerge{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; int64_t tmerge_cap = 0;   // scratch of the grid-wide table merge (tables.hip)
+    int64_t stat_table_merges = 0;
+    int64_t stat_grid_rebalances = 0;               // launches of the grid-wide rebalance (window_rebalance / root_rebalance)
+    int64_t* d_small = nullptr;                     // 8 x int64 scratch
+    int64_t* h_small = nullptr;                     // its pinned host mirror (small read-backs without a pageable staging copy)
+    int64_t* h_get = nullptr; unsigned long long get_seq = 0;        // pinned landing area of small lookups (get_batch: keys, partitions, answers, error, sequence number)
+    int64_t* h_view = nullptr; unsigned long long view_seq = 0;      // pinned landing area of column views: meta words, sequence number, first cells (col_view_of)
+    hipEvent_t ev_handoff = nullptr;      // recorded on `stream` behind work another handle's stream must wait for (a slice built from this structure)
+    // bumped by every launch that can move cells or change the tables; SpmvMeta is recomputed when it differs
+    int device = 0;              // the device the handle lives on: re-selected at every API entry (a Julia task / finalizer thread or a
+                                 // second Python thread calls in with whatever device its thread last selected)
+    int64_t layout_epoch = 0;
+    int64_t stat_spmv_nomemset = 0;
+    // bumped by every C-ABI entry that can change a value or a slot (layout_epoch misses value-only overwrites): the SpMV plan's key
+    int64_t content_epoch = 0;
+    int64_t stat_spmv_plan = 0, stat_spmv_plan_builds = 0;
+    // column-swept SpMV plan of this orientation (spmv.hip: k_spmv_plan), keyed on (content epoch, layout epoch, nx, ny); built on the
+    // second product at one key, its usability handed over through h_meta[6..8] (ok, cells, sequence number)
+    struct SpmvPlan {
+        enum State { NONE, PENDING, USABLE, UNUSABLE } state = NONE;
+        int64_t content_epoch = -1, layout_epoch = -1, nx = -1, ny = -1, products = 0;
+        PlanDev dev{};
+        void* mem[2] = {nullptr, nullptr};      // cells + values, offsets + scratch
+        int64_t bytes = 0;
+        unsigned long long seq = 0;
+    } plan;
+    struct SpmvMeta { int64_t epoch = -1; bool ordered = false; int64_t max_extent = 0, max_gap = 0, first_key = 0, last_key = 0; } spmv_meta;
+    // its device side: scratch of k_spmv_meta, pinned landing area of the 5 result words, and the epoch a prefetch (enqueued behind
+    // the write batch that changed the layout) is in flight for
+    unsigned long long* d_meta = nullptr; int64_t* h_meta = nullptr; unsigned long long meta_seq = 0; int64_t meta_inflight_epoch = -1;
+    // compressed export (compress.hip): per-tile counts and prefixes (pooled, grown on demand), pinned {error word, sequence number}
+    void* cx_scratch = nullptr; size_t cx_bytes = 0; unsigned long long* h_cx = nullptr; unsigned long long cx_seq = 0;
+    // thresholds  src/pma.jl:58,70,87
+    double t_h = 0.7, t_0 = 0.92, p_h = 0.3, p_0 = 0.08, t_d = 0.0, p_d = 0.0;
+
+    int64_t capacity() const { return h_ctl->capacity; }
+    KeyArr K() const { return KeyArr{keys[cur], wide ? 1 : 0, 0}; }
+    KeyArr KA(int b) const { return KeyArr{keys[b], wide ? 1 : 0, 0}; }
+    size_t kb() const { return wide ? sizeof(int64_t) : sizeof(int32_t); }
+    double* V() const { return vals[cur]; }
+    uint64_t* O() const { return occ[cur]; }
+};
+
+// A batch of ops as the host hands it to a structure: a ready-made Op array (small batches, mixed kinds), or the caller's COLUMNS —
+// op k = (a[k], b ? b[k] : 0, v[k]) of one kind — which go up as they are (16 / 24 bytes per op instead of 32, no Op vector built on
+// the host) and are expanded into the op array by a kernel behind the upload (sequencer.hip: k_make_ops).
+struct OpBatch {
+    int64_t n = 0;
+    const Op* ops = nullptr;
+    const int64_t* a = nullptr; const int64_t* b = nullptr; const double* v = nullptr; int32_t kind = 0;
+    OpBatch() = default;
+    OpBatch(const std::vector<Op>& o) : n((int64_t)o.size()), ops(o.data()) {}      // NOLINT: implicit by design
+    OpBatch(int32_t kind_, const int64_t* a_, const int64_t* b_, const double* v_, int64_t n_) : n(n_), a(a_), b(b_), v(v_), kind(kind_) {}
+    Op at(int64_t k) const {
+        if (ops) return ops[k];
+        Op o; o.a = a[k]; o.b = b ? b[k] : 0; o.v = v[k]; o.kind = kind; o.pad = 0; return o;
+    }
+    int64_t key(int64_t k) const { return ops ? ops[k].a : a[k]; }
+};
+
+struct SeqRun {
+    Pma* P = nullptr;
+    const std::vector<Op>* ops = nullptr;
+    int64_t n = 0;
+    int64_t n_avail = 0;     // ops resident in d_ops (>= n): an append run may consume ops beyond the chunk
+    bool active = false;
+    int32_t err = 0;         // status of the failing op (0 if none)
+    int64_t applied = 0;     // ops fully applied
+    int64_t guard = 0;
+    bool defer_merge = false; // leave pending table entries to the caller (a batch that goes on with more launches)
+};
+
+// view(mpcsc, :, col) that stays in HBM (view_dev): cnt = number of cells, last_key = key of the last one (the largest)
+struct DevView { int64_t cnt = 0, last_key = 0; };
+
+// the pinned landing area of views, small packs and small builds: 8 header words (meta [0..4], sequence number [5], written last) + 2 x 1024 cells
+constexpr int64_t VIEW_AREA_CELLS = 1024;
+// The area is LEASED for one operation and goes back to the pinned pool (pool.hip keeps idle blocks by size class: a lease costs a
+// map lookup) when the operation is over: 10^5 small vectors — Coluna keeps that many — would otherwise pin 32 KB each for life.
+// The sequence numbers stay per handle and start at 1; the header is zeroed at every lease.  When the operation fails with a kernel
+// possibly still in flight the block stays with the handle (released with it) instead of being handed to somebody else.
+struct ViewAreaLease {
+    Pma& P; int exc;
+    explicit ViewAreaLease(Pma& p);
+    ~ViewAreaLease();
+};
+
+// ---- pma_host.hip: lifecycle, key width, partition tables, geometry, grid rebalances, exports, reads
+int64_t capacity_for(int64_t n);
+void pma_free_buffers(Pma& P);
+void pma_destroy(Pma& P);
+void pma_init_common(Pma& P, bool sems, bool cols);
+void upload_keys(Pma& P, void* dst, const int64_t* src, int64_t n);
+bool keys_fit32(const int64_t* k, int64_t n);
+void widen_keys(Pma& P);
+void ensure_tables(Pma& P, int64_t need);
+void compute_bounds(Pma& P);
+void set_geometry_for_new(Pma& P, int64_t capacity, int64_t nb_elements);
+void upload_ctl(Pma& P);
+void ensure_capacity_alloc(Pma& P, int64_t slots, bool zero = true);
+void root_rebalance(Pma& P, int64_t src_cap, int64_t new_cap, int64_t m, bool src_packed);
+void window_rebalance(Pma& P, int64_t ws, int64_t we, int64_t m);
+void build_from_packed(Pma& P, const std::vector<int64_t>& keys, const std::vector<double>& vals);
+void permute_run(Pma& P, const Op* cells, int64_t i0, int64_t n0);
+void wait_policy_block(Pma& P);
+void wait_handover(Pma& P, const volatile void* word, uint64_t want, const char* what, uint64_t mask = ~0ull);
+void pma_info(Pma& P, int64_t nb_partitions_or_len, int64_t* info);
+void export_slots(Pma& P, int64_t* keys, double* vals, uint8_t* occ, int64_t cap);
+void export_tables(Pma& P, int64_t* semaphores, int64_t* col_keys, uint8_t* col_live, int64_t table_cap);
+void pma_check(Pma& P, int64_t* report);
+void get_batch(Pma& P, int mode, const int64_t* qa, const int64_t* qb, int64_t n, double* out);
+void read_range(Pma& P, int64_t from, int64_t to, std::vector<int64_t>& ks, std::vector<double>& vs);
+void col_view_of(Pma& P, int64_t col, std::vector<int64_t>& ks, std::vector<double>& vs);
+DevView view_dev(Pma& P, int64_t col);
+int64_t pack_small(Pma& P, KeyArr k, const double* v, const uint64_t* occ, int64_t from, int64_t to, KeyArr ok, double* ov, int64_t out_cap);
+
+// ---- writes_host.hip: the yield loop around the sequencer and the batch-parallel rounds
+const char* err_text(int32_t e);
+void seq_start(SeqRun& r, Pma& P, const std::vector<Op>& ops);
+bool seq_step(SeqRun& r);
+int64_t run_ops(Pma& P, const std::vector<Op>& ops, int32_t* err);
+int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail = false);
+void run_ops_pair(Pma& A, const std::vector<Op>& opsA, Pma& B, const std::vector<Op>& opsB, SeqRun& ra, SeqRun& rb);
+
+// ---- build_host.hip: the bulk build (K-build)
+void pma_build_dev(Pma& P, const int64_t* d_part, const int64_t* d_key, const double* d_val, int64_t nnz, int32_t combine,
+                   int mode, int64_t nparts_explicit, bool wide, KeyRange part_range = KeyRange(), KeyRange key_range = KeyRange());
+bool mat_build_both_dev(Pma& A, Pma& B, const int64_t* d_part, const int64_t* d_key, const double* d_val, int64_t nnz, bool wideA, bool wideB,
+                        KeyRange part_range, KeyRange key_range);
+void pma_build_from_host(Pma& P, const int64_t* part, const int64_t* key, const double* val, int64_t nnz, int32_t combine,
+                         int mode, int64_t nparts_explicit);
+
+// ---- spmv_host.hip: the Pma-level half of the dense product
+void spmv_plan_drop(Pma& P);
+void prefetch_spmv_meta(Pma& P);
+const Pma::SpmvMeta& spmv_meta(Pma& P);
+bool spmv_plan_on();
+bool spmv_plan_shape_ok(const Pma& P, int64_t nx);
+void spmv_plan_build(Pma& P, int64_t nx, hipStream_t s);
+bool spmv_plan_product(Pma& P, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s);
+
+// ---- dsa_host.hip: what sparsex_host.hip needs of the handle layer
+void mat_flush(dsa_mat* h);
+void ensure_xy(dsa_mat* h, int64_t nx, int64_t ny);
+void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s,
+              int pattern = 0);
+
+// Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks
+// and uploaded asynchronously as a chunk fills (the copy of chunk k overlaps the caller's appends into chunk k+1), so that
+// closefillmode! finds the (row, col, value) stream already in HBM and only ships the last partial chunk.  The reference keeps
+// a Dict row -> (colids, vals); what it uses the per-row structure for — rejecting a second addrow! of a row id
+// (src/buffer.jl:13) — is the `rows` set here; the order of the entries is irrelevant after the (col, row) sort of the
+// builder, duplicates of (i, j) are accumulated with + at the flush like the reference (test/functional/sparsematrix.jl:433-437).
+struct FillBuffer {
+    static constexpr int64_t CHUNK = 1 << 20;            // triples per pinned staging chunk (24 MB)
+    static constexpr int64_t EAGER = 1 << 16;            // a finished batch ships its staged triples at once from this many on
+    std::vector<uint64_t> row_bits;                       // rows 1 .. 2^28 already written (one bit each, grown on demand)
+    std::unordered_set<int64_t> rows_far;                 // ... and the others
+    int64_t* hI[2] = {nullptr, nullptr}; int64_t* hJ[2] = {nullptr, nullptr}; double* hV[2] = {nullptr, nullptr};
+    hipEvent_t uploaded[2] = {nullptr, nullptr};
+    bool in_flight[2] = {false, false};
+    static constexpr int64_t PIECE = 1 << 18;            // a chunk goes up in pieces of this many triples, behind the memcpy that stages them
+    int cur = 0;
+    int64_t fill = 0;                                     // triples in the current pinned chunk
+    int64_t sent = 0;                                     // ... of which already on their way to HBM
+    int64_t *dI = nullptr, *dJ = nullptr; double* dV = nullptr;
+    int64_t dcap = 0, dlen = 0;                           // triples allocated / resident in HBM
+    long long* d_acc = nullptr;                           // running value ranges of the resident triples (build.hip: k_minmax_acc), 5 words
+    long long* h_acc = nullptr;                           // pinned read-back of them
+    hipStream_t stream = nullptr;
+    int64_t length = 0;
+    int device = 0;
+};
+
+}  // namespace host
+}  // namespace dsa
+#pragma GCC visibility pop
+
+// ---- the handle structs (dsa_host.hip; here for the two groups with entry points of their own: raw_host.hip, sparsex_host.hip)
+struct dsa_vec { dsa::host::Pma P; int64_t n = 0; std::vector<int64_t> pk; std::vector<double> pv; };
+struct dsa_pcsc { dsa::host::Pma P; };
+struct dsa_mat {
+    int64_t m = 0, n = 0;
+    bool fillmode = false;
+    dsa::host::FillBuffer buf;
+    bool has_major = false;
+    dsa::host::Pma col, row;          // colmajor / rowmajor MappedPackedCSC
+    double* d_x = nullptr; double* d_y = nullptr; int64_t x_cap = 0, y_cap = 0;
+    // sparse-x product (sparsex.hip): acc / bm keep a ZERO INVARIANT between two products; everything grown, never shrunk
+    struct Spx {
+        double* acc = nullptr; uint64_t* bm = nullptr; int64_t rows_cap = 0;      // sums per row, one bit per touched row
+        uint32_t* tile_cnt = nullptr; uint32_t* tile_off = nullptr; unsigned int* ticket = nullptr; int64_t tiles_cap = 0;
+        int64_t* oi = nullptr; double* ov = nullptr; int64_t out_cap = 0;         // packed result in HBM
+        int64_t* dx = nullptr; int64_t x_cap = 0;                                 // xi | xv uploaded
+        int64_t* d_count = nullptr;
+        long long* pin = nullptr;                                                 // landing area: 8 header words + 2 x SPX_PIN_CELLS
+        void* stage = nullptr; size_t stage_bytes = 0;                            // pinned staging: x on the way up, long results on the way down
+        unsigned long long seq = 0;
+        std::vector<hipEvent_t> ev;                                               // behind the pieces of a long result on their way down
+        bool dl_started = false; int dl_np = 0; size_t dl_off[8] = {}, dl_bytes[8] = {}; // ... its pieces: offset in [rows | values], bytes
+        int64_t res_count = -1;                                                   // result of the last begin (-1: none)
+        hipStream_t res_stream = nullptr;
+    } spx;
+    std::vector<int64_t> pi, pj; std::vector<double> pv;      // queued single writes (non-fill mode)
+};

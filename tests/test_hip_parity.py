@@ -363,7 +363,7 @@ def test_small_matrix_batches_match_oracle(dsa, hip, oracle, shape):
 @pytest.mark.gpu
 def test_kbuild_buffers_sized_for_the_upper_bound_then_duplicates_fold(dsa, hip, oracle):
     """K-build allocates tables and slot buffers while its sort runs, for the UPPER bounds (every triple a cell of its own, every key of the
-    partition range a partition: csrc/dsa_host.hip, pma_build_dev) — the exact counts are known only after the sort.  When most triples are
+    partition range a partition: csrc/build_host.hip, pma_build_dev) — the exact counts are known only after the sort.  When most triples are
     duplicates, and when the partition keys are few but far apart, the structure ends up far smaller than its buffers: geometry, layout and
     tables must still be the reference's (capacity from the FOLDED count, src/pma.jl:42-55), and the structure must keep working (writes,
     _extend!, product) in buffers it did not size itself."""

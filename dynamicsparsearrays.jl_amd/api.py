@@ -296,6 +296,12 @@ class Transposed:
     def mul(self, x, **kw):
         return self.array.mul(x, transpose=True, **kw)
 
+    def matmul(self, X):
+        return self.array.matmul(X, transpose=True)
+
+    def __matmul__(self, X):
+        return self.array.matmul(X, transpose=True)
+
 
 class DynamicSparseMatrix(_Handle):
     """DynamicSparseMatrix{Int64,Int64,Float64}  (src/matrix.jl:1-8)."""
@@ -561,6 +567,61 @@ class DynamicSparseMatrix(_Handle):
         """the sparse product with every operand in HBM (device addresses, e.g. tensor.data_ptr()); stream-ordered, no host wait"""
         self.b.call("mat_spmv_sparse_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_xi)), C.c_void_p(int(d_xv)), int(nx),
                     C.c_void_p(int(d_yi)), C.c_void_p(int(d_yv)), int(cap), C.c_void_p(int(d_count)))
+
+    # ---- dense multi-vector product (include/dsa.h: dsa_mat_spmm_dense[_dev]; HIP library only) ------------------------------------
+    def _require_spmm(self):
+        if not self.b.has("mat_spmm_dense"):
+            raise B.DsaArgumentError(B.EARG, "the multi-vector product needs the HIP product library")
+
+    def matmul(self, X, transpose=False):
+        """mat * X / transpose(mat) * X for k right-hand sides: column j of the result is mul(X[:, j]).
+
+        A 2-D float64 numpy array returns a new (size(mat, 1 | 2), k) array; a 2-D float64 torch tensor on the GPU returns a new
+        tensor on the same device (the operands never leave HBM); a 1-D input returns the 1-D product.  Inputs that are not
+        row-contiguous are copied into that form first."""
+        self._require_spmm()
+        tr = 1 if transpose else 0
+        m, n = self.size()
+        ny = n if transpose else m
+        if isinstance(X, np.ndarray):
+            one_d = X.ndim == 1
+            xx = np.ascontiguousarray(X.reshape(-1, 1) if one_d else X, dtype=np.float64)
+            if xx.ndim != 2:
+                raise B.DsaArgumentError(B.EARG, "X must have one or two dimensions")
+            nx, k = xx.shape
+            y = np.empty((ny, k), dtype=np.float64)
+            self.b.call("mat_spmm_dense", self.h, tr, xx.ctypes.data_as(P_F64), nx, k, k, y.ctypes.data_as(P_F64), ny, k)
+            return y[:, 0] if one_d else y
+        import torch
+        if not isinstance(X, torch.Tensor):
+            raise B.DsaArgumentError(B.EARG, "X must be a numpy array or a torch tensor")
+        if X.dtype != torch.float64 or not X.is_cuda or X.dim() not in (1, 2):
+            raise B.DsaArgumentError(B.EARG, "X must be a 1-D or 2-D float64 tensor on the GPU")
+        one_d = X.dim() == 1
+        xx = X.unsqueeze(1) if one_d else X
+        nx, k = xx.shape
+        if k < 1:
+            raise B.DsaArgumentError(B.EARG, "X has no columns")
+        if xx.stride(1) != 1 or (nx > 1 and xx.stride(0) < k):
+            xx = xx.contiguous()
+        ldx = xx.stride(0) if nx > 1 else k
+        y = torch.empty((ny, k), dtype=torch.float64, device=X.device)
+        # the library works on the orientation's stream: torch's pending work on X and on the fresh block must be over first, and
+        # torch's consumers of the result must start after the product has finished (as in to_torch)
+        torch.cuda.current_stream(X.device).synchronize()
+        self.matmul_dev(xx.data_ptr(), nx, k, y.data_ptr(), ny, ldx=ldx, ldy=k, transpose=transpose)
+        self.sync()
+        return y[:, 0] if one_d else y
+
+    def __matmul__(self, X):
+        return self.matmul(X)
+
+    def matmul_dev(self, d_x, nx, k, d_y, ny, ldx=None, ldy=None, transpose=False):
+        """the multi-vector product with both operands in HBM (device addresses, e.g. tensor.data_ptr()), row-major with leading
+        dimensions ldx / ldy (default k); stream-ordered on the orientation's stream, no host wait (sync())"""
+        self._require_spmm()
+        self.b.call("mat_spmm_dense_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_x)), int(nx), int(k),
+                    int(k if ldx is None else ldx), C.c_void_p(int(d_y)), int(ny), int(k if ldy is None else ldy))
 
 
 def dynamicsparse(I=None, J=None, V=None, m=None, n=None, fill_mode=True,

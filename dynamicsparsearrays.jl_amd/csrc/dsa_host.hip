@@ -1478,6 +1478,43 @@ int32_t dsa_mat_spmv_dense(dsa_mat_t* h, int32_t transpose, const double* x, int
     API_CATCH
 }
 
+int32_t dsa_mat_spmm_dense_dev(dsa_mat_t* h, int32_t transpose, const double* d_x, int64_t nx, int64_t k, int64_t ldx,
+                               double* d_y, int64_t ny, int64_t ldy) {
+    API_TRY
+    mat_flush(h);
+    Pma& P = transpose ? h->col : h->row;
+    spmm_dev(h, transpose, d_x, nx, k, ldx, d_y, ny, ldy, P.stream);
+    API_CATCH
+}
+
+int32_t dsa_mat_spmm_dense(dsa_mat_t* h, int32_t transpose, const double* x, int64_t nx, int64_t k, int64_t ldx,
+                           double* y, int64_t ny, int64_t ldy) {
+    API_TRY
+    mat_flush(h);
+    if (!h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
+    if (k < 1) fail(DSA_EARG, "k must be at least 1");
+    if (ldx < k || ldy < k) fail(DSA_EARG, "leading dimension smaller than k");
+    if (nx < 0 || ny < 0) fail(DSA_EARG, "negative length");
+    if ((nx > 0 && !x) || (ny > 0 && !y)) fail(DSA_EARG, "operand is NULL");
+    Pma& P = transpose ? h->col : h->row;
+    struct Bufs {      // packed device staging (leading dimension k); released once the stream has drained
+        hipStream_t s; void* p[2] = {nullptr, nullptr};
+        ~Bufs() { if (p[0] || p[1]) { (void)hipStreamSynchronize(s); for (void* q : p) pool_free(q); } }
+    } b{P.stream};
+    const size_t row = (size_t)k * sizeof(double);
+    if (nx > 0) {
+        HIPCHK(pool_alloc(&b.p[0], (size_t)nx * row));
+        HIPCHK(hipMemcpy2DAsync(b.p[0], row, x, (size_t)ldx * sizeof(double), row, (size_t)nx, hipMemcpyHostToDevice, P.stream));
+    }
+    if (ny > 0) {
+        HIPCHK(pool_alloc(&b.p[1], (size_t)ny * row));
+        spmm_dev(h, transpose, static_cast<const double*>(b.p[0]), nx, k, k, static_cast<double*>(b.p[1]), ny, k, P.stream);
+        HIPCHK(hipMemcpy2DAsync(y, (size_t)ldy * sizeof(double), b.p[1], row, row, (size_t)ny, hipMemcpyDeviceToHost, P.stream));
+    }
+    HIPCHK(hipStreamSynchronize(P.stream));
+    API_CATCH
+}
+
 int32_t dsa_mat_check(dsa_mat_t* h, int32_t o, int64_t* report) { API_TRY mat_flush(h); pma_check(orient(h, o), report); API_CATCH }
 int32_t dsa_mat_set_stream(dsa_mat_t* h, void* s) {
     API_TRY

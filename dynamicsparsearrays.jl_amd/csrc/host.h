@@ -240,6 +240,10 @@ void ensure_xy(dsa_mat* h, int64_t nx, int64_t ny);
 void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s,
               int pattern = 0);
 
+// ---- spmm_host.hip: the dense multi-vector product
+void spmm_dev(dsa_mat* h, int32_t transpose, const double* d_x, int64_t nx, int64_t k, int64_t ldx, double* d_y, int64_t ny, int64_t ldy,
+              hipStream_t s);
+
 // Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks
 // and uploaded asynchronously as a chunk fills (the copy of chunk k overlaps the caller's appends into chunk k+1), so that
 // closefillmode! finds the (row, col, value) stream already in HBM and only ships the last partial chunk.  The reference keeps

@@ -19,6 +19,7 @@
 module DynamicSparseArraysAMD
 
 using SparseArrays
+using LinearAlgebra: Transpose
 
 export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC, dynamicsparsevec, dynamicsparse, nbpartitions,
        deletecolumn!, deleterow!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
@@ -517,5 +518,20 @@ function Base.:(*)(a::DynamicSparseMatrix, x::Vector{Float64})
         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64), a.h, 0, x, length(x), y, length(y)))
     return y
 end
+
+# Y = A X / transpose(A) X for k right-hand sides (include/dsa.h: dsa_mat_spmm_dense; no reference counterpart — the k-column form of
+# _mul, src/operations.jl:107-135).  The ABI takes X and Y ROW-MAJOR: a k x n Julia matrix (column-major) is exactly the row-major
+# n x k operand, so transpose(Xt) goes in without a copy and the result comes back as the transpose of a k x ny matrix.
+function _spmm(a::DynamicSparseMatrix, tr::Bool, xt::Matrix{Float64}, ny::Integer)
+    k, nx = size(xt)
+    yt = Matrix{Float64}(undef, k, ny)
+    GC.@preserve xt yt _check(ccall((:dsa_mat_spmm_dense, libdsa), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64), a.h, tr ? 1 : 0, xt, nx, k, k, yt, ny, k))
+    return yt
+end
+Base.:(*)(a::DynamicSparseMatrix, X::Transpose{Float64,Matrix{Float64}}) = transpose(_spmm(a, false, parent(X), _size_int(a)[1]))
+Base.:(*)(a::DynamicSparseMatrix, X::Matrix{Float64}) = permutedims(_spmm(a, false, permutedims(X), _size_int(a)[1]))
+Base.:(*)(t::Transposed{<:DynamicSparseMatrix}, X::Transpose{Float64,Matrix{Float64}}) = transpose(_spmm(t.array, true, parent(X), _size_int(t.array)[2]))
+Base.:(*)(t::Transposed{<:DynamicSparseMatrix}, X::Matrix{Float64}) = permutedims(_spmm(t.array, true, permutedims(X), _size_int(t.array)[2]))
 
 end # module

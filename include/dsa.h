@@ -236,6 +236,20 @@ int32_t dsa_mat_spmv_sparse_dev(dsa_mat_t* h, int32_t transpose, const int64_t* 
  * orientation with fp64 atomics (the literal _mul loop nest) */
 int32_t dsa_mat_spmv_dense_dev(dsa_mat_t* h, int32_t transpose, int32_t algo, const double* d_x,
                                int64_t nx, double* d_y, int64_t ny);
+/* Dense multi-vector product (SpMM), the k-column form of _mul (src/operations.jl:107-135); no reference counterpart.
+ * Y = A X (transpose = 0: X is nx x k, Y is ny x k, ny = m) or Y = A' X (transpose = 1), X and Y dense, ROW-MAJOR:
+ * X[i, j] = x[i * ldx + j], Y[i, j] = y[i * ldy + j], ldx >= k, ldy >= k.  Column j of Y is what dsa_mat_spmv_dense computes
+ * for column j of X: Y[r, j] = 0.0 + a1 * X[c1, j] + a2 * X[c2, j] + ... over the stored cells of row r in ascending key order, added
+ * left to right, one multiply then one add per term (no FMA) — the reference's order, for rows of any length.  Rows without a
+ * partition are +0.0; a cell whose key is outside 1..nx contributes nothing, a partition whose key is outside 1..ny writes nothing.
+ * y[i * ldy + j] for k <= j < ldy is not written.  x and y must not overlap.  k > 16 reads the matrix once per 16 columns.
+ * DSA_EARG: k < 1, ldx < k, ldy < k, negative nx / ny, NULL operand of a non-empty shape; DSA_EMODE in fill mode.
+ * _dev: operands resident in HBM, asynchronous on the stream of the orientation that is walked (rowmajor for transpose = 0, colmajor
+ * for transpose = 1; dsa_mat_set_stream / dsa_mat_sync).  The host form stages through pooled device memory and waits. */
+int32_t dsa_mat_spmm_dense_dev(dsa_mat_t* h, int32_t transpose, const double* d_x, int64_t nx, int64_t k, int64_t ldx,
+                               double* d_y, int64_t ny, int64_t ldy);
+int32_t dsa_mat_spmm_dense(dsa_mat_t* h, int32_t transpose, const double* x, int64_t nx, int64_t k, int64_t ldx,
+                           double* y, int64_t ny, int64_t ldy);
 /* ---- column-range shards.  No reference counterpart: the reference is single-process.  One PROCESS per GPU:
  * each process selects its device (dsa_set_device), builds ITS shard and runs the local SpMV; the single data-path collective —
  * the all-reduce (sum) of the partial y — is dsa_shard_allreduce_dev below (RCCL behind this ABI), or whatever the host layer has

@@ -502,6 +502,112 @@ class DynamicSparseMatrix(_Handle):
             return torch.sparse_csr_tensor(ptr, idx, val, size=(m, n))
         return torch.sparse_csc_tensor(ptr, idx, val, size=(m, n))
 
+    # ---- selected export (include/dsa.h: dsa_mat_select_compressed[_dev]; HIP library only) --------------------------------------
+    def _require_select(self):
+        if not self.b.has("mat_select_compressed"):
+            raise B.DsaArgumentError(B.EARG, "the selected export needs the HIP product library")
+
+    def select_compressed_dev(self, orientation, d_sel, nsel, d_ptr, d_idx, d_vals, cap, index_bits=64, base=0):
+        """A[:, sel] (COLMAJOR) / A[sel, :] (ROWMAJOR) in compressed form into device memory: d_sel = nsel int64 outer keys (1-based,
+        any order, repeats allowed), d_ptr = nsel + 1 indices, d_idx / d_vals = cap entries (device addresses, e.g. tensor.data_ptr();
+        0 for idx / vals with cap = 0: the count-only call).  Enqueued on the orientation's stream (sync()).  Returns (total, fits):
+        the number of selected cells and whether they were delivered; with fits False (cap < total) only ptr has been written."""
+        self._require_select()
+        got = C.c_int64()
+        try:
+            self.b.call("mat_select_compressed_dev", self.h, int(orientation), int(index_bits), int(base), C.c_void_p(int(d_sel)),
+                        int(nsel), C.c_void_p(int(d_ptr)), C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)), int(cap), C.byref(got))
+        except B.DsaError as e:
+            if e.code == B.ECAP:
+                return got.value, False
+            raise
+        return got.value, True
+
+    def _select(self, orientation, keys, base, count_only=False):
+        self._require_select()
+        sel, sp = _i64(keys)
+        if sel.ndim != 1:
+            raise B.DsaArgumentError(B.EARG, "the selection must be one-dimensional")
+        nsel = len(sel)
+        ptr = np.empty(nsel + 1, dtype=np.int64)
+        got = C.c_int64()
+        idx = val = None
+        for _ in range(2):              # the count-only call, then the one that fits
+            cap = 0 if idx is None else len(idx)
+            try:
+                self.b.call("mat_select_compressed", self.h, int(orientation), int(base), sp, nsel, ptr.ctypes.data_as(P_I64),
+                            idx.ctypes.data_as(P_I64) if cap else None, val.ctypes.data_as(P_F64) if cap else None, cap, C.byref(got))
+            except B.DsaError as e:
+                if e.code != B.ECAP or idx is not None:
+                    raise
+                if count_only:
+                    return ptr, None, None
+                idx = np.empty(got.value, dtype=np.int64)
+                val = np.empty(got.value, dtype=np.float64)
+                continue
+            break
+        if idx is None:
+            idx, val = np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
+        return ptr, idx[:got.value], val[:got.value]
+
+    def select_columns(self, cols, base=0):
+        """A[:, cols] as scipy-style CSC arrays (indptr, indices, data) with len(cols) columns: int64 indices counted from `base`"""
+        return self._select(COLMAJOR, cols, base)
+
+    def select_rows(self, rows, base=0):
+        """A[rows, :] as scipy-style CSR arrays (indptr, indices, data) with len(rows) rows: int64 indices counted from `base`"""
+        return self._select(ROWMAJOR, rows, base)
+
+    def count_columns(self, cols):
+        """stored entries of each of the columns `cols` (0 for a column that is not there)"""
+        return np.diff(self._select(COLMAJOR, cols, 0, count_only=True)[0])
+
+    def count_rows(self, rows):
+        """stored entries of each of the rows `rows` (0 for a row that is not there)"""
+        return np.diff(self._select(ROWMAJOR, rows, 0, count_only=True)[0])
+
+    def select_torch(self, layout, keys, index_dtype=None):
+        """A[:, keys] as torch.sparse_csc_tensor of shape (m, len(keys)) (layout torch.sparse_csc) or A[keys, :] as
+        torch.sparse_csr_tensor of shape (len(keys), n) (torch.sparse_csr) on the current device.  `keys`: a list, a numpy array, or
+        an int64 CUDA tensor (used in place); the arrays never leave HBM."""
+        import torch
+        self._require_select()
+        if index_dtype is None:
+            index_dtype = torch.int64
+        if layout not in (torch.sparse_csr, torch.sparse_csc):
+            raise B.DsaArgumentError(B.EARG, "layout must be torch.sparse_csr or torch.sparse_csc")
+        if index_dtype not in (torch.int32, torch.int64):
+            raise B.DsaArgumentError(B.EARG, "index_dtype must be torch.int32 or torch.int64")
+        orientation = ROWMAJOR if layout == torch.sparse_csr else COLMAJOR
+        bits = 32 if index_dtype == torch.int32 else 64
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if isinstance(keys, torch.Tensor):
+            if keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1:
+                raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 CUDA tensor")
+            sel = keys.contiguous()
+        else:
+            sel = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)).to(dev)
+        nsel = sel.numel()
+        m, n = self.size()
+        ptr = torch.empty(nsel + 1, dtype=index_dtype, device=dev)
+        # the library works on the orientation's stream: the keys and the fresh blocks must be free of torch's pending work first, and
+        # torch's consumers of the result must start after the selection has finished (the stream discipline of to_torch)
+        torch.cuda.current_stream(dev).synchronize()
+        total, fits = self.select_compressed_dev(orientation, sel.data_ptr(), nsel, ptr.data_ptr(), 0, 0, 0, index_bits=bits)
+        idx = torch.empty(max(total, 1), dtype=index_dtype, device=dev)
+        val = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+        if not fits:
+            torch.cuda.current_stream(dev).synchronize()
+            total, fits = self.select_compressed_dev(orientation, sel.data_ptr(), nsel, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(),
+                                                     total, index_bits=bits)
+            if not fits:
+                raise B.DsaErrorException(B.ECAP, "the selection grew between the count and the emit")
+        self.sync()
+        idx, val = idx[:total], val[:total]
+        if orientation == ROWMAJOR:
+            return torch.sparse_csr_tensor(ptr, idx, val, size=(nsel, n))
+        return torch.sparse_csc_tensor(ptr, idx, val, size=(m, nsel))
+
     def check(self, orientation):
         """device-side invariant checker (HIP library only): report[2..6] must be 0."""
         r = np.zeros(8, dtype=np.int64)

@@ -1454,6 +1454,22 @@ int32_t dsa_mat_to_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_b
     API_CATCH
 }
 
+// ---- selected export (select.hip, select_host.hip): the partitions of a key list as one CSC / CSR; read-only like the full export
+int32_t dsa_mat_select_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t index_bits, int32_t index_base,
+                                      const int64_t* d_sel, int64_t nsel,
+                                      void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out) {
+    API_TRY
+    select_compressed_dev(h, orientation, index_bits, index_base, d_sel, nsel, d_ptr, d_idx, d_vals, cap, nnz_out);
+    API_CATCH
+}
+int32_t dsa_mat_select_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_base,
+                                  const int64_t* sel, int64_t nsel,
+                                  int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out) {
+    API_TRY
+    select_compressed_host(h, orientation, index_base, sel, nsel, ptr, idx, vals, cap, nnz_out);
+    API_CATCH
+}
+
 int32_t dsa_mat_spmv_dense_dev(dsa_mat_t* h, int32_t transpose, int32_t algo, const double* d_x, int64_t nx, double* d_y, int64_t ny) {
     API_TRY
     mat_flush(h);

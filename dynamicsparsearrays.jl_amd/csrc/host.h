@@ -125,6 +125,9 @@ struct Pma {
     unsigned long long* d_meta = nullptr; int64_t* h_meta = nullptr; unsigned long long meta_seq = 0; int64_t meta_inflight_epoch = -1;
     // compressed export (compress.hip): per-tile counts and prefixes (pooled, grown on demand), pinned {error word, sequence number}
     void* cx_scratch = nullptr; size_t cx_bytes = 0; unsigned long long* h_cx = nullptr; unsigned long long cx_seq = 0;
+    // selected export (select.hip): per-key spans, counts and prefixes (pooled, grown on demand), pinned {error word, cells, work items,
+    // sequence number} of the count and {error word, sequence number} of the emit
+    void* sel_scratch = nullptr; size_t sel_bytes = 0; unsigned long long* h_sel = nullptr; unsigned long long sel_seq = 0;
     // thresholds  src/pma.jl:58,70,87
     double t_h = 0.7, t_0 = 0.92, p_h = 0.3, p_0 = 0.08, t_d = 0.0, p_d = 0.0;
 
@@ -243,6 +246,12 @@ void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, in
 // ---- spmm_host.hip: the dense multi-vector product
 void spmm_dev(dsa_mat* h, int32_t transpose, const double* d_x, int64_t nx, int64_t k, int64_t ldx, double* d_y, int64_t ny, int64_t ldy,
               hipStream_t s);
+
+// ---- select_host.hip: the compressed form of selected columns / rows (d_* are device arrays; *nnz_out also with DSA_ECAP)
+void select_compressed_dev(dsa_mat* h, int32_t orientation, int32_t index_bits, int32_t index_base, const int64_t* d_sel, int64_t nsel,
+                           void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out);
+void select_compressed_host(dsa_mat* h, int32_t orientation, int32_t index_base, const int64_t* sel, int64_t nsel, int64_t* ptr,
+                            int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out);
 
 // Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks
 // and uploaded asynchronously as a chunk fills (the copy of chunk k overlaps the caller's appends into chunk k+1), so that

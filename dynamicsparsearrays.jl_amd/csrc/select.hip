@@ -1,0 +1,294 @@
+// csrc/select.hip — K-select: the partitions of a list of outer keys as one compressed matrix (A[:, J] from colmajor, A[I, :] from
+// rowmajor), cost proportional to what is selected.
+//
+// The j-th outer slice of the result is the live partition whose key is sel[j] (any order, repeats allowed; a key without a live
+// partition gives an empty slice).  The cells of a partition are the occupied slots strictly between its semaphore and the next live
+// semaphore (the end of the slot array behind the last one): its SPAN.  Three launches, two host waits:
+//   k_sel_count  one wave per selected key: range check, wave-parallel table search (find_dev.h), the span (tombstoned table entries
+//                behind the partition are skipped 64 at a time), cnt[j] = popcount of the span's bitmap words,
+//                nchunk[j] = 2048-slot tiles of the slot array the span touches (0 for a span without cells)
+//   k_sel_scan   one workgroup: exclusive prefixes of cnt (-> ptr in the caller's index type, and off[] for the emit) and of nchunk
+//                (-> the work-item offsets), 8192 keys per step; both totals and the error word go to pinned memory
+//   (host: waits for the totals, checks cap and the 32-bit rule, sizes the emit grid from the chunk total)
+//   k_sel_emit   one wave per work item (selection j, chunk c): j by an upper-bound search over the chunk prefix, output position =
+//                off[j] + occupied slots of the span in front of the chunk (re-popcounted), the chunk's cells compacted by popcount
+//                ranks; keys and values loaded and idx / vals stored non-temporally; the last workgroup hands the error word to
+//                pinned memory
+// No wave owns a whole long partition: a span is cut at the tile boundaries of the slot array, whatever its length.  No atomics on
+// the output, no floating-point arithmetic (values are copied bit for bit).  The count phase relies on popcounts only, so there is NO
+// inner-index selection or renumbering (A[I, J] with both lists): every cell of a selected partition is delivered.
+// Bytes in: 8 * nsel selection keys, about 8 * log2(table_len) probed table bytes per key, (kb + 8) per slot of the selected spans,
+// their bitmap words twice (count and emit; the emit reads the words in front of a chunk once more to place it: for a span of c
+// chunks c / 2 times its bitmap, 1/64 of the slot bytes per pass).  Bytes out: (ib + 8) * total + ib * (nsel + 1).  Nothing is
+// proportional to the capacity.
+#include "select.h"
+#include "find_dev.h"
+#include <type_traits>
+
+namespace dsa {
+
+constexpr int SEL_CHUNK_SHIFT = 11;                      // 2048 slots = 32 bitmap words per work item, the tile of compress.hip
+constexpr int64_t SEL_CHUNK = int64_t(1) << SEL_CHUNK_SHIFT;
+constexpr int SEL_WORDS = (int)(SEL_CHUNK >> 6);
+constexpr int SEL_U = 8;                                 // bitmap words whose keys and values a wave requests at once
+constexpr int SEL_SCAN_THREADS = 1024;
+constexpr int64_t SEL_EMIT_BLOCKS_MAX = 4096;            // emit grid: beyond 16384 work items a wave strides over several (one ticket per
+                                                         // workgroup at the end: a million of them on one address cost more than the cells)
+
+// scratch: four arrays of nsel entries, then the error word and the ticket of the emit (one 8-byte memset)
+struct SelScratch {
+    int64_t* lo; int64_t* hi;                            // span of selection j: slots [lo, hi), 0-based
+    int64_t* off;                                        // cells (k_sel_count), then their exclusive prefix (k_sel_scan)
+    int64_t* choff;                                      // chunks, then their exclusive prefix
+    uint32_t* err; uint32_t* ticket;
+};
+static SelScratch sel_carve(void* base, int64_t nsel) {
+    SelScratch s;
+    s.lo = static_cast<int64_t*>(base);
+    s.hi = s.lo + nsel;
+    s.off = s.hi + nsel;
+    s.choff = s.off + nsel;
+    s.err = reinterpret_cast<uint32_t*>(s.choff + nsel);
+    s.ticket = s.err + 1;
+    return s;
+}
+size_t select_scratch_bytes(int64_t nsel) { return (size_t)(nsel > 0 ? nsel : 0) * 32 + 8; }
+
+__device__ __forceinline__ uint64_t sel_readlane64(uint64_t v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint32_t sel_wave_or(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int64_t sel_wave_sum(int64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o, 64);
+    return v;
+}
+// occupied slots of [from, to) (0-based, from < to): the lanes stride over the words, first and last word masked
+__device__ __forceinline__ int64_t sel_span_popc(const uint64_t* __restrict__ occ, int64_t from, int64_t to, int lane) {
+    int64_t c = 0;
+    const int64_t w1 = (to - 1) >> 6;
+    for (int64_t w = (from >> 6) + lane; w <= w1; w += 64) c += popc64(occ[w] & word_range_mask(w, from, to - 1));
+    return sel_wave_sum(c);
+}
+
+// one wave per selected key
+__global__ __launch_bounds__(256) void k_sel_count(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
+                                                   const int64_t* __restrict__ col_keys, const uint8_t* __restrict__ col_live,
+                                                   int64_t table_len, bool dense, const int64_t* __restrict__ sel, int64_t nsel,
+                                                   int64_t dim_out, SelScratch s) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t j = (int64_t)blockIdx.x * 4 + wv;
+    if (j >= nsel) return;
+    const int64_t key = sel[j];
+    int64_t lo = 0, hi = 0;
+    uint32_t err = 0;
+    if (key < 1 || key > dim_out) {
+        err = 1u;
+    } else {
+        const DFoundKey f = d_find_table_fast(col_keys, col_live, table_len, key, dense);
+        if (f.has && f.key == key) {
+            const int64_t sp = sems[f.pos - 1];                  // 1-based slot of the semaphore = 0-based slot of the first cell
+            int64_t nx = 0;                                      // the next live semaphore (tombstones have none)
+            for (int64_t e0 = f.pos; e0 < table_len; e0 += 64) {
+                const int64_t e = e0 + lane;
+                const int64_t v = e < table_len ? sems[e] : 0;
+                const uint64_t m = __ballot(v != 0);
+                if (m) { nx = (int64_t)sel_readlane64((uint64_t)v, __ffsll((unsigned long long)m) - 1); break; }
+            }
+            const int64_t end = nx ? nx - 1 : capacity;
+            if (sp < 1 || sp > capacity || end < sp || end > capacity) err = 2u;      // tables out of step with the slots
+            else { lo = sp; hi = end; }
+        }
+    }
+    const int64_t cnt = hi > lo ? sel_span_popc(occ, lo, hi, lane) : 0;
+    if (lane != 0) return;
+    s.lo[j] = lo; s.hi[j] = hi;
+    s.off[j] = cnt;
+    s.choff[j] = cnt > 0 ? ((hi - 1) >> SEL_CHUNK_SHIFT) - (lo >> SEL_CHUNK_SHIFT) + 1 : 0;
+    if (err) atomicOr(s.err, err);
+}
+
+// one workgroup: off / choff become exclusive prefixes in place, ptr[j] = base + off[j], ptr[nsel] = base + total
+template <typename IT>
+__global__ __launch_bounds__(SEL_SCAN_THREADS) void k_sel_scan(SelScratch s, int64_t nsel, int64_t base, IT* __restrict__ ptr,
+                                                               unsigned long long* pinned, unsigned long long seq) {
+    __shared__ unsigned long long sO[SEL_SCAN_THREADS], sS[SEL_SCAN_THREADS];
+    const int t = threadIdx.x;
+    constexpr int PER = 8;
+    unsigned long long carry_o = 0, carry_s = 0;
+    for (int64_t c0 = 0; c0 < nsel; c0 += (int64_t)SEL_SCAN_THREADS * PER) {
+        unsigned long long vo[PER], vs[PER], to = 0, ts = 0;
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const int64_t i = c0 + (int64_t)t * PER + q;
+            vo[q] = i < nsel ? (unsigned long long)s.off[i] : 0ull;
+            vs[q] = i < nsel ? (unsigned long long)s.choff[i] : 0ull;
+            to += vo[q]; ts += vs[q];
+        }
+        sO[t] = to; sS[t] = ts;
+        __syncthreads();
+        for (int o = 1; o < SEL_SCAN_THREADS; o <<= 1) {         // inclusive scan (Hillis-Steele)
+            const unsigned long long a = t >= o ? sO[t - o] : 0ull, b = t >= o ? sS[t - o] : 0ull;
+            __syncthreads();
+            sO[t] += a; sS[t] += b;
+            __syncthreads();
+        }
+        unsigned long long ro = carry_o + sO[t] - to, rs = carry_s + sS[t] - ts;
+#pragma unroll
+        for (int q = 0; q < PER; ++q) {
+            const int64_t i = c0 + (int64_t)t * PER + q;
+            if (i < nsel) { s.off[i] = (int64_t)ro; s.choff[i] = (int64_t)rs; ptr[i] = (IT)(base + (int64_t)ro); }
+            ro += vo[q]; rs += vs[q];
+        }
+        carry_o += sO[SEL_SCAN_THREADS - 1]; carry_s += sS[SEL_SCAN_THREADS - 1];
+        __syncthreads();
+    }
+    if (t != 0) return;
+    ptr[nsel] = (IT)(base + (int64_t)carry_o);
+    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(pinned + 1, carry_o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(pinned + 2, carry_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    __hip_atomic_store(pinned + 3, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+struct SelArgs {
+    void* idx; double* val;
+    int64_t nsel, items, total, dim_in, base;
+    unsigned long long* pinned;         // {error word, sequence number}
+    unsigned long long seq;
+};
+
+// one wave per work item.  Error bits: 1 an inner key outside 1..dim_in, 2 slots and tables disagree.
+template <bool WIDE, typename IT>
+__global__ __launch_bounds__(256) void k_sel_emit(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ,
+                                                  SelScratch s, SelArgs a) {
+    typedef typename std::conditional<WIDE, int64_t, int32_t>::type key_t;
+    const key_t* __restrict__ kp = static_cast<const key_t*>(keys.p);
+    IT* __restrict__ idx = static_cast<IT*>(a.idx);
+    __shared__ uint32_t sErr[4];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t below = mask_lt(lane);
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    uint32_t err = 0;
+    for (int64_t w = (int64_t)blockIdx.x * 4 + wv; w < a.items; w += nwaves) {
+        // the first selection F whose chunk prefix exceeds w (nsel if none): a 64-ary search, one probe per lane and round.  Prefixes
+        // in front of L are <= w, the one at H is > w (or H = nsel).  The selection in front of F owns w (choff[0] = 0 <= w).
+        int64_t L = 0, H = a.nsel;
+        while (H - L > 64) {
+            const int64_t width = H - L;
+            const int64_t p = L + (width * (lane + 1)) / 64;     // ascending with the lane, lane 63 probes H
+            const bool le = p < a.nsel && s.choff[p] <= w;
+            const uint64_t nb = ~__ballot(le);
+            const int f = nb ? __ffsll((unsigned long long)nb) - 1 : 63;
+            H = L + (width * (f + 1)) / 64;
+            if (f > 0) L = L + (width * f) / 64 + 1;
+        }
+        const bool le = L + lane <= H && L + lane < a.nsel && s.choff[L + lane] <= w;
+        const uint64_t nb = ~__ballot(le);
+        const int64_t j = L + (nb ? __ffsll((unsigned long long)nb) - 1 : 64) - 1;
+        if (j < 0 || j >= a.nsel) { err |= 2u; continue; }
+        const int64_t lo = s.lo[j], hi = s.hi[j];
+        const int64_t tile = (lo >> SEL_CHUNK_SHIFT) + (w - s.choff[j]);
+        const int64_t t0 = tile << SEL_CHUNK_SHIFT;
+        const int64_t cs = lo > t0 ? lo : t0, ce = hi < t0 + SEL_CHUNK ? hi : t0 + SEL_CHUNK;
+        if (ce <= cs) { err |= 2u; continue; }
+        int64_t run = s.off[j] + (cs > lo ? sel_span_popc(occ, lo, cs, lane) : 0);      // output position of the chunk's first cell
+        const int64_t w0 = tile * SEL_WORDS;
+        const uint64_t myword = lane < SEL_WORDS && ((w0 + lane) << 6) < ce ? occ[w0 + lane] & word_range_mask(w0 + lane, cs, ce - 1) : 0ull;
+        const uint32_t nz = (uint32_t)__ballot(myword != 0ull);  // words with a cell: a short span leaves most groups of a chunk empty
+        for (int q = 0; q < SEL_WORDS; q += SEL_U) {
+            if (((nz >> q) & ((1u << SEL_U) - 1u)) == 0u) continue;
+            uint64_t wd[SEL_U];
+            int64_t k[SEL_U];
+            double v[SEL_U];
+#pragma unroll
+            for (int u = 0; u < SEL_U; ++u) {
+                wd[u] = sel_readlane64(myword, q + u);
+                const int64_t i = ((w0 + q + u) << 6) + lane;
+                k[u] = -1; v[u] = 0.0;
+                if ((wd[u] >> lane) & 1ull) { k[u] = (int64_t)__builtin_nontemporal_load(kp + i); v[u] = __builtin_nontemporal_load(vals + i); }
+            }
+#pragma unroll
+            for (int u = 0; u < SEL_U; ++u) {
+                if ((wd[u] >> lane) & 1ull) {
+                    const int64_t pos = run + popc64(wd[u] & below);
+                    if (k[u] == SEM_KEY || pos >= a.total) {
+                        err |= 2u;                               // a semaphore inside a span, or more cells than were counted
+                    } else {
+                        __builtin_nontemporal_store((IT)(k[u] - 1 + a.base), idx + pos);
+                        __builtin_nontemporal_store(v[u], a.val + pos);
+                        if (k[u] < 1 || k[u] > a.dim_in) err |= 1u;
+                    }
+                }
+                run += popc64(wd[u]);
+            }
+        }
+    }
+    err = sel_wave_or(err);
+    if (lane == 0) sErr[wv] = err;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    err = sErr[0] | sErr[1] | sErr[2] | sErr[3];
+    if (err) __hip_atomic_fetch_or(s.err, err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __builtin_amdgcn_s_waitcnt(0);
+    const uint32_t tk = __hip_atomic_fetch_add(s.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tk != gridDim.x - 1) return;
+    // the last workgroup: every other one has added its bits before taking its ticket
+    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(a.pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    __hip_atomic_store(a.pinned + 1, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+hipError_t launch_select_count(const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,
+                               int64_t table_len, bool dense, const int64_t* d_sel, int64_t nsel, int64_t dim_out, int32_t index_bits,
+                               int64_t base, void* d_ptr, void* scratch, unsigned long long* pinned4, unsigned long long seq,
+                               hipStream_t stream) {
+    if (capacity < 0 || table_len < 0 || nsel < 0 || nsel > INT32_MAX || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
+    const SelScratch s = sel_carve(scratch, nsel);
+    hipError_t e = hipMemsetAsync(s.err, 0, 8, stream);
+    if (e != hipSuccess) return e;
+    if (nsel > 0)
+        hipLaunchKernelGGL(k_sel_count, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, occ, capacity, sems, col_keys, col_live,
+                           table_len, dense || col_live == nullptr, d_sel, nsel, dim_out, s);
+    if (index_bits == 32)
+        hipLaunchKernelGGL(k_sel_scan<int32_t>, dim3(1), dim3(SEL_SCAN_THREADS), 0, stream, s, nsel, base, static_cast<int32_t*>(d_ptr), pinned4, seq);
+    else
+        hipLaunchKernelGGL(k_sel_scan<int64_t>, dim3(1), dim3(SEL_SCAN_THREADS), 0, stream, s, nsel, base, static_cast<int64_t*>(d_ptr), pinned4, seq);
+    return hipGetLastError();
+}
+
+template <bool WIDE, typename IT>
+static void launch_sel_emit_t(unsigned grid, hipStream_t stream, KeyArr keys, const double* vals, const uint64_t* occ, const SelScratch& s,
+                              const SelArgs& a) {
+    hipLaunchKernelGGL((k_sel_emit<WIDE, IT>), dim3(grid), dim3(256), 0, stream, keys, vals, occ, s, a);
+}
+
+hipError_t launch_select_emit(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t nsel, int64_t items,
+                              int64_t total, int64_t dim_in, int32_t index_bits, int64_t base, void* d_idx, double* d_vals, void* scratch,
+                              unsigned long long* pinned2, unsigned long long seq, hipStream_t stream) {
+    if (capacity < 0 || nsel < 1 || items < 1 || total < 1 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
+    const SelScratch s = sel_carve(scratch, nsel);
+    const SelArgs a{d_idx, d_vals, nsel, items, total, dim_in, base, pinned2, seq};
+    const int64_t blocks = (items + 3) / 4;
+    const unsigned grid = (unsigned)(blocks < SEL_EMIT_BLOCKS_MAX ? blocks : SEL_EMIT_BLOCKS_MAX);
+    if (keys.wide) {
+        if (index_bits == 32) launch_sel_emit_t<true, int32_t>(grid, stream, keys, vals, occ, s, a);
+        else launch_sel_emit_t<true, int64_t>(grid, stream, keys, vals, occ, s, a);
+    } else {
+        if (index_bits == 32) launch_sel_emit_t<false, int32_t>(grid, stream, keys, vals, occ, s, a);
+        else launch_sel_emit_t<false, int64_t>(grid, stream, keys, vals, occ, s, a);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace dsa

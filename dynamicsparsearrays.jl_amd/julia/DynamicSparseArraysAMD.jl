@@ -379,6 +379,39 @@ end
 # A[:, col] / A[row, :]: the new vector is built device to device (view kernel -> one spread launch); nothing but its handle comes back
 Base.getindex(a::DynamicSparseMatrix{K,L}, ::Colon, col) where {K,L} = DynamicSparseVector{K}(_col_slice(a, _in(a.cols, col)), a.rows)
 Base.getindex(a::DynamicSparseMatrix{K,L}, row, ::Colon) where {K,L} = DynamicSparseVector{L}(_row_slice(a, _in(a.rows, row)), a.cols)
+
+# A[:, cols] / A[rows, :] for a list of keys (dsa_mat_select_compressed, 1-based): the partitions of the listed keys as one compressed
+# matrix — any order, repeats allowed, a key without entries gives an empty slice.  Integer keys only, like _csc_int.  The first call
+# counts (cap = 0: DSA_ECAP leaves ptr filled and the total in `got`), the second one fetches.
+function _select_int(a::DynamicSparseMatrix{K,L}, orientation::Int32, keys::AbstractVector{<:Integer}) where {K,L}
+    (K <: Integer && L <: Integer) || throw(ArgumentError("a key-list selection needs integer row and column keys, got $(K), $(L)"))
+    sel = Vector{Int64}(keys)
+    ptr = Vector{Int64}(undef, length(sel) + 1); idx = Int64[]; val = Float64[]
+    got = Ref{Int64}(0)
+    for _ in 1:2
+        cap = length(idx)
+        rc = GC.@preserve sel ptr idx val ccall((:dsa_mat_select_compressed, libdsa), Int32,
+            (Ptr{Cvoid}, Int32, Int32, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ref{Int64}),
+            a.h, orientation, Int32(1), sel, length(sel), ptr, cap == 0 ? Ptr{Int64}(C_NULL) : pointer(idx),
+            cap == 0 ? Ptr{Float64}(C_NULL) : pointer(val), cap, got)
+        if rc == 8 && cap == 0                      # DSA_ECAP
+            resize!(idx, got[]); resize!(val, got[])
+            continue
+        end
+        _check(rc)
+        break
+    end
+    return ptr, idx, val
+end
+function Base.getindex(a::DynamicSparseMatrix{K,L}, ::Colon, cols::AbstractVector{<:Integer}) where {K,L}
+    colptr, rowval, nzval = _select_int(a, Int32(0), cols)
+    return SparseMatrixCSC(_size_int(a)[1], length(cols), colptr, rowval, nzval)
+end
+# the rowmajor selection is the CSC of the transpose (one column per selected row)
+function Base.getindex(a::DynamicSparseMatrix{K,L}, rows::AbstractVector{<:Integer}, ::Colon) where {K,L}
+    rowptr, colval, nzval = _select_int(a, Int32(1), rows)
+    return SparseMatrixCSC(transpose(SparseMatrixCSC(_size_int(a)[2], length(rows), rowptr, colval, nzval)))
+end
 "n getindex calls in one ccall"
 function getindex_batch(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector)
     Ii = _in(a.rows, I); Ji = _in(a.cols, J); out = Vector{Float64}(undef, length(Ii))

@@ -209,6 +209,34 @@ int32_t dsa_mat_to_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t ind
 int32_t dsa_mat_to_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_base,
                               int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out);
 
+/* Selected columns (orientation DSA_COLMAJOR: A[:, sel] as CSC) or rows (DSA_ROWMAJOR: A[sel, :] as CSR) in compressed form.  sel holds
+ * nsel OUTER keys (column keys for colmajor, row keys for rowmajor): 1-based, in any order, repeats allowed, 0 <= nsel <= 2^31 - 1.  The
+ * j-th outer slice of the result is the live partition whose key is sel[j]: ptr has nsel + 1 entries, ptr[j] = base + cells of the
+ * slices in front of j; idx / vals hold, for j = 0, 1, ..., the cells of that partition in slot order (ascending inner key),
+ * idx = key - 1 + base, values copied bit for bit (stored zeros as stored).  A key inside 1..dim_out without a live partition (never
+ * written, deleted, or empty) gives an empty slice.  With repeats the result may hold more cells than nnz(m); nsel = 0 gives
+ * ptr = [base].  dim_out = n (colmajor) | m (rowmajor), dim_in the other one, (m, n) = dsa_mat_size at the call.
+ * There is no inner-index selection or renumbering (A[I, J] with both lists): every cell of a selected partition is delivered.
+ * _dev: every array is a device address; enqueued on the orientation's stream (dsa_mat_set_stream / dsa_mat_sync).  The host waits
+ * twice: for the total, which only the device knows, and behind the emit for the bounds word.  The number of launches and waits does
+ * not depend on nsel.  *nnz_out = the number of selected cells on return, also with DSA_ECAP.
+ * Capacity: cap < total returns DSA_ECAP with *nnz_out = total, ptr COMPLETE AND VALID, idx / vals untouched.  cap = 0 with
+ * d_idx = d_vals = NULL is the count-only call (DSA_OK when the total is 0): it sizes the caller's buffers and gives the entries per
+ * selected key as the differences of ptr.  The second call looks the keys up again: nothing about a selection stays on the handle.
+ * Errors: DSA_EMODE in fill mode.  DSA_EARG: orientation, index_bits (32 | 64) or index_base (0 | 1) invalid; nsel out of range;
+ * ptr NULL, sel NULL with nsel > 0, idx or vals NULL with cap > 0; with index_bits 32, dim_in > INT32_MAX or total + base >
+ * INT32_MAX (the latter found after the count).  DSA_EBOUNDS: a selected key outside 1..dim_out (0 included), or a cell of a
+ * SELECTED partition whose inner key lies outside 1..dim_in (partitions that are not selected are not looked at).  DSA_EASSERT:
+ * partition tables and slot array out of step.  Read-only: slots, tables and both epochs stay as they are, a cached SpMV plan
+ * survives. */
+int32_t dsa_mat_select_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t index_bits, int32_t index_base,
+                                      const int64_t* d_sel, int64_t nsel,
+                                      void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out);
+/* the same with host arrays and int64 indices, staged through pooled device memory (DSA_ECAP leaves ptr filled) */
+int32_t dsa_mat_select_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_base,
+                                  const int64_t* sel, int64_t nsel,
+                                  int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out);
+
 /* ---- SpMV:  mat * v, transpose(mat) * v   src/operations.jl:14-60 -> _mul :107-135 ---- */
 /* dense x (every index of x is a stored entry), dense y of length ny; rows never touched are 0.
  * transpose = 0: y = A x  (nx >= #cols used, ny = m) ; transpose = 1: y = A' x. */

@@ -748,6 +748,78 @@ def dynamicsparse(I=None, J=None, V=None, m=None, n=None, fill_mode=True,
     return DynamicSparseMatrix(b, h)
 
 
+# ---- import from device memory (include/dsa.h: dsa_mat_create_from_coo_dev / _compressed_dev; HIP library only) ------------------
+def _require_import(b):
+    if not b.has("mat_create_from_coo_dev"):
+        raise B.DsaArgumentError(B.EARG, "the device import needs the HIP product library")
+
+
+def dynamicsparse_dev(d_I, d_J, d_V, nnz, m=None, n=None, index_bits=64, index_base=1,
+                      binding: Binding | None = None) -> DynamicSparseMatrix:
+    """dynamicsparse(I, J, V, [m, n]) with the triples in HBM (device addresses, e.g. tensor.data_ptr()): indices of `index_bits`
+    counted from `index_base`, float64 values.  The arrays must be complete at the call and are the caller's again when it returns."""
+    b = _bind(binding)
+    _require_import(b)
+    h = VP()
+    b.call("mat_create_from_coo_dev", C.c_void_p(int(d_I)), C.c_void_p(int(d_J)), C.c_void_p(int(d_V)), int(nnz), int(index_bits),
+           int(index_base), -1 if m is None else int(m), -1 if n is None else int(n), C.byref(h))
+    return DynamicSparseMatrix(b, h)
+
+
+def dynamicsparse_compressed_dev(orientation, d_ptr, d_idx, d_vals, outer, inner, nnz, index_bits=64, index_base=0,
+                                 binding: Binding | None = None) -> DynamicSparseMatrix:
+    """the matrix of a CSR (orientation ROWMAJOR, outer = rows) or CSC (COLMAJOR, outer = columns) form in HBM: the conventions of
+    to_compressed_dev, so an export can be fed straight back; size = (outer, inner) for CSR, (inner, outer) for CSC"""
+    b = _bind(binding)
+    _require_import(b)
+    h = VP()
+    b.call("mat_create_from_compressed_dev", int(orientation), int(index_bits), int(index_base), C.c_void_p(int(d_ptr)),
+           C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)), int(outer), int(inner), int(nnz), C.byref(h))
+    return DynamicSparseMatrix(b, h)
+
+
+def from_torch(t, binding: Binding | None = None) -> DynamicSparseMatrix:
+    """DynamicSparseMatrix of a 2-d torch.sparse_coo (coalesced or not: duplicates are summed), torch.sparse_csr or torch.sparse_csc
+    tensor on the GPU, int32 or int64 indices; size = t.shape.  The arrays never leave HBM."""
+    import torch
+    b = _bind(binding)
+    _require_import(b)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise B.DsaArgumentError(B.EARG, "from_torch needs a sparse tensor on the GPU")
+    if t.layout not in (torch.sparse_coo, torch.sparse_csr, torch.sparse_csc):
+        raise B.DsaArgumentError(B.EARG, "layout must be torch.sparse_coo, torch.sparse_csr or torch.sparse_csc")
+    if t.layout == torch.sparse_coo:
+        unsupported = t.sparse_dim() != 2 or t.dense_dim() != 0
+    else:
+        unsupported = t.dim() != 2 or t.values().dim() != 1
+    if unsupported:
+        raise B.DsaArgumentError(B.EARG, "batched and hybrid sparse tensors are not supported")
+    m, n = (int(s) for s in t.shape)
+    if t.layout == torch.sparse_coo:
+        ind = t._indices()
+        val = t._values()
+        ptr, idx = ind[0].contiguous(), ind[1].contiguous()          # (row indices, column indices)
+    elif t.layout == torch.sparse_csr:
+        ptr, idx, val = t.crow_indices().contiguous(), t.col_indices().contiguous(), t.values()
+    else:
+        ptr, idx, val = t.ccol_indices().contiguous(), t.row_indices().contiguous(), t.values()
+    if ptr.dtype not in (torch.int32, torch.int64) or idx.dtype != ptr.dtype:
+        raise B.DsaArgumentError(B.EARG, "indices must be int32 or int64")
+    val = val.to(torch.float64).contiguous()
+    bits = 32 if ptr.dtype == torch.int32 else 64
+    nnz = int(val.numel())
+    # the library reads on streams of its own: what torch has enqueued for these arrays must have finished first; when the call
+    # returns nothing reads them any more
+    torch.cuda.current_stream(t.device).synchronize()
+    if t.layout == torch.sparse_coo:
+        return dynamicsparse_dev(ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nnz, m, n, index_bits=bits, index_base=0, binding=b)
+    if t.layout == torch.sparse_csr:
+        return dynamicsparse_compressed_dev(ROWMAJOR, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), m, n, nnz, index_bits=bits,
+                                            index_base=0, binding=b)
+    return dynamicsparse_compressed_dev(COLMAJOR, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), n, m, nnz, index_bits=bits,
+                                        index_base=0, binding=b)
+
+
 # free-function spellings of the exported names (src/DynamicSparseArrays.jl:5-16)
 def deletecolumn(mat, col):
     mat.deletecolumn(col)

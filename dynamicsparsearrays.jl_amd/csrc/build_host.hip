@@ -235,6 +235,9 @@ bool mat_build_both_dev(Pma& A, Pma& B, const int64_t* d_part, const int64_t* d_
         if (derive) { upload_ctl(B); build_abort(sb); sb_live = false; }
         return derive;
     } catch (...) {
+        // emit and sort kernels may still run on either stream: they read the scratch released here and the caller's triples, which
+        // are the caller's again as soon as this throws
+        (void)hipStreamSynchronize(A.stream); (void)hipStreamSynchronize(B.stream);
         build_abort(sa);
         if (sb_live) build_abort(sb);
         throw;

@@ -714,6 +714,14 @@ void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, in
     launch_check(e, "spmv launch: ");
 }
 
+// both builds of a fresh handle from triples in HBM with known key ranges (ingest_host.hip), then the SpMV meta prefetch every
+// constructor ends with
+void mat_build_from_dev(dsa_mat* h, const int64_t* dI, const int64_t* dJ, const double* dV, int64_t nnz, KeyRange rows, KeyRange cols) {
+    auto fit32 = [](const KeyRange& r) { return !g_force_wide && (!r.known() || (key_fits32(r.lo) && key_fits32(r.hi))); };
+    mat_build_major_dev(h, dI, dJ, dV, nnz, !fit32(rows), !fit32(cols), rows, cols);
+    try { mat_prefetch_spmv_meta(h); } catch (...) { pma_destroy(h->col); pma_destroy(h->row); h->has_major = false; throw; }
+}
+
 }  // namespace host
 }  // namespace dsa
 
@@ -1125,6 +1133,19 @@ int32_t dsa_mat_create_from_coo(const int64_t* I, const int64_t* J, const double
     if (n < 0) n = cols.known() ? std::max<int64_t>(0, cols.hi) : 0;
     h->m = m; h->n = n;
     *out = h;
+    API_CATCH
+}
+// dynamicsparse(I, J, V, m, n) with the triples in HBM, and the same from CSR / CSC arrays (ingest_host.hip)
+int32_t dsa_mat_create_from_coo_dev(const void* d_I, const void* d_J, const double* d_V, int64_t nnz, int32_t index_bits, int32_t index_base,
+                                    int64_t m, int64_t n, dsa_mat_t** out) {
+    API_TRY
+    *out = mat_from_coo_dev(d_I, d_J, d_V, nnz, index_bits, index_base, m, n);
+    API_CATCH
+}
+int32_t dsa_mat_create_from_compressed_dev(int32_t orientation, int32_t index_bits, int32_t index_base, const void* d_ptr, const void* d_idx,
+                                           const double* d_vals, int64_t outer, int64_t inner, int64_t nnz, dsa_mat_t** out) {
+    API_TRY
+    *out = mat_from_compressed_dev(orientation, index_bits, index_base, d_ptr, d_idx, d_vals, outer, inner, nnz);
     API_CATCH
 }
 // ---------------- column-range shards (the reference is single-process) ----------------

@@ -242,6 +242,14 @@ void mat_flush(dsa_mat* h);
 void ensure_xy(dsa_mat* h, int64_t nx, int64_t ny);
 void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s,
               int pattern = 0);
+// both orientations of a fresh handle from 1-based int64 triples in HBM whose key ranges are known; on failure nothing is left of them
+void mat_build_from_dev(dsa_mat* h, const int64_t* dI, const int64_t* dJ, const double* dV, int64_t nnz, KeyRange rows, KeyRange cols);
+
+// ---- ingest_host.hip: a matrix from COO / CSR / CSC arrays in HBM (new handle; the entry points are in dsa_host.hip)
+dsa_mat* mat_from_coo_dev(const void* d_I, const void* d_J, const double* d_V, int64_t nnz, int32_t index_bits, int32_t index_base,
+                          int64_t m, int64_t n);
+dsa_mat* mat_from_compressed_dev(int32_t orientation, int32_t index_bits, int32_t index_base, const void* d_ptr, const void* d_idx,
+                                 const double* d_vals, int64_t outer, int64_t inner, int64_t nnz);
 
 // ---- spmm_host.hip: the dense multi-vector product
 void spmm_dev(dsa_mat* h, int32_t transpose, const double* d_x, int64_t nx, int64_t k, int64_t ldx, double* d_y, int64_t ny, int64_t ldy,

@@ -24,7 +24,7 @@ using LinearAlgebra: Transpose
 export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC, dynamicsparsevec, dynamicsparse, nbpartitions,
        deletecolumn!, deleterow!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
-       keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!
+       keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev
 
 const libdsa = get(ENV, "DSA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libdsa_hip.so"))
 
@@ -253,6 +253,26 @@ function dynamicsparse(::Type{K}, ::Type{L}, ::Type{Float64}; fill_mode = true) 
     out = Ref{Ptr{Cvoid}}(C_NULL)
     _check(ccall((:dsa_mat_create_empty, libdsa), Int32, (Int32, Ref{Ptr{Cvoid}}), fill_mode ? 1 : 0, out))
     return DynamicSparseMatrix{K,L}(out[])
+end
+"`dynamicsparse(I, J, V, m, n)` with the triples already in HBM: `d_I` / `d_J` are device pointers to `nnz` indices of `index_bits` (32 | 64)
+counted from `index_base` (0 | 1), `d_V` to `nnz` Float64; integer keys only (key = index + 1 - base).  The arrays must be complete at the call
+and are the caller's again when it returns — dsa_mat_create_from_coo_dev"
+function dynamicsparse_dev(d_I::Ptr{Cvoid}, d_J::Ptr{Cvoid}, d_V::Ptr{Cvoid}, nnz::Integer, m::Integer = -1, n::Integer = -1;
+                           index_bits::Integer = 64, index_base::Integer = 1)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _check(ccall((:dsa_mat_create_from_coo_dev, libdsa), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Int64, Int64, Ref{Ptr{Cvoid}}),
+                 d_I, d_J, d_V, nnz, index_bits, index_base, m, n, out))
+    return DynamicSparseMatrix{Int64,Int64}(out[])
+end
+"the same from a compressed form in HBM, the conventions of dsa_mat_to_compressed_dev: `orientation` 1 = CSR (outer = rows), 0 = CSC (outer =
+columns); `d_ptr` has `outer + 1` entries, `d_idx` / `d_vals` `nnz` — dsa_mat_create_from_compressed_dev"
+function dynamicsparse_compressed_dev(orientation::Integer, d_ptr::Ptr{Cvoid}, d_idx::Ptr{Cvoid}, d_vals::Ptr{Cvoid}, outer::Integer, inner::Integer,
+                                      nnz::Integer; index_bits::Integer = 64, index_base::Integer = 0)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _check(ccall((:dsa_mat_create_from_compressed_dev, libdsa), Int32,
+                 (Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Ref{Ptr{Cvoid}}),
+                 orientation, index_bits, index_base, d_ptr, d_idx, d_vals, outer, inner, nnz, out))
+    return DynamicSparseMatrix{Int64,Int64}(out[])
 end
 
 function Base.setindex!(a::DynamicSparseMatrix, val, row, col)

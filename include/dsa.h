@@ -150,6 +150,28 @@ int32_t dsa_pcsc_export_layout(dsa_pcsc_t* h, int64_t* keys, double* vals, uint8
  * m, n < 0 => _guess_length */
 int32_t dsa_mat_create_from_coo(const int64_t* I, const int64_t* J, const double* V, int64_t nnz,
                                 int64_t m, int64_t n, dsa_mat_t** out);
+/* dynamicsparse(I, J, V, m, n) with the triples ALREADY IN HBM: every array is a device address and stays the caller's.  index_bits
+ * 32 | 64 (d_I and d_J share it), index_base 0 | 1, key = index + 1 - base.  The result is the matrix dsa_mat_create_from_coo builds
+ * from those 1-based int64 keys in input order, slot for slot: duplicates summed in input order, a 0.0 stays a stored zero; m, n < 0 =>
+ * _guess_length.  With 64 bits and base 1 the arrays are read in place (any non-zero key, negative ones included).  The arrays must be
+ * complete when the call is made; when it returns, with success or with an error, nothing enqueued reads them any more.  The number of
+ * launches and host waits does not depend on nnz; no device-to-host copy grows with it.
+ * DSA_EARG: index_bits / index_base invalid, nnz < 0 or > 2^32 - 1, a NULL array with nnz > 0, with 32 bits a dimension or nnz + base
+ * above INT32_MAX.  DSA_EKEY: a key that maps to 0 (found on the device).  On any error *out is untouched. */
+int32_t dsa_mat_create_from_coo_dev(const void* d_I, const void* d_J, const double* d_V, int64_t nnz,
+                                    int32_t index_bits, int32_t index_base, int64_t m, int64_t n, dsa_mat_t** out);
+/* The same from a compressed form in HBM, the conventions of dsa_mat_to_compressed_dev (an export can be fed straight back):
+ * orientation DSA_ROWMAJOR = CSR (outer = rows, size = outer x inner), DSA_COLMAJOR = CSC (outer = columns, size = inner x outer);
+ * ptr (outer + 1 entries) and idx (nnz entries) share index_bits, index_base offsets both.  The outer key of position p is the j
+ * (1-based) with ptr[j-1] - base <= p < ptr[j] - base, the inner key idx[p] + 1 - base; input order is storage order.  The inner
+ * indices of a slice need not be sorted or unique.
+ * DSA_EARG: orientation / index_bits / index_base invalid, nnz < 0 or > 2^32 - 1, outer or inner < 0, d_ptr NULL (also with nnz = 0),
+ * d_idx or d_vals NULL with nnz > 0, with 32 bits a dimension or nnz + base above INT32_MAX, a malformed ptr (ptr[0] != base,
+ * ptr[outer] != base + nnz, a decreasing step).  DSA_EBOUNDS: an inner index outside base .. base + inner - 1.  The malformed ptr
+ * and the index out of range are found on the device; no input makes a kernel read outside the caller's arrays. */
+int32_t dsa_mat_create_from_compressed_dev(int32_t orientation, int32_t index_bits, int32_t index_base,
+                                           const void* d_ptr, const void* d_idx, const double* d_vals,
+                                           int64_t outer, int64_t inner, int64_t nnz, dsa_mat_t** out);
 /* dynamicsparse(K, L, T; fill_mode)  src/matrix.jl:31-41 */
 int32_t dsa_mat_create_empty(int32_t fill_mode, dsa_mat_t** out);
 int32_t dsa_mat_destroy(dsa_mat_t* h);

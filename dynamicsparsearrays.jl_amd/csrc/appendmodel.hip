@@ -21,7 +21,7 @@
 // The bitmap is written once: those patterns, widest first, then the last leaf.  Nothing is committed before that point: any
 // precondition that fails (counts outside the tables, a leaf without its free slots) leaves the bitmap untouched and the run to
 // k_append_run (sequencer.hip), which also takes over whatever this kernel did not consume.
-#include "dsa_dev.h"
+#include "wave_dev.h"
 
 namespace dsa {
 
@@ -72,9 +72,6 @@ __device__ __forceinline__ int m3_leaf_reject(int c0, int lo0, int hi0) { return
 // only LDS traffic of a step is the table lookup itself, whose address depends on the time accumulated so far.
 struct M3Lane { int W, lo, hi, cmin, base; };
 __device__ __forceinline__ int rl(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ uint64_t rl64(uint64_t v, int l) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
 struct M3Rec { int tau; uint32_t reb; uint64_t slots; };      // lane i: time of the first visit of level i, what the complete chains below added
 
 // time of the first visit of level `upto` from the suffix counts of the levels below (tables of levels 1 .. upto-1); adds the
@@ -125,7 +122,7 @@ __device__ int m3_final_descent(const M3Lane& L, int& cnt, const uint64_t* X, co
         int m = 1;
         while (m + 1 <= kmax && rl(rec.tau, m + 1) <= b) ++m;
         if (m >= kmax) { bail = 11; return 0; }
-        reb_tot += (uint64_t)(uint32_t)rl((int)rec.reb, m); slots_tot += rl64(rec.slots, m);
+        reb_tot += (uint64_t)(uint32_t)rl((int)rec.reb, m); slots_tot += readlane64(rec.slots, m);
         const int tt = rl(rec.tau, m);
         const int c0 = rl(cnt, m) + tt;
         const int lom = rl(L.lo, m), him = rl(L.hi, m), Wm = rl(L.W, m), cm = rl(L.cmin, m), bm = rl(L.base, m);

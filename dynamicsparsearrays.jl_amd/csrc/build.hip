@@ -23,7 +23,7 @@
 // Composites that do not fit 64 bits (partition AND key ranges beyond 2^32) take the general path at the end of the file: two
 // stable 64-bit sorts by key then by partition (rocPRIM) carrying the input index.
 // Bound: HBM (sort passes: 40 B per triple and pass).
-#include "dsa_dev.h"
+#include "wave_dev.h"
 #include <functional>
 
 #include <algorithm>
@@ -200,20 +200,10 @@ __global__ __launch_bounds__(RS_BLOCK) void k_rs_hist(const uint64_t* __restrict
     hist[(int64_t)tid * nblocks + blockIdx.x] = h[tid];
 }
 
-__device__ __forceinline__ uint32_t bld_wave_excl_scan(uint32_t v) {
-    const int lane = lane_id();
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x - v;
-}
 // exclusive scan over the 256 threads of a workgroup; *total = sum (same in every thread)
 __device__ __forceinline__ uint32_t bld_block_excl_scan(uint32_t v, uint32_t* sW /*[RS_WAVES]*/, uint32_t* total) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t ex = bld_wave_excl_scan(v);
+    const uint32_t ex = wave_excl_scan(v);
     __syncthreads();                                    // sW may still be read from a previous use
     if (lane == 63) sW[wv] = ex + v;
     __syncthreads();
@@ -356,7 +346,7 @@ __global__ __launch_bounds__(1024) void k_bf_scan(uint32_t* __restrict__ cnt_c, 
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             const uint32_t v = i < ntiles ? arr[a][i] : 0u;
-            const uint32_t ex = bld_wave_excl_scan(v);
+            const uint32_t ex = wave_excl_scan(v);
             if (lane == 63) wsum[a][wv] = ex + v;
             __syncthreads();
             uint32_t run = carry[a] + ex, total = 0;
@@ -372,8 +362,7 @@ __global__ __launch_bounds__(1024) void k_bf_scan(uint32_t* __restrict__ cnt_c, 
         if (host != nullptr) {
             __hip_atomic_store(host + 4, (unsigned long long)carry[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // BuildCtl::ncells
             __hip_atomic_store(host + 5, (unsigned long long)carry[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // BuildCtl::nparts
-            __atomic_thread_fence(__ATOMIC_RELEASE);
-            __hip_atomic_store(host + 7, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);                               // BuildCtl::zeros doubles as the sequence word here
+            publish_seq(host + 7, seq);      // BuildCtl::zeros doubles as the sequence word here
         }
     }
 }
@@ -692,8 +681,7 @@ __global__ __launch_bounds__(BSV_MAX) void k_build_small_vec(int64_t* io, int n,
     __syncthreads();
     if (i == 0) {
         __hip_atomic_store(io, (int64_t)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __atomic_thread_fence(__ATOMIC_RELEASE);
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(io) + 5, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        publish_seq(reinterpret_cast<unsigned long long*>(io) + 5, seq);
     }
 }
 hipError_t launch_build_small_vec(int64_t* io, int n, int cap, int32_t combine, KeyArr out_k, double* out_v, unsigned long long seq, hipStream_t stream) {

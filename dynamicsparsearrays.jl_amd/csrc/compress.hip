@@ -13,16 +13,11 @@
 // The slot arrays, the tables and both epochs stay untouched.  Bytes: (kb + 8) * capacity + capacity / 8 (+ the bitmap once more in
 // k_cx_count) + 17 * table_len in, (ib + 8) * nnz + ib * (dim + 1) out.
 #include "compress.h"
+#include "export_dev.h"
 #include <climits>
 #include <type_traits>
 
 namespace dsa {
-
-constexpr int CX_TILE_SHIFT = 11;                        // 2048 slots = 32 bitmap words: one wave (8192 waves for 2^24 slots)
-constexpr int64_t CX_TILE = int64_t(1) << CX_TILE_SHIFT;
-constexpr int CX_WORDS = (int)(CX_TILE >> 6);
-constexpr int CX_U = 8;                                  // bitmap words whose keys and values a wave requests at once
-constexpr int CX_SCAN_THREADS = 1024;
 
 // scratch: the four per-tile arrays, then the error word and the ticket of the emit (the memset covers sem_cnt .. ticket)
 struct CxScratch {
@@ -42,19 +37,8 @@ static CxScratch cx_carve(void* base, int64_t tiles) {
     s.tiles = tiles;
     return s;
 }
-static int64_t cx_tiles(int64_t capacity) { return capacity > 0 ? (capacity + CX_TILE - 1) >> CX_TILE_SHIFT : 1; }
+static int64_t cx_tiles(int64_t capacity) { return capacity > 0 ? (capacity + EX_TILE - 1) >> EX_TILE_SHIFT : 1; }
 size_t compress_scratch_bytes(int64_t capacity) { return (size_t)cx_tiles(capacity) * 24 + 8; }
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
 
 // blocks [0, tile_blocks): four tiles each; the rest: 256 table entries each.  Live semaphores ascend with the id, so the entries of
 // a wave fall into few tiles: one atomic per (wave, tile).
@@ -64,8 +48,8 @@ __global__ __launch_bounds__(256) void k_cx_count(const uint64_t* __restrict__ o
     if ((int64_t)blockIdx.x < tile_blocks) {
         const int64_t t = (int64_t)blockIdx.x * 4 + wv;
         if (t >= s.tiles) return;
-        const int64_t w = t * CX_WORDS + lane, nwords = (capacity + 63) >> 6;
-        int c = lane < CX_WORDS && w < nwords ? popc64(__builtin_nontemporal_load(occ + w)) : 0;
+        const int64_t w = t * EX_WORDS + lane, nwords = (capacity + 63) >> 6;
+        int c = lane < EX_WORDS && w < nwords ? popc64(__builtin_nontemporal_load(occ + w)) : 0;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
         if (lane == 0) s.occ_cnt[t] = (uint32_t)c;
@@ -78,7 +62,7 @@ __global__ __launch_bounds__(256) void k_cx_count(const uint64_t* __restrict__ o
         const int64_t sp = sems[i];
         const bool live = col_live == nullptr || col_live[i] != 0;
         if ((sp != 0) != live || sp < 0 || sp > capacity) bad = 2;          // tables out of step with each other or with the slots
-        else if (sp != 0) tile = (sp - 1) >> CX_TILE_SHIFT;
+        else if (sp != 0) tile = (sp - 1) >> EX_TILE_SHIFT;
     }
     uint64_t todo = __ballot(tile >= 0);
     while (todo) {
@@ -94,45 +78,19 @@ __global__ __launch_bounds__(256) void k_cx_count(const uint64_t* __restrict__ o
 
 // one workgroup: occ_off / sem_off; totals against the host's counts; ptr[k] = base + nnz for k from the last live key to dim_out
 template <typename IT>
-__global__ __launch_bounds__(CX_SCAN_THREADS) void k_cx_scan(CxScratch s, const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
+__global__ __launch_bounds__(EX_SCAN_THREADS) void k_cx_scan(CxScratch s, const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
                                                              int64_t table_len, int64_t nparts, int64_t nnz, int64_t dim_out, int64_t base,
                                                              IT* __restrict__ ptr) {
-    __shared__ unsigned long long sO[CX_SCAN_THREADS], sS[CX_SCAN_THREADS];
     __shared__ long long sLast;
     const int t = threadIdx.x;
-    constexpr int PER = 8;
-    unsigned long long carry_o = 0, carry_s = 0;
-    for (int64_t c0 = 0; c0 < s.tiles; c0 += (int64_t)CX_SCAN_THREADS * PER) {
-        unsigned long long vo[PER], vs[PER], to = 0, ts = 0;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int64_t i = c0 + (int64_t)t * PER + q;
-            vo[q] = i < s.tiles ? s.occ_cnt[i] : 0u;
-            vs[q] = i < s.tiles ? s.sem_cnt[i] : 0u;
-            to += vo[q]; ts += vs[q];
-        }
-        sO[t] = to; sS[t] = ts;
-        __syncthreads();
-        for (int o = 1; o < CX_SCAN_THREADS; o <<= 1) {          // inclusive scan (Hillis-Steele)
-            const unsigned long long a = t >= o ? sO[t - o] : 0ull, b = t >= o ? sS[t - o] : 0ull;
-            __syncthreads();
-            sO[t] += a; sS[t] += b;
-            __syncthreads();
-        }
-        unsigned long long ro = carry_o + sO[t] - to, rs = carry_s + sS[t] - ts;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int64_t i = c0 + (int64_t)t * PER + q;
-            if (i < s.tiles) { s.occ_off[i] = (int64_t)ro; s.sem_off[i] = (int64_t)rs; }
-            ro += vo[q]; rs += vs[q];
-        }
-        carry_o += sO[CX_SCAN_THREADS - 1]; carry_s += sS[CX_SCAN_THREADS - 1];
-        __syncthreads();
-    }
+    unsigned long long carry_o, carry_s;
+    block_excl_scan2(s.occ_cnt, s.sem_cnt, s.tiles,
+                     [&](int64_t i, unsigned long long ro, unsigned long long rs) { s.occ_off[i] = (int64_t)ro; s.sem_off[i] = (int64_t)rs; },
+                     carry_o, carry_s);
     // the last live partition (tombstones at the end of the tables are skipped, 1024 entries per step)
     if (t == 0) sLast = -1;
     __syncthreads();
-    for (int64_t hi = table_len - 1; hi >= 0; hi -= CX_SCAN_THREADS) {
+    for (int64_t hi = table_len - 1; hi >= 0; hi -= EX_SCAN_THREADS) {
         const int64_t i = hi - t;
         if (i >= 0 && sems[i] != 0) atomicMax(&sLast, (long long)i);
         __syncthreads();
@@ -148,7 +106,7 @@ __global__ __launch_bounds__(CX_SCAN_THREADS) void k_cx_scan(CxScratch s, const 
         if (e) atomicOr(s.err, e);
     }
     const IT v = (IT)(base + nnz);
-    for (int64_t k = (c_last > 0 ? c_last : 0) + t; k <= dim_out; k += CX_SCAN_THREADS) __builtin_nontemporal_store(v, ptr + k);
+    for (int64_t k = (c_last > 0 ? c_last : 0) + t; k <= dim_out; k += EX_SCAN_THREADS) __builtin_nontemporal_store(v, ptr + k);
 }
 
 struct CxArgs {
@@ -167,30 +125,29 @@ __global__ __launch_bounds__(256) void k_cx_emit(KeyArr keys, const double* __re
     const key_t* __restrict__ kp = static_cast<const key_t*>(keys.p);
     IT* __restrict__ ptr = static_cast<IT*>(a.ptr);
     IT* __restrict__ idx = static_cast<IT*>(a.idx);
-    __shared__ uint32_t sErr[4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t t = (int64_t)blockIdx.x * 4 + wv;
     const uint64_t below = mask_lt(lane);
     uint32_t err = 0;
     if (t < s.tiles) {
-        const int64_t w0 = t * CX_WORDS, nwords = (capacity + 63) >> 6;
-        const uint64_t myword = lane < CX_WORDS && w0 + lane < nwords ? __builtin_nontemporal_load(occ + w0 + lane) : 0ull;
+        const int64_t w0 = t * EX_WORDS, nwords = (capacity + 63) >> 6;
+        const uint64_t myword = lane < EX_WORDS && w0 + lane < nwords ? __builtin_nontemporal_load(occ + w0 + lane) : 0ull;
         int64_t run_o = s.occ_off[t], run_r = s.sem_off[t];
         int64_t c_run = 0;
         bool have_prev = false;          // c_run holds the key of the last semaphore seen in this tile
-        for (int q = 0; q < CX_WORDS; q += CX_U) {
-            uint64_t wd[CX_U];
-            int64_t k[CX_U], ck[CX_U];
-            double v[CX_U];
+        for (int q = 0; q < EX_WORDS; q += EX_U) {
+            uint64_t wd[EX_U];
+            int64_t k[EX_U], ck[EX_U];
+            double v[EX_U];
 #pragma unroll
-            for (int u = 0; u < CX_U; ++u) {
+            for (int u = 0; u < EX_U; ++u) {
                 wd[u] = readlane64(myword, q + u);
                 const int64_t i = ((w0 + q + u) << 6) + lane;
                 k[u] = -1; v[u] = 0.0;
                 if ((wd[u] >> lane) & 1ull) { k[u] = (int64_t)__builtin_nontemporal_load(kp + i); v[u] = __builtin_nontemporal_load(vals + i); }
             }
 #pragma unroll
-            for (int u = 0; u < CX_U; ++u) {        // keys of the partitions whose semaphores these words hold (semaphore value = id)
+            for (int u = 0; u < EX_U; ++u) {        // keys of the partitions whose semaphores these words hold (semaphore value = id)
                 ck[u] = 0;
                 if (k[u] == SEM_KEY) {
                     const int64_t p = (int64_t)v[u];
@@ -198,7 +155,7 @@ __global__ __launch_bounds__(256) void k_cx_emit(KeyArr keys, const double* __re
                 }
             }
 #pragma unroll
-            for (int u = 0; u < CX_U; ++u) {
+            for (int u = 0; u < EX_U; ++u) {
                 const bool bit = (wd[u] >> lane) & 1ull;
                 const bool sem = bit && k[u] == SEM_KEY;
                 const uint64_t sb = __ballot(sem);
@@ -245,20 +202,7 @@ __global__ __launch_bounds__(256) void k_cx_emit(KeyArr keys, const double* __re
             }
         }
     }
-    err = wave_or(err);
-    if (lane == 0) sErr[wv] = err;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    err = sErr[0] | sErr[1] | sErr[2] | sErr[3];
-    if (err) __hip_atomic_fetch_or(s.err, err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_s_waitcnt(0);
-    const uint32_t tk = __hip_atomic_fetch_add(s.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tk != gridDim.x - 1) return;
-    // the last workgroup: every other one has added its bits before taking its ticket
-    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(a.pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __hip_atomic_store(a.pinned + 1, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    emit_epilogue(err, lane, wv, s.err, s.ticket, a.pinned, a.seq);
 }
 
 template <bool WIDE, typename IT>
@@ -280,10 +224,10 @@ hipError_t launch_to_compressed(KeyArr keys, const double* vals, const uint64_t*
     hipLaunchKernelGGL(k_cx_count, dim3((unsigned)(tile_blocks + table_blocks)), dim3(256), 0, stream, occ, capacity, sems, col_live,
                        table_len, tile_blocks, s);
     if (index_bits == 32)
-        hipLaunchKernelGGL(k_cx_scan<int32_t>, dim3(1), dim3(CX_SCAN_THREADS), 0, stream, s, sems, col_keys, table_len, nparts, nnz, dim_out,
+        hipLaunchKernelGGL(k_cx_scan<int32_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, sems, col_keys, table_len, nparts, nnz, dim_out,
                            base, static_cast<int32_t*>(d_ptr));
     else
-        hipLaunchKernelGGL(k_cx_scan<int64_t>, dim3(1), dim3(CX_SCAN_THREADS), 0, stream, s, sems, col_keys, table_len, nparts, nnz, dim_out,
+        hipLaunchKernelGGL(k_cx_scan<int64_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, sems, col_keys, table_len, nparts, nnz, dim_out,
                            base, static_cast<int64_t*>(d_ptr));
     CxArgs a{d_ptr, d_idx, d_vals, dim_out, dim_in, nnz, base, out2_pinned, seq};
     const unsigned grid = (unsigned)tile_blocks;

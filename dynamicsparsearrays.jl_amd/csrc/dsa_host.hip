@@ -1,11 +1,12 @@
 // csrc/dsa_host.hip — the handle layer of libdsa_hip.so: the last-error text, the table of development switches, the fill-mode
 // staging buffer, what is written in terms of dsa_vec / dsa_pcsc / dsa_mat (flush and apply of queued writes, the builds of both
-// orientations, slices, the compressed export, the dense product) and the C ABI of include/dsa.h.
+// orientations, slices, the dense product) and the C ABI of include/dsa.h.
 //
 // Everything that works on ONE packed-memory array (the Pma of host.h) is in the engine units pma_host.hip (lifecycle, geometry,
 // rebalances, reads), writes_host.hip (yield loop around the sequencer, batch-parallel rounds), build_host.hip (K-build) and
-// spmv_host.hip (SpMV meta and plan); the sparse-x product and the parity hooks have entry points of their own in sparsex_host.hip
-// and raw_host.hip.
+// spmv_host.hip (SpMV meta and plan); the exports, the multi-vector product and the device import sit behind three-line entry points
+// in export_host.hip, spmm_host.hip and ingest_host.hip; the sparse-x product and the parity hooks have entry points of their own in
+// sparsex_host.hip and raw_host.hip.
 //
 // Everything that touches slots runs on the GPU (rebalance.hip, sequencer.hip, spmv.hip).  The host
 // keeps only: the control scalars of each PMA (mirrored from the device control block), the integer
@@ -14,7 +15,6 @@
 // (sort by (col,row), combine, emit, spread) runs on the device (build.hip + rebalance.hip).
 // There is no CPU fallback for any slot operation.
 #include "host.h"
-#include "compress.h"
 
 #include <dlfcn.h>
 
@@ -779,42 +779,6 @@ int32_t view_dev_impl(dsa_mat_t* h, int32_t o, int64_t key, int64_t* d_keys, dou
     API_CATCH
 }
 
-// ---- compressed export (compress.hip): CSC from colmajor, CSR from rowmajor; read-only (no epoch moves, a cached SpMV plan survives)
-void to_compressed_dev(dsa_mat_t* h, int32_t o, int32_t index_bits, int32_t index_base, void* d_ptr, void* d_idx, double* d_vals,
-                              int64_t cap, int64_t* nnz_out) {
-    mat_flush(h);
-    if (h->fillmode || !h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
-    Pma& P = orient(h, o);
-    if (!nnz_out) fail(DSA_EARG, "nnz_out is NULL");
-    if (index_bits != 32 && index_bits != 64) fail(DSA_EARG, "index_bits must be 32 or 64");
-    if (index_base != 0 && index_base != 1) fail(DSA_EARG, "index_base must be 0 or 1");
-    const int64_t parts = P.h_ctl->nb_partitions, nnz = P.h_ctl->nb_elements - parts;
-    const int64_t dim_out = o == DSA_ROWMAJOR ? h->m : h->n, dim_in = o == DSA_ROWMAJOR ? h->n : h->m;
-    *nnz_out = nnz;
-    if (index_bits == 32 && (dim_out > INT32_MAX || dim_in > INT32_MAX || nnz + index_base > INT32_MAX))
-        fail(DSA_EARG, "a dimension or nnz does not fit 32-bit indices");
-    if (cap < nnz) fail(DSA_ECAP, "output buffers too small");
-    if (!d_ptr || (nnz > 0 && (!d_idx || !d_vals))) fail(DSA_EARG, "output pointer is NULL");
-    const size_t need = compress_scratch_bytes(P.capacity());
-    if (P.cx_bytes < need) {
-        if (P.cx_scratch) { HIPCHK(hipStreamSynchronize(P.stream)); pool_free(P.cx_scratch); P.cx_scratch = nullptr; P.cx_bytes = 0; }
-        HIPCHK(pool_alloc(&P.cx_scratch, need));
-        P.cx_bytes = need;
-    }
-    if (!P.h_cx) {
-        HIPCHK(pinned_alloc(reinterpret_cast<void**>(&P.h_cx), 2 * sizeof(unsigned long long)));
-        std::memset(P.h_cx, 0, 2 * sizeof(unsigned long long));
-        P.cx_seq = 0;
-    }
-    const unsigned long long seq = ++P.cx_seq;
-    LAUNCH("compressed export", launch_to_compressed(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, parts, nnz,
-                                                     dim_out, dim_in, index_bits, index_base, d_ptr, d_idx, d_vals, P.cx_scratch, P.h_cx, seq, P.stream));
-    wait_handover(P, P.h_cx + 1, seq, "compressed export");
-    const unsigned long long err = __atomic_load_n(P.h_cx, __ATOMIC_ACQUIRE);
-    if (err & 2u) fail(DSA_EASSERT, "compressed export: slot array and partition tables disagree");
-    if (err & 1u) fail(DSA_EBOUNDS, "a stored entry lies outside size(m)");
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -1447,35 +1411,11 @@ int32_t dsa_mat_to_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t ind
 int32_t dsa_mat_to_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_base,
                               int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out) {
     API_TRY
-    mat_flush(h);
-    if (h->fillmode || !h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
-    Pma& P = orient(h, orientation);
-    if (!ptr || !nnz_out) fail(DSA_EARG, "output pointer is NULL");
-    const int64_t nnz = P.h_ctl->nb_elements - P.h_ctl->nb_partitions;
-    const int64_t dim_out = orientation == DSA_ROWMAJOR ? h->m : h->n;
-    *nnz_out = nnz;
-    if (cap < nnz) fail(DSA_ECAP, "output buffers too small");
-    if (nnz > 0 && (!idx || !vals)) fail(DSA_EARG, "output pointer is NULL");
-    struct Bufs {      // device staging; released once the stream has drained (also on an error after the launch)
-        hipStream_t s; void* p[3] = {nullptr, nullptr, nullptr};
-        ~Bufs() { if (p[0] || p[1] || p[2]) { (void)hipStreamSynchronize(s); for (void* q : p) pool_free(q); } }
-    } b{P.stream};
-    const size_t pb = (size_t)(dim_out + 1) * sizeof(int64_t), cb = (size_t)std::max<int64_t>(nnz, 1) * sizeof(int64_t);
-    HIPCHK(pool_alloc(&b.p[0], pb));
-    HIPCHK(pool_alloc(&b.p[1], cb));
-    HIPCHK(pool_alloc(&b.p[2], cb));
-    int64_t n = 0;
-    to_compressed_dev(h, orientation, 64, index_base, b.p[0], b.p[1], static_cast<double*>(b.p[2]), nnz, &n);
-    HIPCHK(hipMemcpyAsync(ptr, b.p[0], pb, hipMemcpyDeviceToHost, P.stream));
-    if (n > 0) {
-        HIPCHK(hipMemcpyAsync(idx, b.p[1], (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, P.stream));
-        HIPCHK(hipMemcpyAsync(vals, b.p[2], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, P.stream));
-    }
-    HIPCHK(hipStreamSynchronize(P.stream));
+    to_compressed_host(h, orientation, index_base, ptr, idx, vals, cap, nnz_out);
     API_CATCH
 }
 
-// ---- selected export (select.hip, select_host.hip): the partitions of a key list as one CSC / CSR; read-only like the full export
+// ---- selected export (select.hip): the partitions of a key list as one CSC / CSR; read-only like the full export
 int32_t dsa_mat_select_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t index_bits, int32_t index_base,
                                       const int64_t* d_sel, int64_t nsel,
                                       void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out) {
@@ -1527,28 +1467,7 @@ int32_t dsa_mat_spmm_dense_dev(dsa_mat_t* h, int32_t transpose, const double* d_
 int32_t dsa_mat_spmm_dense(dsa_mat_t* h, int32_t transpose, const double* x, int64_t nx, int64_t k, int64_t ldx,
                            double* y, int64_t ny, int64_t ldy) {
     API_TRY
-    mat_flush(h);
-    if (!h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
-    if (k < 1) fail(DSA_EARG, "k must be at least 1");
-    if (ldx < k || ldy < k) fail(DSA_EARG, "leading dimension smaller than k");
-    if (nx < 0 || ny < 0) fail(DSA_EARG, "negative length");
-    if ((nx > 0 && !x) || (ny > 0 && !y)) fail(DSA_EARG, "operand is NULL");
-    Pma& P = transpose ? h->col : h->row;
-    struct Bufs {      // packed device staging (leading dimension k); released once the stream has drained
-        hipStream_t s; void* p[2] = {nullptr, nullptr};
-        ~Bufs() { if (p[0] || p[1]) { (void)hipStreamSynchronize(s); for (void* q : p) pool_free(q); } }
-    } b{P.stream};
-    const size_t row = (size_t)k * sizeof(double);
-    if (nx > 0) {
-        HIPCHK(pool_alloc(&b.p[0], (size_t)nx * row));
-        HIPCHK(hipMemcpy2DAsync(b.p[0], row, x, (size_t)ldx * sizeof(double), row, (size_t)nx, hipMemcpyHostToDevice, P.stream));
-    }
-    if (ny > 0) {
-        HIPCHK(pool_alloc(&b.p[1], (size_t)ny * row));
-        spmm_dev(h, transpose, static_cast<const double*>(b.p[0]), nx, k, k, static_cast<double*>(b.p[1]), ny, k, P.stream);
-        HIPCHK(hipMemcpy2DAsync(y, (size_t)ldy * sizeof(double), b.p[1], row, row, (size_t)ny, hipMemcpyDeviceToHost, P.stream));
-    }
-    HIPCHK(hipStreamSynchronize(P.stream));
+    spmm_host(h, transpose, x, nx, k, ldx, y, ny, ldy);
     API_CATCH
 }
 

@@ -1,0 +1,194 @@
+// csrc/export_host.hip — host side of the two compressed exports: the whole orientation (dsa_mat_to_compressed[_dev], kernels in
+// compress.hip) and the partitions of a key list (dsa_mat_select_compressed[_dev], kernels in select.hip).  Argument checks, the
+// scratch and pinned words of an orientation (ExportArea), the hand-overs and the staging of the host forms.  Host-only unit.
+// Read-only: no epoch moves (a cached SpMV plan survives), nothing about an export stays on the handle between two calls.
+#include "host.h"
+#include "compress.h"
+#include "select.h"
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+
+namespace dsa {
+namespace host {
+
+void ExportArea::ensure(hipStream_t stream, size_t need, int words) {
+    if (bytes < need) {
+        if (scratch) { HIPCHK(hipStreamSynchronize(stream)); pool_free(scratch); scratch = nullptr; bytes = 0; }
+        HIPCHK(pool_alloc(&scratch, need));
+        bytes = need;
+    }
+    if (!pin) {
+        HIPCHK(pinned_alloc(reinterpret_cast<void**>(&pin), (size_t)words * sizeof(unsigned long long)));
+        std::memset(pin, 0, (size_t)words * sizeof(unsigned long long));
+        seq = 0;
+    }
+}
+void ExportArea::release() {
+    pool_free(scratch);
+    pinned_free(pin);
+    *this = ExportArea();
+}
+
+void check_index_format(int32_t index_bits, int32_t index_base) {
+    if (index_bits != 32 && index_bits != 64) fail(DSA_EARG, "index_bits must be 32 or 64");
+    if (index_base != 0 && index_base != 1) fail(DSA_EARG, "index_base must be 0 or 1");
+}
+
+namespace {
+
+// what every export starts with: queued writes applied, not in fill mode, the orientation and its two dimensions
+struct Side { Pma& P; int64_t dim_out, dim_in; };
+Side export_side(dsa_mat* h, int32_t o) {
+    mat_flush(h);
+    if (h->fillmode || !h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
+    if (o != DSA_COLMAJOR && o != DSA_ROWMAJOR) fail(DSA_EARG, "orientation must be 0 or 1");
+    const bool rows = o == DSA_ROWMAJOR;
+    return Side{rows ? h->row : h->col, rows ? h->m : h->n, rows ? h->n : h->m};
+}
+
+// the error word an export kernel handed over: bit 2 the structure contradicts itself, bit 1 something lies outside size(m)
+void export_verdict(const unsigned long long* word, const char* what, const char* outside) {
+    const unsigned long long err = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    if (err & 2u) fail(DSA_EASSERT, std::string(what) + ": slot array and partition tables disagree");
+    if (err & 1u) fail(DSA_EBOUNDS, outside);
+}
+
+// ---- the whole orientation: CSC from colmajor, CSR from rowmajor
+void compress_side(const Side& e, int32_t index_bits, int32_t index_base, void* d_ptr, void* d_idx, double* d_vals, int64_t cap,
+                   int64_t* nnz_out) {
+    Pma& P = e.P;
+    if (!nnz_out) fail(DSA_EARG, "nnz_out is NULL");
+    check_index_format(index_bits, index_base);
+    const int64_t parts = P.h_ctl->nb_partitions, nnz = P.h_ctl->nb_elements - parts;
+    *nnz_out = nnz;
+    if (index_bits == 32 && (e.dim_out > INT32_MAX || e.dim_in > INT32_MAX || nnz + index_base > INT32_MAX))
+        fail(DSA_EARG, "a dimension or nnz does not fit 32-bit indices");
+    if (cap < nnz) fail(DSA_ECAP, "output buffers too small");
+    if (!d_ptr || (nnz > 0 && (!d_idx || !d_vals))) fail(DSA_EARG, "output pointer is NULL");
+    ExportArea& A = P.cx;
+    A.ensure(P.stream, compress_scratch_bytes(P.capacity()), 2);      // pinned {error word, sequence number}
+    const unsigned long long seq = A.next();
+    LAUNCH("compressed export", launch_to_compressed(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, parts, nnz,
+                                                     e.dim_out, e.dim_in, index_bits, index_base, d_ptr, d_idx, d_vals, A.scratch, A.pin, seq, P.stream));
+    wait_handover(P, A.pin + 1, seq, "compressed export");
+    export_verdict(A.pin, "compressed export", "a stored entry lies outside size(m)");
+}
+
+// ---- the partitions of a key list
+struct SelTotals { int64_t total = 0, items = 0; };
+
+// argument checks, count + scan, the first wait.  ptr is complete when this returns; *nnz_out = cells selected.
+SelTotals select_count(const Side& e, int32_t index_bits, int32_t index_base, const int64_t* d_sel, int64_t nsel, void* d_ptr,
+                       int64_t* nnz_out) {
+    Pma& P = e.P;
+    if (!nnz_out) fail(DSA_EARG, "nnz_out is NULL");
+    check_index_format(index_bits, index_base);
+    if (nsel < 0 || nsel > INT32_MAX) fail(DSA_EARG, "nsel must lie in 0 .. 2^31 - 1");
+    if (!d_ptr || (nsel > 0 && !d_sel)) fail(DSA_EARG, "selection or ptr is NULL");
+    if (index_bits == 32 && e.dim_in > INT32_MAX) fail(DSA_EARG, "the inner dimension does not fit 32-bit indices");
+    *nnz_out = 0;
+    ExportArea& A = P.sel;
+    // pinned {error word, cells, work items, sequence number} of the count and {error word, sequence number} of the emit
+    A.ensure(P.stream, select_scratch_bytes(nsel), 6);
+    const unsigned long long seq = A.next();
+    const Ctl& c = *P.h_ctl;
+    LAUNCH("selected export (count)", launch_select_count(P.O(), c.capacity, P.sems, P.col_keys, P.col_live, c.table_len,
+                                                          c.nb_partitions == c.table_len, d_sel, nsel, e.dim_out, index_bits, index_base,
+                                                          d_ptr, A.scratch, A.pin, seq, P.stream));
+    wait_handover(P, A.pin + 3, seq, "selected export (count)");
+    export_verdict(A.pin, "selected export", "a selected key lies outside size(m)");
+    SelTotals t;
+    t.total = (int64_t)A.pin[1]; t.items = (int64_t)A.pin[2];
+    *nnz_out = t.total;
+    if (index_bits == 32 && t.total + index_base > INT32_MAX) fail(DSA_EARG, "the selected cells do not fit 32-bit indices");
+    return t;
+}
+
+// the emit on the scratch select_count left, and the second wait
+void select_emit(const Side& e, const SelTotals& t, int32_t index_bits, int32_t index_base, int64_t nsel, void* d_idx, double* d_vals) {
+    if (t.total <= 0) return;
+    if (t.items <= 0) fail(DSA_EASSERT, "selected export: cells without a work item");
+    Pma& P = e.P;
+    ExportArea& A = P.sel;
+    const unsigned long long seq = A.next();
+    LAUNCH("selected export (emit)", launch_select_emit(P.K(), P.V(), P.O(), P.capacity(), nsel, t.items, t.total, e.dim_in, index_bits,
+                                                        index_base, d_idx, d_vals, A.scratch, A.pin + 4, seq, P.stream));
+    wait_handover(P, A.pin + 5, seq, "selected export (emit)");
+    export_verdict(A.pin + 4, "selected export", "a stored entry of a selected partition lies outside size(m)");
+}
+
+}  // namespace
+
+void to_compressed_dev(dsa_mat* h, int32_t o, int32_t index_bits, int32_t index_base, void* d_ptr, void* d_idx, double* d_vals,
+                       int64_t cap, int64_t* nnz_out) {
+    compress_side(export_side(h, o), index_bits, index_base, d_ptr, d_idx, d_vals, cap, nnz_out);
+}
+
+void to_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, int64_t* ptr, int64_t* idx, double* vals, int64_t cap,
+                        int64_t* nnz_out) {
+    const Side e = export_side(h, o);
+    Pma& P = e.P;
+    if (!ptr || !nnz_out) fail(DSA_EARG, "output pointer is NULL");
+    const int64_t nnz = P.h_ctl->nb_elements - P.h_ctl->nb_partitions;
+    *nnz_out = nnz;
+    if (cap < nnz) fail(DSA_ECAP, "output buffers too small");
+    if (nnz > 0 && (!idx || !vals)) fail(DSA_EARG, "output pointer is NULL");
+    DevStaging b(P.stream);
+    const size_t pb = (size_t)(e.dim_out + 1) * sizeof(int64_t), cb = (size_t)std::max<int64_t>(nnz, 1) * sizeof(int64_t);
+    HIPCHK(pool_alloc(&b.p[0], pb));
+    HIPCHK(pool_alloc(&b.p[1], cb));
+    HIPCHK(pool_alloc(&b.p[2], cb));
+    int64_t n = 0;
+    compress_side(e, 64, index_base, b.p[0], b.p[1], static_cast<double*>(b.p[2]), nnz, &n);
+    HIPCHK(hipMemcpyAsync(ptr, b.p[0], pb, hipMemcpyDeviceToHost, P.stream));
+    if (n > 0) {
+        HIPCHK(hipMemcpyAsync(idx, b.p[1], (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, P.stream));
+        HIPCHK(hipMemcpyAsync(vals, b.p[2], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, P.stream));
+    }
+    HIPCHK(hipStreamSynchronize(P.stream));
+}
+
+void select_compressed_dev(dsa_mat* h, int32_t o, int32_t index_bits, int32_t index_base, const int64_t* d_sel, int64_t nsel,
+                           void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out) {
+    if (cap < 0) fail(DSA_EARG, "negative capacity");
+    if (cap > 0 && (!d_idx || !d_vals)) fail(DSA_EARG, "output pointer is NULL");
+    const Side e = export_side(h, o);
+    const SelTotals t = select_count(e, index_bits, index_base, d_sel, nsel, d_ptr, nnz_out);
+    if (cap < t.total) fail(DSA_ECAP, "output buffers too small");
+    select_emit(e, t, index_bits, index_base, nsel, d_idx, d_vals);
+}
+
+void select_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, const int64_t* sel, int64_t nsel, int64_t* ptr, int64_t* idx,
+                            double* vals, int64_t cap, int64_t* nnz_out) {
+    if (cap < 0) fail(DSA_EARG, "negative capacity");
+    if (!ptr || !nnz_out || (nsel > 0 && !sel)) fail(DSA_EARG, "selection, ptr or nnz_out is NULL");
+    if (cap > 0 && (!idx || !vals)) fail(DSA_EARG, "output pointer is NULL");
+    if (nsel < 0 || nsel > INT32_MAX) fail(DSA_EARG, "nsel must lie in 0 .. 2^31 - 1");
+    const Side e = export_side(h, o);
+    Pma& S = e.P;
+    DevStaging b(S.stream);
+    const size_t sb = (size_t)std::max<int64_t>(nsel, 1) * sizeof(int64_t), pb = (size_t)(nsel + 1) * sizeof(int64_t);
+    HIPCHK(pool_alloc(&b.p[0], sb));
+    HIPCHK(pool_alloc(&b.p[1], pb));
+    if (nsel > 0) HIPCHK(hipMemcpyAsync(b.p[0], sel, (size_t)nsel * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
+    const SelTotals t = select_count(e, 64, index_base, static_cast<const int64_t*>(b.p[0]), nsel, b.p[1], nnz_out);
+    HIPCHK(hipMemcpyAsync(ptr, b.p[1], pb, hipMemcpyDeviceToHost, S.stream));
+    if (cap < t.total) {
+        HIPCHK(hipStreamSynchronize(S.stream));      // ptr is the caller's to read with DSA_ECAP
+        fail(DSA_ECAP, "output buffers too small");
+    }
+    if (t.total > 0) {
+        const size_t cb = (size_t)t.total * sizeof(int64_t);
+        HIPCHK(pool_alloc(&b.p[2], cb));
+        HIPCHK(pool_alloc(&b.p[3], cb));
+        select_emit(e, t, 64, index_base, nsel, b.p[2], static_cast<double*>(b.p[3]));
+        HIPCHK(hipMemcpyAsync(idx, b.p[2], cb, hipMemcpyDeviceToHost, S.stream));
+        HIPCHK(hipMemcpyAsync(vals, b.p[3], cb, hipMemcpyDeviceToHost, S.stream));
+    }
+    HIPCHK(hipStreamSynchronize(S.stream));
+}
+
+}  // namespace host
+}  // namespace dsa

@@ -1,7 +1,9 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
-// unit boundary, and the handle structs.  Host units only: a kernel unit (rebalance.hip, spmv.hip, sequencer.hip, ...) never
-// includes it.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
+// unit boundary, and the handle structs.  The host units are dsa_host.hip, pma_host.hip, writes_host.hip, build_host.hip,
+// spmv_host.hip, spmm_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
+// (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h
+// and export_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
 #pragma once
 #include "../../include/dsa.h"
@@ -55,6 +57,25 @@ struct ApiRange {
 extern int g_device;                      // the device new handles are created on (dsa_set_device)
 extern const int g_wait_policy_default;   // default of Pma::wait_policy (DSA_WAIT_POLICY=1: yield-friendly waits for every new handle)
 extern const bool g_force_wide;           // dev knob: DSA_KEYS_WIDE=1 keeps every structure in 64-bit keys
+
+// What an export keeps on its orientation (export_host.hip): a pooled device scratch, grown on demand, and the pinned words its
+// kernels hand their results to, allocated at the first export.  Sequence numbers start at 1.
+struct ExportArea {
+    void* scratch = nullptr; size_t bytes = 0;
+    unsigned long long* pin = nullptr; unsigned long long seq = 0;
+    void ensure(hipStream_t stream, size_t need, int words);      // at least `need` bytes of scratch (waits for `stream` before it lets go of a smaller one) and `words` pinned words
+    unsigned long long next() { return ++seq; }
+    void release();
+};
+
+// Pooled device staging of a host-form entry point: up to four blocks, released once the stream has drained (also on an error
+// after a launch).
+struct DevStaging {
+    hipStream_t s; void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    explicit DevStaging(hipStream_t stream) : s(stream) {}
+    DevStaging(const DevStaging&) = delete;
+    ~DevStaging() { if (p[0] || p[1] || p[2] || p[3]) { (void)hipStreamSynchronize(s); for (void* q : p) pool_free(q); } }
+};
 
 // ------------------------------------------------------------------------------------------------
 // One packed-memory array resident in HBM, optionally with PackedCSC / MappedPackedCSC tables
@@ -123,11 +144,8 @@ struct Pma {
     // its device side: scratch of k_spmv_meta, pinned landing area of the 5 result words, and the epoch a prefetch (enqueued behind
     // the write batch that changed the layout) is in flight for
     unsigned long long* d_meta = nullptr; int64_t* h_meta = nullptr; unsigned long long meta_seq = 0; int64_t meta_inflight_epoch = -1;
-    // compressed export (compress.hip): per-tile counts and prefixes (pooled, grown on demand), pinned {error word, sequence number}
-    void* cx_scratch = nullptr; size_t cx_bytes = 0; unsigned long long* h_cx = nullptr; unsigned long long cx_seq = 0;
-    // selected export (select.hip): per-key spans, counts and prefixes (pooled, grown on demand), pinned {error word, cells, work items,
-    // sequence number} of the count and {error word, sequence number} of the emit
-    void* sel_scratch = nullptr; size_t sel_bytes = 0; unsigned long long* h_sel = nullptr; unsigned long long sel_seq = 0;
+    // compressed export (compress.hip): per-tile counts and prefixes; selected export (select.hip): per-key spans, counts and prefixes
+    ExportArea cx, sel;
     // thresholds  src/pma.jl:58,70,87
     double t_h = 0.7, t_0 = 0.92, p_h = 0.3, p_0 = 0.08, t_d = 0.0, p_d = 0.0;
 
@@ -251,11 +269,18 @@ dsa_mat* mat_from_coo_dev(const void* d_I, const void* d_J, const double* d_V, i
 dsa_mat* mat_from_compressed_dev(int32_t orientation, int32_t index_bits, int32_t index_base, const void* d_ptr, const void* d_idx,
                                  const double* d_vals, int64_t outer, int64_t inner, int64_t nnz);
 
-// ---- spmm_host.hip: the dense multi-vector product
+// ---- spmm_host.hip: the dense multi-vector product (spmm_host: X and Y in host memory, staged packed through HBM)
 void spmm_dev(dsa_mat* h, int32_t transpose, const double* d_x, int64_t nx, int64_t k, int64_t ldx, double* d_y, int64_t ny, int64_t ldy,
               hipStream_t s);
+void spmm_host(dsa_mat* h, int32_t transpose, const double* x, int64_t nx, int64_t k, int64_t ldx, double* y, int64_t ny, int64_t ldy);
 
-// ---- select_host.hip: the compressed form of selected columns / rows (d_* are device arrays; *nnz_out also with DSA_ECAP)
+// ---- export_host.hip: the compressed form of an orientation and of selected columns / rows (d_* are device arrays; *nnz_out also
+// with DSA_ECAP), and the check of an index format that the import shares: index_bits 32 | 64, index_base 0 | 1
+void check_index_format(int32_t index_bits, int32_t index_base);
+void to_compressed_dev(dsa_mat* h, int32_t orientation, int32_t index_bits, int32_t index_base, void* d_ptr, void* d_idx, double* d_vals,
+                       int64_t cap, int64_t* nnz_out);
+void to_compressed_host(dsa_mat* h, int32_t orientation, int32_t index_base, int64_t* ptr, int64_t* idx, double* vals, int64_t cap,
+                        int64_t* nnz_out);
 void select_compressed_dev(dsa_mat* h, int32_t orientation, int32_t index_bits, int32_t index_base, const int64_t* d_sel, int64_t nsel,
                            void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out);
 void select_compressed_host(dsa_mat* h, int32_t orientation, int32_t index_base, const int64_t* sel, int64_t nsel, int64_t* ptr,

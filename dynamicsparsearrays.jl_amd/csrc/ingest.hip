@@ -13,6 +13,7 @@
 // Bytes, compressed with ib-byte indices: ib * (outer + 1) (twice through the cache: the check reads the neighbour, the bisections hit
 // L2) + ib * nnz in, 16 * nnz out.  One atomic per workgroup and word; none on the entry stream.
 #include "ingest.h"
+#include "wave_dev.h"
 #include <algorithm>
 #include <climits>
 
@@ -112,8 +113,7 @@ __global__ __launch_bounds__(256) void k_in_keys(const IT* __restrict__ a, const
 __global__ void k_in_publish(const long long* __restrict__ acc, unsigned long long* __restrict__ pinned, unsigned long long seq) {
     if (threadIdx.x != 0) return;
     for (int q = 0; q < 5; ++q) __hip_atomic_store(pinned + q, (unsigned long long)acc[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __hip_atomic_store(pinned + 5, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_seq(pinned + 5, seq);
 }
 
 hipError_t launch_in_init(long long* d_acc, hipStream_t stream) {

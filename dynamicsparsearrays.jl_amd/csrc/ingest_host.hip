@@ -55,8 +55,7 @@ struct Ingest {
 };
 
 void check_index_args(int32_t index_bits, int32_t index_base, int64_t nnz) {
-    if (index_bits != 32 && index_bits != 64) fail(DSA_EARG, "index_bits must be 32 or 64");
-    if (index_base != 0 && index_base != 1) fail(DSA_EARG, "index_base must be 0 or 1");
+    check_index_format(index_bits, index_base);
     if (nnz < 0) fail(DSA_EARG, "negative length");
     if (nnz > 0xffffffffll) fail(DSA_EARG, "more than 2^32-1 triples in one call");
     if (index_bits == 32 && nnz + index_base > INT32_MAX) fail(DSA_EARG, "nnz + base does not fit 32-bit indices");

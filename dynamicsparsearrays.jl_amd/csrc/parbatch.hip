@@ -17,7 +17,7 @@
 //
 // The host (dsa_host.hip) applies the prefix in parallel and hands the op at d (and a growing chunk after it when the
 // prefixes stay short, e.g. ascending appends) to the sequential sequencer.  Result: bit-identical to the sequential order.
-#include "dsa_dev.h"
+#include "wave_dev.h"
 #include "find_dev.h"
 
 namespace dsa {
@@ -93,11 +93,6 @@ __device__ __forceinline__ void fp_cnt(int64_t, int64_t) {}
 #define DSA_FP_REGRESS 0
 #endif
 
-__device__ __forceinline__ int64_t pb_wave_sum(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ uint64_t pb_occ_load(const uint64_t* occ, int64_t w) {
     // L2-served load: other waves of the same launch update neighbouring bits of shared words with device-scope atomics
     return __hip_atomic_load(occ + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -108,7 +103,7 @@ __device__ int64_t pb_wave_count(const uint64_t* occ, int64_t ws, int64_t we, bo
     int64_t c = 0;
     for (int64_t w = w0 + lane_id(); w <= w1; w += 64)
         c += popc64((coherent ? pb_occ_load(occ, w) : occ[w]) & word_range_mask(w, lo0, hi0));
-    return pb_wave_sum(c);
+    return wave_reduce_add(c);
 }
 
 // Plan of ONE op by one wave (read-only): what the op would do on the current state, and its footprint.  w = index of the op in its
@@ -1017,16 +1012,6 @@ __device__ __forceinline__ void pb_bit_clear(uint64_t* occ, int64_t pos) {
     fp_touch(pos, pos);
     atomicAnd((unsigned long long*)(occ + ((pos - 1) >> 6)), ~(1ull << ((pos - 1) & 63)));
 }
-__device__ __forceinline__ uint32_t pb_wave_excl_scan(uint32_t v) {
-    const int lane = lane_id();
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x - v;
-}
 
 // pack! + spread! of [ws, we] (W <= PB_MAX_W) holding m cells, by one wave  (src/moves.jl:94-140)
 __device__ void pb_wave_rebalance(KeyArr keys, double* vals, uint64_t* occ, int64_t* sems, int64_t ws, int64_t we, int64_t m,
@@ -1038,7 +1023,7 @@ __device__ void pb_wave_rebalance(KeyArr keys, double* vals, uint64_t* occ, int6
     if (W >= 64) {
         const int nwords = (int)(W >> 6);                          // <= 16
         const uint64_t myword = lane < nwords ? pb_occ_load(occ, w0 + lane) : 0ull;
-        const uint32_t myoff = pb_wave_excl_scan((uint32_t)popc64(myword));
+        const uint32_t myoff = wave_excl_scan((uint32_t)popc64(myword));
         for (int w = 0; w < nwords; ++w) {
             const uint64_t mask = __shfl(myword, w, 64);
             const uint32_t off = __shfl(myoff, w, 64);
@@ -1612,8 +1597,7 @@ __global__ __launch_bounds__(256) void k_publish(const RoundState* rs, const Ctl
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
     if (threadIdx.x == 0) {
-        __atomic_thread_fence(__ATOMIC_RELEASE);
-        __hip_atomic_store(pub.host_seq, (unsigned long long)(unsigned int)rs->seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        publish_seq(pub.host_seq, (unsigned long long)(unsigned int)rs->seq);
     }
 }
 

@@ -64,10 +64,8 @@ void pma_destroy(Pma& P) {
     spmv_plan_drop(P);
     if (P.d_meta) hipFree(P.d_meta);
     pinned_free(P.h_meta);
-    pool_free(P.cx_scratch);
-    pinned_free(P.h_cx);
-    pool_free(P.sel_scratch);
-    pinned_free(P.h_sel);
+    P.cx.release();
+    P.sel.release();
     if (P.tmerge.sems2) hipFree(P.tmerge.sems2);
     if (P.tmerge.keys2) hipFree(P.tmerge.keys2);
     if (P.tmerge.pkey) hipFree(P.tmerge.pkey);
@@ -381,7 +379,7 @@ void pma_info(Pma& P, int64_t nb_partitions_or_len, int64_t* info) {
                                (P.has_sems ? c.table_cap * 8 : 0) + (P.has_cols ? c.table_cap * 9 : 0) + 2 * P.tmerge_cap * 8 +
                                (P.d_ops ? P.ops_cap * (int64_t)sizeof(Op) + (P.ops_cap / 64 + 8) * 8 : 0) + (P.d_opsrc ? P.opsrc_cap * 24 : 0) +      // op array, run-break bitmap, batch columns
                                P.plan.bytes +     // the SpMV plan: 12 B per stored cell + offsets
-                               (int64_t)P.sel_bytes;      // scratch of the selected export: 32 B per key of the longest selection so far
+                               (int64_t)P.sel.bytes;      // scratch of the selected export: 32 B per key of the longest selection so far
 }
 
 void export_slots(Pma& P, int64_t* keys, double* vals, uint8_t* occ, int64_t cap) {

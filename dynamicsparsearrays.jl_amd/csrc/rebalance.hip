@@ -14,7 +14,7 @@
 //                  every owned destination offset — gaps included, so lines are written whole — stored as 16-byte
 //                  key / value pairs, occupancy words closed-form, semaphore positions scattered to the table.
 //   k_tile_count / k_tile_scan : flat prefix (count, then a one-workgroup scan) for k_compact / k_permute / views
-#include "dsa_dev.h"
+#include "wave_dev.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -35,22 +35,6 @@ __device__ __forceinline__ uint64_t range_mask_for_word(int64_t w, int64_t lo0, 
     if (z > 63) z = 63;
     const uint64_t upto = (z == 63) ? ~0ull : ((1ull << (z + 1)) - 1ull);
     return upto & ~mask_lt((int)a);
-}
-
-__device__ __forceinline__ uint32_t wave_reduce_add(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v) {
-    const int lane = lane_id();
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x - v;
 }
 
 // 256-thread workgroups, 16 tiles each (wave w: tiles 16b+4w .. +3): the four occupancy loads of a lane are in flight together

@@ -22,16 +22,12 @@
 // chunks c / 2 times its bitmap, 1/64 of the slot bytes per pass).  Bytes out: (ib + 8) * total + ib * (nsel + 1).  Nothing is
 // proportional to the capacity.
 #include "select.h"
+#include "export_dev.h"
 #include "find_dev.h"
 #include <type_traits>
 
 namespace dsa {
 
-constexpr int SEL_CHUNK_SHIFT = 11;                      // 2048 slots = 32 bitmap words per work item, the tile of compress.hip
-constexpr int64_t SEL_CHUNK = int64_t(1) << SEL_CHUNK_SHIFT;
-constexpr int SEL_WORDS = (int)(SEL_CHUNK >> 6);
-constexpr int SEL_U = 8;                                 // bitmap words whose keys and values a wave requests at once
-constexpr int SEL_SCAN_THREADS = 1024;
 constexpr int64_t SEL_EMIT_BLOCKS_MAX = 4096;            // emit grid: beyond 16384 work items a wave strides over several (one ticket per
                                                          // workgroup at the end: a million of them on one address cost more than the cells)
 
@@ -54,27 +50,12 @@ static SelScratch sel_carve(void* base, int64_t nsel) {
 }
 size_t select_scratch_bytes(int64_t nsel) { return (size_t)(nsel > 0 ? nsel : 0) * 32 + 8; }
 
-__device__ __forceinline__ uint64_t sel_readlane64(uint64_t v, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint32_t sel_wave_or(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int64_t sel_wave_sum(int64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (int64_t)__shfl_xor((long long)v, o, 64);
-    return v;
-}
 // occupied slots of [from, to) (0-based, from < to): the lanes stride over the words, first and last word masked
 __device__ __forceinline__ int64_t sel_span_popc(const uint64_t* __restrict__ occ, int64_t from, int64_t to, int lane) {
     int64_t c = 0;
     const int64_t w1 = (to - 1) >> 6;
     for (int64_t w = (from >> 6) + lane; w <= w1; w += 64) c += popc64(occ[w] & word_range_mask(w, from, to - 1));
-    return sel_wave_sum(c);
+    return wave_reduce_add(c);
 }
 
 // one wave per selected key
@@ -99,7 +80,7 @@ __global__ __launch_bounds__(256) void k_sel_count(const uint64_t* __restrict__ 
                 const int64_t e = e0 + lane;
                 const int64_t v = e < table_len ? sems[e] : 0;
                 const uint64_t m = __ballot(v != 0);
-                if (m) { nx = (int64_t)sel_readlane64((uint64_t)v, __ffsll((unsigned long long)m) - 1); break; }
+                if (m) { nx = (int64_t)readlane64((uint64_t)v, __ffsll((unsigned long long)m) - 1); break; }
             }
             const int64_t end = nx ? nx - 1 : capacity;
             if (sp < 1 || sp > capacity || end < sp || end > capacity) err = 2u;      // tables out of step with the slots
@@ -110,53 +91,27 @@ __global__ __launch_bounds__(256) void k_sel_count(const uint64_t* __restrict__ 
     if (lane != 0) return;
     s.lo[j] = lo; s.hi[j] = hi;
     s.off[j] = cnt;
-    s.choff[j] = cnt > 0 ? ((hi - 1) >> SEL_CHUNK_SHIFT) - (lo >> SEL_CHUNK_SHIFT) + 1 : 0;
+    s.choff[j] = cnt > 0 ? ((hi - 1) >> EX_TILE_SHIFT) - (lo >> EX_TILE_SHIFT) + 1 : 0;
     if (err) atomicOr(s.err, err);
 }
 
 // one workgroup: off / choff become exclusive prefixes in place, ptr[j] = base + off[j], ptr[nsel] = base + total
 template <typename IT>
-__global__ __launch_bounds__(SEL_SCAN_THREADS) void k_sel_scan(SelScratch s, int64_t nsel, int64_t base, IT* __restrict__ ptr,
-                                                               unsigned long long* pinned, unsigned long long seq) {
-    __shared__ unsigned long long sO[SEL_SCAN_THREADS], sS[SEL_SCAN_THREADS];
-    const int t = threadIdx.x;
-    constexpr int PER = 8;
-    unsigned long long carry_o = 0, carry_s = 0;
-    for (int64_t c0 = 0; c0 < nsel; c0 += (int64_t)SEL_SCAN_THREADS * PER) {
-        unsigned long long vo[PER], vs[PER], to = 0, ts = 0;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int64_t i = c0 + (int64_t)t * PER + q;
-            vo[q] = i < nsel ? (unsigned long long)s.off[i] : 0ull;
-            vs[q] = i < nsel ? (unsigned long long)s.choff[i] : 0ull;
-            to += vo[q]; ts += vs[q];
-        }
-        sO[t] = to; sS[t] = ts;
-        __syncthreads();
-        for (int o = 1; o < SEL_SCAN_THREADS; o <<= 1) {         // inclusive scan (Hillis-Steele)
-            const unsigned long long a = t >= o ? sO[t - o] : 0ull, b = t >= o ? sS[t - o] : 0ull;
-            __syncthreads();
-            sO[t] += a; sS[t] += b;
-            __syncthreads();
-        }
-        unsigned long long ro = carry_o + sO[t] - to, rs = carry_s + sS[t] - ts;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int64_t i = c0 + (int64_t)t * PER + q;
-            if (i < nsel) { s.off[i] = (int64_t)ro; s.choff[i] = (int64_t)rs; ptr[i] = (IT)(base + (int64_t)ro); }
-            ro += vo[q]; rs += vs[q];
-        }
-        carry_o += sO[SEL_SCAN_THREADS - 1]; carry_s += sS[SEL_SCAN_THREADS - 1];
-        __syncthreads();
-    }
-    if (t != 0) return;
+__global__ __launch_bounds__(EX_SCAN_THREADS) void k_sel_scan(SelScratch s, int64_t nsel, int64_t base, IT* __restrict__ ptr,
+                                                              unsigned long long* pinned, unsigned long long seq) {
+    unsigned long long carry_o, carry_s;
+    block_excl_scan2(s.off, s.choff, nsel,
+                     [&](int64_t i, unsigned long long ro, unsigned long long rs) {
+                         s.off[i] = (int64_t)ro; s.choff[i] = (int64_t)rs; ptr[i] = (IT)(base + (int64_t)ro);
+                     },
+                     carry_o, carry_s);
+    if (threadIdx.x != 0) return;
     ptr[nsel] = (IT)(base + (int64_t)carry_o);
     const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(pinned + 1, carry_o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     __hip_atomic_store(pinned + 2, carry_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __hip_atomic_store(pinned + 3, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_seq(pinned + 3, seq);
 }
 
 struct SelArgs {
@@ -173,7 +128,6 @@ __global__ __launch_bounds__(256) void k_sel_emit(KeyArr keys, const double* __r
     typedef typename std::conditional<WIDE, int64_t, int32_t>::type key_t;
     const key_t* __restrict__ kp = static_cast<const key_t*>(keys.p);
     IT* __restrict__ idx = static_cast<IT*>(a.idx);
-    __shared__ uint32_t sErr[4];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t below = mask_lt(lane);
@@ -197,28 +151,28 @@ __global__ __launch_bounds__(256) void k_sel_emit(KeyArr keys, const double* __r
         const int64_t j = L + (nb ? __ffsll((unsigned long long)nb) - 1 : 64) - 1;
         if (j < 0 || j >= a.nsel) { err |= 2u; continue; }
         const int64_t lo = s.lo[j], hi = s.hi[j];
-        const int64_t tile = (lo >> SEL_CHUNK_SHIFT) + (w - s.choff[j]);
-        const int64_t t0 = tile << SEL_CHUNK_SHIFT;
-        const int64_t cs = lo > t0 ? lo : t0, ce = hi < t0 + SEL_CHUNK ? hi : t0 + SEL_CHUNK;
+        const int64_t tile = (lo >> EX_TILE_SHIFT) + (w - s.choff[j]);
+        const int64_t t0 = tile << EX_TILE_SHIFT;
+        const int64_t cs = lo > t0 ? lo : t0, ce = hi < t0 + EX_TILE ? hi : t0 + EX_TILE;
         if (ce <= cs) { err |= 2u; continue; }
         int64_t run = s.off[j] + (cs > lo ? sel_span_popc(occ, lo, cs, lane) : 0);      // output position of the chunk's first cell
-        const int64_t w0 = tile * SEL_WORDS;
-        const uint64_t myword = lane < SEL_WORDS && ((w0 + lane) << 6) < ce ? occ[w0 + lane] & word_range_mask(w0 + lane, cs, ce - 1) : 0ull;
+        const int64_t w0 = tile * EX_WORDS;
+        const uint64_t myword = lane < EX_WORDS && ((w0 + lane) << 6) < ce ? occ[w0 + lane] & word_range_mask(w0 + lane, cs, ce - 1) : 0ull;
         const uint32_t nz = (uint32_t)__ballot(myword != 0ull);  // words with a cell: a short span leaves most groups of a chunk empty
-        for (int q = 0; q < SEL_WORDS; q += SEL_U) {
-            if (((nz >> q) & ((1u << SEL_U) - 1u)) == 0u) continue;
-            uint64_t wd[SEL_U];
-            int64_t k[SEL_U];
-            double v[SEL_U];
+        for (int q = 0; q < EX_WORDS; q += EX_U) {
+            if (((nz >> q) & ((1u << EX_U) - 1u)) == 0u) continue;
+            uint64_t wd[EX_U];
+            int64_t k[EX_U];
+            double v[EX_U];
 #pragma unroll
-            for (int u = 0; u < SEL_U; ++u) {
-                wd[u] = sel_readlane64(myword, q + u);
+            for (int u = 0; u < EX_U; ++u) {
+                wd[u] = readlane64(myword, q + u);
                 const int64_t i = ((w0 + q + u) << 6) + lane;
                 k[u] = -1; v[u] = 0.0;
                 if ((wd[u] >> lane) & 1ull) { k[u] = (int64_t)__builtin_nontemporal_load(kp + i); v[u] = __builtin_nontemporal_load(vals + i); }
             }
 #pragma unroll
-            for (int u = 0; u < SEL_U; ++u) {
+            for (int u = 0; u < EX_U; ++u) {
                 if ((wd[u] >> lane) & 1ull) {
                     const int64_t pos = run + popc64(wd[u] & below);
                     if (k[u] == SEM_KEY || pos >= a.total) {
@@ -233,20 +187,7 @@ __global__ __launch_bounds__(256) void k_sel_emit(KeyArr keys, const double* __r
             }
         }
     }
-    err = sel_wave_or(err);
-    if (lane == 0) sErr[wv] = err;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    err = sErr[0] | sErr[1] | sErr[2] | sErr[3];
-    if (err) __hip_atomic_fetch_or(s.err, err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_s_waitcnt(0);
-    const uint32_t tk = __hip_atomic_fetch_add(s.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tk != gridDim.x - 1) return;
-    // the last workgroup: every other one has added its bits before taking its ticket
-    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(a.pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    __hip_atomic_store(a.pinned + 1, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    emit_epilogue(err, lane, wv, s.err, s.ticket, a.pinned, a.seq);
 }
 
 hipError_t launch_select_count(const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,
@@ -261,9 +202,9 @@ hipError_t launch_select_count(const uint64_t* occ, int64_t capacity, const int6
         hipLaunchKernelGGL(k_sel_count, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, occ, capacity, sems, col_keys, col_live,
                            table_len, dense || col_live == nullptr, d_sel, nsel, dim_out, s);
     if (index_bits == 32)
-        hipLaunchKernelGGL(k_sel_scan<int32_t>, dim3(1), dim3(SEL_SCAN_THREADS), 0, stream, s, nsel, base, static_cast<int32_t*>(d_ptr), pinned4, seq);
+        hipLaunchKernelGGL(k_sel_scan<int32_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, nsel, base, static_cast<int32_t*>(d_ptr), pinned4, seq);
     else
-        hipLaunchKernelGGL(k_sel_scan<int64_t>, dim3(1), dim3(SEL_SCAN_THREADS), 0, stream, s, nsel, base, static_cast<int64_t*>(d_ptr), pinned4, seq);
+        hipLaunchKernelGGL(k_sel_scan<int64_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, nsel, base, static_cast<int64_t*>(d_ptr), pinned4, seq);
     return hipGetLastError();
 }
 

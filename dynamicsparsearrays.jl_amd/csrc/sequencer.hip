@@ -16,7 +16,7 @@
 //                            (src/moves.jl:94-171)
 // Windows larger than that, _extend! / _shrink!, and table growth are handed back to the host
 // ("yield"), which runs the grid-wide kernel of rebalance.hip and relaunches the sequencer.
-#include "dsa_dev.h"
+#include "wave_dev.h"
 #include "find_dev.h"
 
 namespace dsa {
@@ -120,17 +120,6 @@ __device__ void blk_shift_left(Seq& S, int64_t a, int64_t b, bool last_occ) {
 __device__ __forceinline__ void occ_set(Seq& S, int64_t pos) { S.occ[(pos - 1) >> 6] |= 1ull << ((pos - 1) & 63); }
 __device__ __forceinline__ void occ_clear(Seq& S, int64_t pos) { S.occ[(pos - 1) >> 6] &= ~(1ull << ((pos - 1) & 63)); }
 
-__device__ __forceinline__ uint32_t seq_wave_excl_scan(uint32_t v) {
-    const int lane = lane_id();
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    return x - v;
-}
-
 // pack! + spread! of [ws, we] (W <= SMALL_W) holding m cells  src/moves.jl:94-171
 __device__ void blk_rebalance_small(Seq& S, int64_t ws, int64_t we, int64_t m) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -146,7 +135,7 @@ __device__ void blk_rebalance_small(Seq& S, int64_t ws, int64_t we, int64_t m) {
             for (int g0 = 0; g0 < nwords; g0 += 64) {
                 const int w = g0 + lane;
                 const uint32_t pc = w < nwords ? (uint32_t)popc64(S.occ[w0 + w]) : 0u;
-                const uint32_t ex = seq_wave_excl_scan(pc);
+                const uint32_t ex = wave_excl_scan(pc);
                 if (w < nwords) S.sWordOff[w] = carry + ex;
                 carry += __shfl(ex + pc, 63, 64);
             }
@@ -371,16 +360,7 @@ hipError_t launch_op_breaks(const Op* ops, int64_t n, int mode, uint64_t* breaks
     return hipGetLastError();
 }
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t y = __shfl_xor(v, o, 64); v = y > v ? y : v; }
-    return v;
-}
-
 __device__ __forceinline__ uint32_t rdlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
-__device__ __forceinline__ uint64_t rdlane64(uint64_t v, int l) {
-    return ((uint64_t)rdlane((uint32_t)(v >> 32), l) << 32) | (uint64_t)rdlane((uint32_t)v, l);
-}
 
 // memo of spread! patterns for windows of up to 256 slots: the pattern depends on (W, c) only and an append run keeps
 // hitting the same few (level, count) pairs.  Filled on first use by wave 0.
@@ -924,7 +904,7 @@ __device__ void wave_fast_appends(Seq& S, RunComm* rc, RunMemo* memo, const uint
                 io->lo[lane] = lvl_valid ? (uint32_t)S.lo[lane] : 1u; io->hi[lane] = lvl_valid ? (uint32_t)S.hi[lane] : 0u;
                 io->wb[lane] = my_wb;
                 if (lane == 0) {
-                    io->lw = rdlane64(word, 63); io->idx = (int64_t)idx; io->end = (int64_t)end; io->nlow = nlow; io->seg = (int)seg;
+                    io->lw = readlane64(word, 63); io->idx = (int64_t)idx; io->end = (int64_t)end; io->nlow = nlow; io->seg = (int)seg;
                     io->need = 0; io->progressed = 0; io->reb = 0; io->slots = 0;
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -993,7 +973,7 @@ __device__ void wave_fast_appends(Seq& S, RunComm* rc, RunMemo* memo, const uint
                 // semaphore (always inserted "after position capacity", src/pcsr.jl:99-112).  The nearest empty slot left
                 // of the last slot takes the shift; almost always it is in the last word.
                 if (((cap - 1) >> RUN_BLOCK_LOG2) != blk) break;
-                const uint64_t wl = rdlane64(word, last_lane);
+                const uint64_t wl = readlane64(word, last_lane);
                 uint64_t zl = ~wl & ~cap_bit;
                 if (cap < 64) zl &= (1ull << cap) - 1ull;
                 uint32_t best;
@@ -1020,7 +1000,7 @@ __device__ void wave_fast_appends(Seq& S, RunComm* rc, RunMemo* memo, const uint
             const int lane_ip = __builtin_amdgcn_readfirstlane((int)(((ip - 1) >> 6) & 63));
             const int bit_ip = (int)((ip - 1) & 63);
             // _look_for_rebalance!  src/pma.jl:105-141: lane h evaluates level h
-            const uint64_t word_ip = rdlane64(word, lane_ip);
+            const uint64_t word_ip = readlane64(word, lane_ip);
             uint32_t c_l = (uint32_t)popc64(word_ip & (my_low_mask << (bit_ip & my_low_align)));
             uint64_t acc = __ballot(lvl_low && my_lo <= c_l && c_l <= my_hi);
             if (acc == 0 && any_mid) {
@@ -1253,7 +1233,7 @@ __global__ __launch_bounds__(1024) void k_run_expand(const Op* ops, int64_t i0, 
             o = ops[i0 + j];
             newc = (j == 0) ? ((tl0 == 0 || o.b != lastcol) ? 1u : 0u) : (o.b != ops[i0 + j - 1].b ? 1u : 0u);
         }
-        const uint32_t ex = seq_wave_excl_scan(newc);
+        const uint32_t ex = wave_excl_scan(newc);
         if (lane == 63) wsum[wv] = ex + newc;
         __syncthreads();
         uint32_t woff = 0;
@@ -1985,8 +1965,7 @@ __global__ __launch_bounds__(SEQ_BLOCK) void k_sequencer(KeyArr keys, double* va
         __builtin_amdgcn_s_waitcnt(0);
         __syncthreads();
         if (threadIdx.x == 0) {
-            __atomic_thread_fence(__ATOMIC_RELEASE);
-            __hip_atomic_store(host_seq, (unsigned long long)seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            publish_seq(host_seq, (unsigned long long)seq);
         }
     }
 }
@@ -2061,8 +2040,7 @@ __global__ __launch_bounds__(64) void k_get_small(int mode, KeyArr keys, const d
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {
         __hip_atomic_store(io + 192, (int64_t)(eb ? e0 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __atomic_thread_fence(__ATOMIC_RELEASE);
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(io) + 193, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        publish_seq(reinterpret_cast<unsigned long long*>(io) + 193, seq);
     }
 }
 hipError_t launch_get_small(int mode, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems,
@@ -2280,8 +2258,7 @@ __global__ __launch_bounds__(VIEW_BLOCK) void k_view_small(KeyArr keys, const do
             const int64_t m5[5] = {from, to, err, pid, cnt};
             for (int q = 0; q < 5; ++q) __hip_atomic_store(host + q, m5[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __hip_atomic_store(host + 6, last_key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __atomic_thread_fence(__ATOMIC_RELEASE);
-            __hip_atomic_store(reinterpret_cast<unsigned long long*>(host) + 5, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            publish_seq(reinterpret_cast<unsigned long long*>(host) + 5, seq);
         }
     }
 }

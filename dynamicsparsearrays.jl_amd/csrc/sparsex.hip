@@ -17,24 +17,9 @@
 #include <algorithm>
 #include <cstdint>
 #include <mutex>
-#include "dsa_dev.h"
+#include "wave_dev.h"
 
 namespace dsa {
-
-namespace {
-__device__ __forceinline__ uint32_t sx_wave_reduce_add(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t sx_wave_excl_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o, 64); if (lane >= o) inc += y; }
-    return inc - v;
-}
-}  // namespace
 
 // ---- accumulate ---------------------------------------------------------------------------------------------------------------
 // x entries come from HBM or straight from pinned host memory (few entries: no copy command in front of the launch).
@@ -134,7 +119,7 @@ __global__ __launch_bounds__(256) void k_spx_count(const unsigned long long* __r
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int64_t t = (int64_t)blockIdx.x * SX_CNT_TILES + wv * 4 + i;
-        const uint32_t r = sx_wave_reduce_add(pc[i]);
+        const uint32_t r = wave_reduce_add(pc[i]);
         if (lane == 0 && t < ntiles) __hip_atomic_store(tile_cnt + t, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __builtin_amdgcn_s_waitcnt(0);
@@ -153,7 +138,7 @@ __global__ __launch_bounds__(256) void k_spx_count(const unsigned long long* __r
 #pragma unroll
         for (int i = 0; i < 4; ++i) c[i] = i0 + i < ntiles ? __hip_atomic_load(tile_cnt + i0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
         const uint32_t local = c[0] + c[1] + c[2] + c[3];
-        const uint32_t ex = sx_wave_excl_scan(local);
+        const uint32_t ex = wave_excl_scan(local);
         if (lane == 63) wsum[wv] = ex + local;
         __syncthreads();
         uint32_t run = carry + ex, total = 0;
@@ -179,7 +164,7 @@ __global__ __launch_bounds__(64) void k_spx_emit(unsigned long long* __restrict_
     const int64_t t = blockIdx.x;
     const int64_t wl = t * 64 + lane;
     const uint64_t myword = wl < nwords ? bm[wl] : 0ull;
-    const uint32_t myoff = sx_wave_excl_scan((uint32_t)__popcll(myword));
+    const uint32_t myoff = wave_excl_scan((uint32_t)__popcll(myword));
     const int64_t base = tile_off[t];
     uint64_t nz = __ballot(myword != 0ull);
     while (nz) {
@@ -210,8 +195,7 @@ __global__ __launch_bounds__(64) void k_spx_emit(unsigned long long* __restrict_
             __hip_atomic_store(ticket + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (host != nullptr) {
                 __hip_atomic_store(host + 0, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                __atomic_thread_fence(__ATOMIC_RELEASE);
-                __hip_atomic_store(reinterpret_cast<unsigned long long*>(host) + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                publish_seq(reinterpret_cast<unsigned long long*>(host) + 1, seq);
             }
         }
     }

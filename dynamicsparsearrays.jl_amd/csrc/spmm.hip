@@ -28,6 +28,7 @@
 //   LDS 31 744 / 40 960 B per workgroup (per wave 576 x 8 B values + 576 x 4 | 8 B rows + 512 x 2 B semaphore list): 5 / 3 workgroups
 //   = 20 / 12 waves per CU, which is the limiter; 62 VGPRs, 80 SGPRs, no scratch in every instantiation.
 #include "spmm.h"
+#include "wave_dev.h"
 #include <type_traits>
 
 namespace dsa {
@@ -46,12 +47,6 @@ struct MmWave {
     key_t c[MM_CELLS];                   // 0-based row of X, -1: contributes nothing (semaphore, key outside 1..nx)
     uint16_t sem[MM_OWN_WORDS * 64];     // compacted positions of the span's semaphores
 };
-
-__device__ __forceinline__ uint64_t mm_uniform(uint64_t w) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w >> 32));
-    return ((uint64_t)hi << 32) | lo;
-}
 
 // Loads words [w0, w0 + 9) of the slot array (clamped to the array) and compacts their occupied slots into S.  Semaphores of the
 // first OWN words are listed in S.sem (nsem of them); behind those words the first semaphore ends the compaction (closed = true:
@@ -84,7 +79,7 @@ __device__ __forceinline__ int mm_load_compact(const typename std::conditional<W
     closed = false;
 #pragma unroll
     for (int j = 0; j < MM_LOAD_WORDS; ++j) {
-        uint64_t o = (closed || w0 + j >= nwords) ? 0ull : mm_uniform(ow[j]);
+        uint64_t o = (closed || w0 + j >= nwords) ? 0ull : readfirstlane64(ow[j]);
         const bool issem = ((o >> lane) & 1ull) && k[j] == (key_t)SEM_KEY;
         const uint64_t sb = __ballot(issem);
         if (j >= OWN && sb != 0ull) {                    // the open row ends in front of this semaphore

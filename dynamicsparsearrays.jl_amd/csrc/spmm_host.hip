@@ -1,5 +1,5 @@
 // csrc/spmm_host.hip — host side of the dense multi-vector product (dsa_mat_spmm_dense[_dev]): argument checks, the orientation that
-// is walked, the zeroing of Y and the launch.  Host-only unit: the kernel is in spmm.hip.
+// is walked, the zeroing of Y, the launch, and the staging of operands in host memory.  Host-only unit: the kernel is in spmm.hip.
 #include "host.h"
 #include "spmm.h"
 
@@ -24,6 +24,29 @@ void spmm_dev(dsa_mat* h, int32_t transpose, const double* d_x, int64_t nx, int6
     // the slot stream goes around the cache when X does not fit an XCD's 4 MB L2 beside it (the rule of SPMV_PLAIN_STREAM)
     const bool nt = nx * k * (int64_t)sizeof(double) > (3 << 20);
     LAUNCH("spmm", launch_spmm(P.K(), P.V(), P.O(), P.capacity(), P.col_keys, P.h_ctl->table_len, d_x, nx, k, ldx, d_y, ny, ldy, nt, s));
+}
+
+// the same with X and Y in host memory: packed device staging (leading dimension k), one stream sync at the end
+void spmm_host(dsa_mat* h, int32_t transpose, const double* x, int64_t nx, int64_t k, int64_t ldx, double* y, int64_t ny, int64_t ldy) {
+    mat_flush(h);
+    if (!h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
+    if (k < 1) fail(DSA_EARG, "k must be at least 1");
+    if (ldx < k || ldy < k) fail(DSA_EARG, "leading dimension smaller than k");
+    if (nx < 0 || ny < 0) fail(DSA_EARG, "negative length");
+    if ((nx > 0 && !x) || (ny > 0 && !y)) fail(DSA_EARG, "operand is NULL");
+    Pma& P = transpose ? h->col : h->row;
+    DevStaging b(P.stream);
+    const size_t row = (size_t)k * sizeof(double);
+    if (nx > 0) {
+        HIPCHK(pool_alloc(&b.p[0], (size_t)nx * row));
+        HIPCHK(hipMemcpy2DAsync(b.p[0], row, x, (size_t)ldx * sizeof(double), row, (size_t)nx, hipMemcpyHostToDevice, P.stream));
+    }
+    if (ny > 0) {
+        HIPCHK(pool_alloc(&b.p[1], (size_t)ny * row));
+        spmm_dev(h, transpose, static_cast<const double*>(b.p[0]), nx, k, k, static_cast<double*>(b.p[1]), ny, k, P.stream);
+        HIPCHK(hipMemcpy2DAsync(y, (size_t)ldy * sizeof(double), b.p[1], row, row, (size_t)ny, hipMemcpyDeviceToHost, P.stream));
+    }
+    HIPCHK(hipStreamSynchronize(P.stream));
 }
 
 }  // namespace host

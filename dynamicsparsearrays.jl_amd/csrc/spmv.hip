@@ -14,7 +14,7 @@
 //
 // Bound: HBM / fabric.  Algorithmic bytes per launch = 16*capacity + 8*nx + 8*ny: the flat
 // scan streams every slot (gaps included — they are part of the bit-identical layout) once.
-#include "dsa_dev.h"
+#include "wave_dev.h"
 #include <type_traits>
 
 namespace dsa {
@@ -25,12 +25,6 @@ constexpr int SP_WAVES = SP_BLOCK / 64;
 constexpr int SP_PER_WAVE = SP_TILE / SP_WAVES;     // 512 slots = 8 words
 constexpr int SP_WORDS_PER_WAVE = SP_PER_WAVE / 64;
 constexpr int SP_BACK_WORDS = 32;                    // backward ballot scan limit before the table bisection
-
-__device__ __forceinline__ double wave_reduce_add_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // partition id (1-based) whose semaphore is the last one located at a 0-based slot < b0, or 0.
 // Executed by one full wave.
@@ -394,7 +388,7 @@ __device__ __forceinline__ void gather_tile(KeyArr keys, const double* __restric
             open_row = sem_row(a).row;
             double sum = 0.0;
             for (int t = a + 1 + lane; t < endpos; t += 64) sum += sP[t];
-            open_sum = wave_reduce_add_f64(sum);
+            open_sum = wave_reduce_add(sum);
         }
     } else {
         // few, long rows: the whole wave sums each of them
@@ -406,7 +400,7 @@ __device__ __forceinline__ void gather_tile(KeyArr keys, const double* __restric
             if (ZFILL && lane == 0) zero_fill_front(y, ny, sr.prev, sr.row, is_last && sr.last);
             double sum = 0.0;
             for (int t = a + 1 + lane; t < end; t += 64) sum += sP[t];
-            sum = wave_reduce_add_f64(sum);
+            sum = wave_reduce_add(sum);
             if (!is_last || closed) { if (lane == 0 && sr.row >= 1 && sr.row <= ny) y[sr.row - 1] = sum; }
             else { open_row = sr.row; open_sum = sum; }
         }
@@ -424,7 +418,7 @@ __device__ __forceinline__ void gather_tile(KeyArr keys, const double* __restric
             const int lim = sbw ? __ffsll((unsigned long long)sbw) - 1 : 64;
             double pp = 0.0;
             if (bit && lane < lim && kk >= 1 && kk <= nx) pp = product_of(vv, x[kk - 1], count_pass);
-            open_sum += wave_reduce_add_f64(pp);
+            open_sum += wave_reduce_add(pp);
             closed = sbw != 0;
         }
         if (w0 + 2 * SW_WORDS >= nwords) closed = true;       // nothing behind the next span: nobody else adds to this row
@@ -449,7 +443,7 @@ __device__ __forceinline__ void gather_tile(KeyArr keys, const double* __restric
             const int head_end = nsem > 0 ? (int)sList[0] : own_words * 64;
             double sum = 0.0;
             for (int t = lane; t < head_end; t += 64) sum += sP[t];
-            sum = wave_reduce_add_f64(sum);
+            sum = wave_reduce_add(sum);
             const int64_t c = carry_in_partition(keys, vals, occ, sems, table_len, (w0 - SW_WORDS > 0 ? w0 - SW_WORDS : 0) << 6);
             if (c >= 1 && c <= table_len) {
                 const int64_t row = part_keys[c - 1];
@@ -591,8 +585,7 @@ __global__ __launch_bounds__(256) void k_spmv_meta(const int64_t* __restrict__ s
         // no copy command, no event, no driver call on the host side of the hand-over
         const unsigned long long r[5] = {ext, gap, (unsigned long long)key_first, (unsigned long long)key_last, bad ? 1ull : 0ull};
         for (int q = 0; q < 5; ++q) __hip_atomic_store(out + q, r[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __atomic_thread_fence(__ATOMIC_RELEASE);
-        __hip_atomic_store(out + 5, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        publish_seq(out + 5, seq);
         __hip_atomic_store(ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -793,8 +786,7 @@ __global__ __launch_bounds__(PLAN_SCAN_THREADS) void k_plan_scan(PlanDev pl, int
         const bool ok = sBad == 0u && (long long)cells <= pl.cap_cells && (long long)parts == table_len && cells < 0xffffffffull;
         __hip_atomic_store(out + 0, ok ? 1ull : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(out + 1, cells, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __atomic_thread_fence(__ATOMIC_RELEASE);
-        __hip_atomic_store(out + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        publish_seq(out + 2, seq);
     }
 }
 

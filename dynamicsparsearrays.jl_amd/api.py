@@ -302,6 +302,12 @@ class Transposed:
     def __matmul__(self, X):
         return self.array.matmul(X, transpose=True)
 
+    def reduce(self, kind, per, out=None):
+        """the reduction per row / column of the transpose: per column / row of the matrix"""
+        if per not in ("row", "column"):
+            raise B.DsaArgumentError(B.EARG, "per must be 'row' or 'column'")
+        return self.array.reduce(kind, "column" if per == "row" else "row", out=out)
+
 
 class DynamicSparseMatrix(_Handle):
     """DynamicSparseMatrix{Int64,Int64,Float64}  (src/matrix.jl:1-8)."""
@@ -728,6 +734,106 @@ class DynamicSparseMatrix(_Handle):
         self._require_spmm()
         self.b.call("mat_spmm_dense_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_x)), int(nx), int(k),
                     int(k if ldx is None else ldx), C.c_void_p(int(d_y)), int(ny), int(k if ldy is None else ldy))
+
+    # ---- reductions per row / column and in-place scaling (include/dsa.h: dsa_mat_reduce[_dev], dsa_mat_scale[_dev]; HIP library only)
+    RED_KINDS = {"sum": 0, "abssum": 1, "sqsum": 2, "absmax": 3, "count": 4}
+
+    def _require_scale(self):
+        if not self.b.has("mat_reduce"):
+            raise B.DsaArgumentError(B.EARG, "reduce and scale need the HIP product library")
+
+    def _reduce_args(self, kind, per):
+        self._require_scale()
+        if kind not in self.RED_KINDS:
+            raise B.DsaArgumentError(B.EARG, "kind must be one of %s" % ", ".join(sorted(self.RED_KINDS)))
+        if per not in ("row", "column"):
+            raise B.DsaArgumentError(B.EARG, "per must be 'row' or 'column'")
+        return self.RED_KINDS[kind], (ROWMAJOR if per == "row" else COLMAJOR)
+
+    def reduce(self, kind, per, out=None):
+        """One value per row (per="row") or column (per="column") over the STORED cells: kind "sum", "abssum" (sum of |v|), "sqsum"
+        (sum of v * v), "absmax" (max |v|, NaN propagates) or "count" (stored cells, stored zeros included).  Keys without cells give
+        0.0.  Returns a numpy array; with out= a float64 tensor on the GPU of the right length the result is written there (it never
+        leaves HBM) and out is returned."""
+        k, o = self._reduce_args(kind, per)
+        self.sync()                                   # size() after the queued single writes
+        m, n = self.size()
+        cnt = m if o == ROWMAJOR else n
+        if out is None:
+            y = np.empty(max(cnt, 1), dtype=np.float64)
+            self.b.call("mat_reduce", self.h, o, k, y.ctypes.data_as(P_F64), cnt)
+            return y[:cnt]
+        import torch
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda or out.dim() != 1 or \
+                not out.is_contiguous() or out.numel() != cnt:
+            raise B.DsaArgumentError(B.EARG, "out must be a contiguous 1-D float64 tensor on the GPU with one element per %s" % per)
+        # the library works on the orientation's stream (as in matmul): torch's pending work on out first, torch's readers after
+        torch.cuda.current_stream(out.device).synchronize()
+        self.reduce_dev(kind, per, out.data_ptr(), cnt)
+        self.sync()
+        return out
+
+    def reduce_dev(self, kind, per, d_out, n):
+        """reduce with the result in HBM (device address of n doubles); stream-ordered on the orientation's stream (sync())"""
+        k, o = self._reduce_args(kind, per)
+        self.b.call("mat_reduce_dev", self.h, o, k, C.c_void_p(int(d_out)), int(n))
+
+    def _norms(self, p, per):
+        if p == 1:
+            return self.reduce("abssum", per)
+        if p == 2:
+            return np.sqrt(self.reduce("sqsum", per))
+        if p in (np.inf, "inf"):
+            return self.reduce("absmax", per)
+        raise B.DsaArgumentError(B.EARG, "p must be 1, 2 or inf")
+
+    def row_norms(self, p=2):
+        """the p-norm of every row, p in {1, 2, inf} (the 2-norm is sqrt of the "sqsum" reduction, taken here)"""
+        return self._norms(p, "row")
+
+    def col_norms(self, p=2):
+        return self._norms(p, "column")
+
+    def scale(self, alpha=1.0, rows=None, cols=None):
+        """A <- diag(rows) * (alpha * A) * diag(cols) in place: every stored value v becomes ((v * alpha) * rows[i]) * cols[j].
+        Structure is preserved: a zero factor leaves stored zeros (nnz unchanged).  rows / cols: numpy arrays (or sequences), or
+        float64 tensors on the GPU (any stride; made contiguous first) — both of the same kind; None = factor absent."""
+        self._require_scale()
+        ops = [x for x in (rows, cols) if x is not None]
+        is_t = [type(x).__module__.split(".")[0] == "torch" for x in ops]
+        if any(is_t):
+            import torch
+            if not all(is_t):
+                raise B.DsaArgumentError(B.EARG, "rows and cols must both be numpy arrays or both be tensors on the GPU")
+            for x in ops:
+                if x.dtype != torch.float64 or not x.is_cuda or x.dim() != 1:
+                    raise B.DsaArgumentError(B.EARG, "rows and cols must be 1-D float64 tensors on the GPU")
+            r = None if rows is None else rows.contiguous()
+            c = None if cols is None else cols.contiguous()
+            # the library reads the factors on its own two streams: torch's pending work on them must be over first, and they must
+            # stay as they are until the scale has finished
+            torch.cuda.current_stream(ops[0].device).synchronize()
+            self.scale_dev(alpha, 0 if r is None else r.data_ptr(), 0 if r is None else r.numel(),
+                           0 if c is None else c.data_ptr(), 0 if c is None else c.numel())
+            self.sync()
+            return self
+        rr, rp = (None, None) if rows is None else _f64(np.asarray(rows, dtype=np.float64))
+        cc, cp = (None, None) if cols is None else _f64(np.asarray(cols, dtype=np.float64))
+        # a factor of length 0 is still "given": a non-NULL pointer that is never read
+        dummy = np.zeros(1, dtype=np.float64)
+        if rr is not None and len(rr) == 0:
+            rp = dummy.ctypes.data_as(P_F64)
+        if cc is not None and len(cc) == 0:
+            cp = dummy.ctypes.data_as(P_F64)
+        self.b.call("mat_scale", self.h, float(alpha), rp, 0 if rr is None else len(rr), cp, 0 if cc is None else len(cc))
+        return self
+
+    def scale_dev(self, alpha, d_r, nr, d_c, nc):
+        """scale with the factors in HBM (device addresses, 0 = factor absent): they are read on both orientations' streams and
+        must stay valid and unchanged until sync()"""
+        self._require_scale()
+        self.b.call("mat_scale_dev", self.h, float(alpha), C.c_void_p(int(d_r)) if d_r else None, int(nr),
+                    C.c_void_p(int(d_c)) if d_c else None, int(nc))
 
 
 def dynamicsparse(I=None, J=None, V=None, m=None, n=None, fill_mode=True,

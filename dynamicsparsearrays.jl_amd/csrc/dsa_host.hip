@@ -1471,6 +1471,38 @@ int32_t dsa_mat_spmm_dense(dsa_mat_t* h, int32_t transpose, const double* x, int
     API_CATCH
 }
 
+// ---- reductions per row / column and the in-place scaling D_r A D_c (scale.hip).  Reduce is read-only; scale changes values: both
+// SpMV plans are dropped before the first write
+int32_t dsa_mat_reduce_dev(dsa_mat_t* h, int32_t orientation, int32_t kind, double* d_out, int64_t n_out) {
+    API_TRY
+    reduce_dev(h, orientation, kind, d_out, n_out);
+    API_CATCH
+}
+int32_t dsa_mat_reduce(dsa_mat_t* h, int32_t orientation, int32_t kind, double* out, int64_t n_out) {
+    API_TRY
+    reduce_host(h, orientation, kind, out, n_out);
+    API_CATCH
+}
+int32_t dsa_mat_scale_dev(dsa_mat_t* h, double alpha, const double* d_r, int64_t nr, const double* d_c, int64_t nc) {
+    API_TRY
+    scale_prepare(h, d_r, nr, d_c, nc);
+    mat_content_changed(h);
+    scale_apply(h, alpha, d_r, d_c);
+    mat_prefetch_spmv_meta(h);
+    API_CATCH
+}
+int32_t dsa_mat_scale(dsa_mat_t* h, double alpha, const double* r, int64_t nr, const double* c, int64_t nc) {
+    API_TRY
+    ScaleStaging st(h, r, nr, c, nc);
+    scale_prepare(h, st.d_r, nr, st.d_c, nc);
+    mat_content_changed(h);
+    scale_apply(h, alpha, st.d_r, st.d_c);
+    mat_prefetch_spmv_meta(h);
+    HIPCHK(hipStreamSynchronize(h->col.stream));
+    HIPCHK(hipStreamSynchronize(h->row.stream));
+    API_CATCH
+}
+
 int32_t dsa_mat_check(dsa_mat_t* h, int32_t o, int64_t* report) { API_TRY mat_flush(h); pma_check(orient(h, o), report); API_CATCH }
 int32_t dsa_mat_set_stream(dsa_mat_t* h, void* s) {
     API_TRY

@@ -36,6 +36,13 @@ void check_index_format(int32_t index_bits, int32_t index_base) {
     if (index_base != 0 && index_base != 1) fail(DSA_EARG, "index_base must be 0 or 1");
 }
 
+// the error word an export kernel handed over: bit 2 the structure contradicts itself, bit 1 something lies outside size(m)
+void export_verdict(const unsigned long long* word, const char* what, const char* outside) {
+    const unsigned long long err = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    if (err & 2u) fail(DSA_EASSERT, std::string(what) + ": slot array and partition tables disagree");
+    if (err & 1u) fail(DSA_EBOUNDS, outside);
+}
+
 namespace {
 
 // what every export starts with: queued writes applied, not in fill mode, the orientation and its two dimensions
@@ -46,13 +53,6 @@ Side export_side(dsa_mat* h, int32_t o) {
     if (o != DSA_COLMAJOR && o != DSA_ROWMAJOR) fail(DSA_EARG, "orientation must be 0 or 1");
     const bool rows = o == DSA_ROWMAJOR;
     return Side{rows ? h->row : h->col, rows ? h->m : h->n, rows ? h->n : h->m};
-}
-
-// the error word an export kernel handed over: bit 2 the structure contradicts itself, bit 1 something lies outside size(m)
-void export_verdict(const unsigned long long* word, const char* what, const char* outside) {
-    const unsigned long long err = __atomic_load_n(word, __ATOMIC_ACQUIRE);
-    if (err & 2u) fail(DSA_EASSERT, std::string(what) + ": slot array and partition tables disagree");
-    if (err & 1u) fail(DSA_EBOUNDS, outside);
 }
 
 // ---- the whole orientation: CSC from colmajor, CSR from rowmajor

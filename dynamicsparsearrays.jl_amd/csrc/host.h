@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, pma_host.hip, writes_host.hip, build_host.hip,
-// spmv_host.hip, spmm_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
+// spmv_host.hip, spmm_host.hip, scale_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h
 // and export_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -146,6 +146,8 @@ struct Pma {
     unsigned long long* d_meta = nullptr; int64_t* h_meta = nullptr; unsigned long long meta_seq = 0; int64_t meta_inflight_epoch = -1;
     // compressed export (compress.hip): per-tile counts and prefixes; selected export (select.hip): per-key spans, counts and prefixes
     ExportArea cx, sel;
+    // reduce / scale (scale.hip): per-span records, and the pinned {error word, sequence number} of their bounds checks
+    ExportArea sc;
     // thresholds  src/pma.jl:58,70,87
     double t_h = 0.7, t_0 = 0.92, p_h = 0.3, p_0 = 0.08, t_d = 0.0, p_d = 0.0;
 
@@ -277,6 +279,8 @@ void spmm_host(dsa_mat* h, int32_t transpose, const double* x, int64_t nx, int64
 // ---- export_host.hip: the compressed form of an orientation and of selected columns / rows (d_* are device arrays; *nnz_out also
 // with DSA_ECAP), and the check of an index format that the import shares: index_bits 32 | 64, index_base 0 | 1
 void check_index_format(int32_t index_bits, int32_t index_base);
+// the verdict on the error word an export, reduce or scale kernel handed over: DSA_EASSERT (value 2 set), DSA_EBOUNDS with the text `outside` (1)
+void export_verdict(const unsigned long long* word, const char* what, const char* outside);
 void to_compressed_dev(dsa_mat* h, int32_t orientation, int32_t index_bits, int32_t index_base, void* d_ptr, void* d_idx, double* d_vals,
                        int64_t cap, int64_t* nnz_out);
 void to_compressed_host(dsa_mat* h, int32_t orientation, int32_t index_base, int64_t* ptr, int64_t* idx, double* vals, int64_t cap,
@@ -285,6 +289,20 @@ void select_compressed_dev(dsa_mat* h, int32_t orientation, int32_t index_bits, 
                            void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out);
 void select_compressed_host(dsa_mat* h, int32_t orientation, int32_t index_base, const int64_t* sel, int64_t nsel, int64_t* ptr,
                             int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out);
+
+// ---- scale_host.hip: per-partition reductions and the in-place scaling D_r A D_c (d_* are device arrays).  A scale is two steps so
+// that the entry point can bump the content epoch between them: scale_prepare (flush, checks, the bounds pass over both orientations:
+// DSA_EBOUNDS with nothing modified) and scale_apply (the writes, enqueued on both streams).  ScaleStaging holds factors that came
+// from host memory in HBM until both streams have drained.
+void reduce_dev(dsa_mat* h, int32_t orientation, int32_t kind, double* d_out, int64_t n_out);
+void reduce_host(dsa_mat* h, int32_t orientation, int32_t kind, double* out, int64_t n_out);
+void scale_prepare(dsa_mat* h, const double* d_r, int64_t nr, const double* d_c, int64_t nc);
+void scale_apply(dsa_mat* h, double alpha, const double* d_r, const double* d_c);
+struct ScaleStaging {
+    dsa_mat* h; DevStaging b; const double* d_r = nullptr; const double* d_c = nullptr;
+    ScaleStaging(dsa_mat* h, const double* r, int64_t nr, const double* c, int64_t nc);
+    ~ScaleStaging();
+};
 
 // Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks
 // and uploaded asynchronously as a chunk fills (the copy of chunk k overlaps the caller's appends into chunk k+1), so that

@@ -66,6 +66,7 @@ void pma_destroy(Pma& P) {
     pinned_free(P.h_meta);
     P.cx.release();
     P.sel.release();
+    P.sc.release();
     if (P.tmerge.sems2) hipFree(P.tmerge.sems2);
     if (P.tmerge.keys2) hipFree(P.tmerge.keys2);
     if (P.tmerge.pkey) hipFree(P.tmerge.pkey);

@@ -24,7 +24,8 @@ using LinearAlgebra: Transpose
 export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC, dynamicsparsevec, dynamicsparse, nbpartitions,
        deletecolumn!, deleterow!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
-       keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev
+       keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev,
+       scale!, reduce_rows, reduce_cols
 
 const libdsa = get(ENV, "DSA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libdsa_hip.so"))
 
@@ -586,5 +587,32 @@ Base.:(*)(a::DynamicSparseMatrix, X::Transpose{Float64,Matrix{Float64}}) = trans
 Base.:(*)(a::DynamicSparseMatrix, X::Matrix{Float64}) = permutedims(_spmm(a, false, permutedims(X), _size_int(a)[1]))
 Base.:(*)(t::Transposed{<:DynamicSparseMatrix}, X::Transpose{Float64,Matrix{Float64}}) = transpose(_spmm(t.array, true, parent(X), _size_int(t.array)[2]))
 Base.:(*)(t::Transposed{<:DynamicSparseMatrix}, X::Matrix{Float64}) = permutedims(_spmm(t.array, true, permutedims(X), _size_int(t.array)[2]))
+
+# Reductions over the stored cells of every row / column and the in-place scaling A <- Diagonal(rows) * (alpha * A) * Diagonal(cols)
+# (include/dsa.h: dsa_mat_reduce, dsa_mat_scale; no reference counterpart — sum(abs, A; dims), maximum(abs, ...), lmul! / rmul! of a
+# SparseMatrixCSC).  kind: :sum, :abssum, :sqsum, :absmax (NaN propagates like maximum(abs, ...)) or :count (stored cells).
+const RED_KINDS = Dict{Symbol,Int32}(:sum => Int32(0), :abssum => Int32(1), :sqsum => Int32(2), :absmax => Int32(3), :count => Int32(4))
+function _reduce(a::DynamicSparseMatrix, orientation::Int32, kind::Symbol, n::Integer)
+    haskey(RED_KINDS, kind) || throw(ArgumentError("kind must be one of :sum, :abssum, :sqsum, :absmax, :count"))
+    y = Vector{Float64}(undef, n)
+    GC.@preserve y _check(ccall((:dsa_mat_reduce, libdsa), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Int64), a.h, orientation, RED_KINDS[kind], y, length(y)))
+    return y
+end
+reduce_rows(a::DynamicSparseMatrix, kind::Symbol) = _reduce(a, Int32(1), kind, _size_int(a)[1])          # DSA_ROWMAJOR
+reduce_cols(a::DynamicSparseMatrix, kind::Symbol) = _reduce(a, Int32(0), kind, _size_int(a)[2])          # DSA_COLMAJOR
+# Structure is preserved like lmul! / rmul!: a zero factor leaves stored zeros.  rows / cols = nothing: the factor is absent.
+function scale!(a::DynamicSparseMatrix; alpha::Real = 1.0, rows::Union{Nothing,AbstractVector{<:Real}} = nothing,
+                cols::Union{Nothing,AbstractVector{<:Real}} = nothing)
+    r = rows === nothing ? Float64[] : Vector{Float64}(rows)
+    c = cols === nothing ? Float64[] : Vector{Float64}(cols)
+    # an empty factor that IS given still goes in as a non-NULL pointer (never read): NULL means absent
+    one = Float64[1.0]
+    GC.@preserve r c one _check(ccall((:dsa_mat_scale, libdsa), Int32,
+        (Ptr{Cvoid}, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64), a.h, Float64(alpha),
+        rows === nothing ? Ptr{Float64}(C_NULL) : pointer(isempty(r) ? one : r), length(r),
+        cols === nothing ? Ptr{Float64}(C_NULL) : pointer(isempty(c) ? one : c), length(c)))
+    return a
+end
 
 end # module

@@ -300,7 +300,40 @@ int32_t dsa_mat_spmm_dense_dev(dsa_mat_t* h, int32_t transpose, const double* d_
                                double* d_y, int64_t ny, int64_t ldy);
 int32_t dsa_mat_spmm_dense(dsa_mat_t* h, int32_t transpose, const double* x, int64_t nx, int64_t k, int64_t ldx,
                            double* y, int64_t ny, int64_t ldy);
-/* ---- column-range shards.  No reference counterpart: the reference is single-process.  One PROCESS per GPU:
+/* ---- reductions per row / column and in-place diagonal scaling (csrc/scale.hip).  No reference counterpart: what sum(abs, A; dims),
+ * maximum(abs, ...) and SparseArrays' lmul! / rmul! with Diagonal factors do for a SparseMatrixCSC.
+ *
+ * Reduce: orientation DSA_ROWMAJOR gives one value per row (n_out must equal m, the rowmajor orientation is walked), DSA_COLMAJOR one
+ * per column (n_out must equal n, colmajor); (m, n) = dsa_mat_size after the queued single writes have been applied.  out[key - 1] is
+ * the reduction over the STORED cells of row / column `key` (stored zeros count): the sum of v, of |v|, of v * v (a rounded multiply,
+ * then separate adds: no FMA), the maximum of |v|, or the number of cells (as a double).  A key without stored cells gives +0.0; every
+ * sum starts at +0.0.  DSA_RED_ABSMAX propagates NaN (a NaN cell makes its result NaN, like Julia's maximum(abs, ...)).  The order in
+ * which the terms of a row are added is fixed by the slot layout alone: no floating-point atomics, two calls on the same state give
+ * the same bits; it is NOT the left-to-right order of dsa_mat_spmm_dense.  Rows of any length are summed correctly.  Read-only: a
+ * cached SpMV plan survives.
+ * DSA_EMODE in fill mode; DSA_EARG: orientation or kind invalid, n_out != the dimension, out NULL with n_out > 0; DSA_EBOUNDS: a
+ * stored row / column key outside 1..n_out (possible only after dynamicsparse with an explicit m / n smaller than the keys).
+ * _dev: d_out is a device array; enqueued on the stream of the orientation that is walked (dsa_mat_set_stream / dsa_mat_sync); the host
+ * waits only for the bounds word.  The host form stages through pooled device memory and waits. */
+enum { DSA_RED_SUM = 0, DSA_RED_ABSSUM = 1, DSA_RED_SQSUM = 2, DSA_RED_ABSMAX = 3, DSA_RED_COUNT = 4 };
+int32_t dsa_mat_reduce_dev(dsa_mat_t* h, int32_t orientation, int32_t kind, double* d_out, int64_t n_out);
+int32_t dsa_mat_reduce(dsa_mat_t* h, int32_t orientation, int32_t kind, double* out, int64_t n_out);
+/* Scale: every stored cell A[i, j] = v becomes ((v * alpha) * r[i - 1]) * c[j - 1] — D_r * (alpha A) * D_c — three separately rounded
+ * multiplies in that order, in BOTH orientations, so that a cell holds the same bits in colmajor and rowmajor.  r or c NULL (its length
+ * argument is then ignored) means that the factor is absent, which equals a factor of 1.0 exactly; when given, nr must equal m and nc
+ * must equal n (dsa_mat_size after the queued single writes have been applied).
+ * STRUCTURE IS PRESERVED, like lmul! / rmul! on a SparseMatrixCSC: a zero factor leaves a STORED 0.0 — nnz is unchanged, A[i, j] reads
+ * 0.0, the cell is still exported and counted by DSA_RED_COUNT.  Non-finite factors follow IEEE (0 * Inf = NaN is stored).  Only the
+ * values of stored cells are written: no slot moves, keys, tables, counts and the rebalance / extend statistics stay as they are.  The
+ * content changes: cached SpMV plans are dropped.
+ * DSA_EMODE in fill mode; DSA_EARG: nr != m or nc != n for a factor that is given; DSA_EBOUNDS: a stored entry outside size(m), found
+ * by a pass in front of the first write — NEITHER orientation is modified.
+ * _dev: d_r / d_c are device arrays, read on BOTH orientations' streams: they must hold their final contents when the call is made
+ * (synchronise the stream that produced them first) and stay valid and unchanged until dsa_mat_sync.  The host waits for the bounds
+ * pass only.  The host form stages r and c through pooled device memory and waits for both streams. */
+int32_t dsa_mat_scale_dev(dsa_mat_t* h, double alpha, const double* d_r, int64_t nr, const double* d_c, int64_t nc);
+int32_t dsa_mat_scale(dsa_mat_t* h, double alpha, const double* r, int64_t nr, const double* c, int64_t nc);
+/* ---- column-range shards. No reference counterpart: the reference is single-process.  One PROCESS per GPU:
  * each process selects its device (dsa_set_device), builds ITS shard and runs the local SpMV; the single data-path collective —
  * the all-reduce (sum) of the partial y — is dsa_shard_allreduce_dev below (RCCL behind this ABI), or whatever the host layer has
  * (torch.distributed in bench.py / sharding.py).

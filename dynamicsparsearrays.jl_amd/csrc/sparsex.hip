@@ -12,7 +12,7 @@
 // Work is proportional to the matched cells + ny / 64 bitmap words, not to ny doubles (rounds 1-5: two memsets of ny doubles / bytes,
 // a byte -> bitmap pass, three compaction launches and a stream synchronisation per product).
 // The dense-ish branch (many stored entries: gather kernel over the twin orientation) hands its y / pattern vectors to the same count
-// and emit kernels.
+// and emit kernels, after k_spx_repair has summed again the touched rows in which a cell of a column x does not store left a NaN.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -21,22 +21,15 @@
 
 namespace dsa {
 
-// ---- accumulate ---------------------------------------------------------------------------------------------------------------
-// x entries come from HBM or straight from pinned host memory (few entries: no copy command in front of the launch).
-__global__ __launch_bounds__(256) void k_spx_accum(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ, int64_t capacity,
-                                                   const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
-                                                   const uint8_t* __restrict__ col_live, int64_t table_len,
-                                                   const int64_t* __restrict__ xi, const double* __restrict__ xv, int64_t nx,
-                                                   double* __restrict__ acc, unsigned long long* __restrict__ bm, int64_t ny) {
-    const int lane = threadIdx.x & 63;
-    const int64_t e = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (e >= nx) return;
-    const int64_t col = xi[e];
-    const double xval = xv[e];
+// ---- locate: the slot range [from, to] (1-based, inclusive) of the live column with key `col`; false: there is none.  Called by a
+// whole wave with a wave-uniform `col`.
+__device__ __forceinline__ bool spx_locate(int64_t col, int lane, int64_t capacity, const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
+                                           const uint8_t* __restrict__ col_live, int64_t table_len, int64_t& from, int64_t& to) {
     // Direct hit first: a table without holes in front of `col` has the column at index col (ids are positions, keys ascend: a
     // matrix whose columns are 1..n, the usual case).  Everything the hit needs is requested in ONE round: key, liveness, the
     // column's semaphore and the next one.
-    int64_t pos = 0, from = 0, to = 0;
+    int64_t pos = 0;
+    from = 0; to = 0;
     bool have = false;
     if (col >= 1 && col <= table_len) {
         const int64_t ck = col_keys[col - 1];
@@ -73,12 +66,29 @@ __global__ __launch_bounds__(256) void k_spx_accum(KeyArr keys, const double* __
         const uint64_t b = __ballot(viol);
         pos = b ? L + __ffsll((unsigned long long)b) - 1 : H;
         while (pos > 0 && !col_live[pos - 1]) --pos;
-        if (pos == 0 || col_keys[pos - 1] != col) return;            // no such column: x entry skipped (src/operations.jl:76-79)
+        if (pos == 0 || col_keys[pos - 1] != col) return false;      // no such column: x entry skipped (src/operations.jl:76-79)
         from = sems[pos - 1] + 1;
         int64_t nxt = pos + 1;
         while (nxt <= table_len && sems[nxt - 1] == 0) ++nxt;
         to = nxt <= table_len ? sems[nxt - 1] - 1 : capacity;
     }
+    return true;
+}
+
+// ---- accumulate ---------------------------------------------------------------------------------------------------------------
+// x entries come from HBM or straight from pinned host memory (few entries: no copy command in front of the launch).
+__global__ __launch_bounds__(256) void k_spx_accum(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ, int64_t capacity,
+                                                   const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
+                                                   const uint8_t* __restrict__ col_live, int64_t table_len,
+                                                   const int64_t* __restrict__ xi, const double* __restrict__ xv, int64_t nx,
+                                                   double* __restrict__ acc, unsigned long long* __restrict__ bm, int64_t ny) {
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (e >= nx) return;
+    const int64_t col = xi[e];
+    const double xval = xv[e];
+    int64_t from, to;
+    if (!spx_locate(col, lane, capacity, sems, col_keys, col_live, table_len, from, to)) return;
     for (int64_t s = from + lane; s <= to; s += 64) {
         if ((occ[(s - 1) >> 6] >> ((s - 1) & 63)) & 1ull) {
             const int64_t row = keys[s - 1];
@@ -99,6 +109,42 @@ __global__ __launch_bounds__(256) void k_spx_pattern_bits(const double* __restri
     const bool t = r < ny && pattern[r] != 0.0;
     const uint64_t b = __ballot(t);
     if (lane == 0) bm[w] = b;
+}
+
+// ---- repair of a gather product: the value pass multiplied EVERY cell of a row by the densified x, also the cells of columns x does not
+// store (x = 0.0 there), so a stored Inf / NaN of the matrix in such a column left NaN in y where the reference's _mul, which walks the
+// stored entries of x only (src/operations.jl:62-135), never reads the cell.  Every touched row whose y is not finite is summed again
+// over its own partition of the twin, cells of columns x does not store left out (xf = the 0/1 pattern of x).  One wave per 64 rows,
+// lane <-> row; a finite y had no such cell (its product would be NaN) and is what it was.  Non-finite rows are the rare case: the
+// kernel reads pattern and y once and ends.
+__global__ __launch_bounds__(256) void k_spx_repair(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ, int64_t capacity,
+                                                    const int64_t* __restrict__ sems, const int64_t* __restrict__ part_keys,
+                                                    const uint8_t* __restrict__ part_live, int64_t table_len,
+                                                    const double* __restrict__ xd, const double* __restrict__ xf, int64_t nx,
+                                                    const double* __restrict__ pattern, double* __restrict__ y, int64_t ny) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t r = (w << 6) + lane;
+    bool bad = false;
+    if (r < ny && pattern[r] != 0.0) bad = ((uint64_t)__double_as_longlong(y[r]) & 0x7ff0000000000000ull) == 0x7ff0000000000000ull;
+    uint64_t todo = __ballot(bad);
+    while (todo) {                                           // (wave-uniform)
+        const int l = __ffsll((unsigned long long)todo) - 1;
+        todo &= todo - 1;
+        const int64_t row = (w << 6) + l + 1;
+        int64_t from, to;
+        double sum = 0.0;
+        if (spx_locate(row, lane, capacity, sems, part_keys, part_live, table_len, from, to)) {
+            for (int64_t s = from + lane; s <= to; s += 64) {
+                if ((occ[(s - 1) >> 6] >> ((s - 1) & 63)) & 1ull) {
+                    const int64_t c = keys[s - 1];
+                    if (c >= 1 && c <= nx && xf[c - 1] != 0.0) sum += vals[s - 1] * xd[c - 1];
+                }
+            }
+        }
+        sum = wave_reduce_add(sum);
+        if (lane == 0) y[row - 1] = sum;
+    }
 }
 
 // ---- count: tile = 64 bitmap words = 4096 rows; scratch = tile_cnt[ntiles], tile_off[ntiles + 1], ticket ---------------------------
@@ -213,6 +259,15 @@ hipError_t launch_spx_pattern_bits(const double* pattern, int64_t ny, uint64_t* 
     const int64_t nwords = (ny + 63) >> 6;
     if (nwords <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_spx_pattern_bits, dim3((unsigned)((nwords + 3) / 4)), dim3(256), 0, stream, pattern, ny, reinterpret_cast<unsigned long long*>(bm), nwords);
+    return hipGetLastError();
+}
+hipError_t launch_spx_repair(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* part_keys,
+                             const uint8_t* part_live, int64_t table_len, const double* xd, const double* xf, int64_t nx, const double* pattern,
+                             double* y, int64_t ny, hipStream_t stream) {
+    const int64_t nwords = (ny + 63) >> 6;
+    if (nwords <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_spx_repair, dim3((unsigned)((nwords + 3) / 4)), dim3(256), 0, stream, keys, vals, occ, capacity, sems, part_keys, part_live,
+                       table_len, xd, xf, nx, pattern, y, ny);
     return hipGetLastError();
 }
 // count + emit (a single-workgroup count + emit for small products was measured: 30 vs 15 us per product — dropped); scratch = the caller's (tile_cnt, tile_off [ntiles + 1], ticket [2 words, zero between launches])

@@ -265,7 +265,10 @@ int32_t dsa_mat_select_compressed(dsa_mat_t* h, int32_t orientation, int32_t ind
 int32_t dsa_mat_spmv_dense(dsa_mat_t* h, int32_t transpose, const double* x, int64_t nx,
                            double* y, int64_t ny);
 /* sparse x given by its stored entries (xi ascending) ; result = touched rows only, ascending,
- * stored zeros kept: the shape of _mul_output(result, n)  src/operations.jl:11-12 */
+ * stored zeros kept: the shape of _mul_output(result, n)  src/operations.jl:11-12.
+ * Only the columns x stores are visited, as in _mul: a stored Inf / NaN of the matrix makes a row non-finite only through a column
+ * x stores (a stored 0.0 of x included: 0 * Inf = NaN); an absent entry of x contributes nothing.  This holds for every
+ * dsa_mat_spmv_sparse* entry point, however many entries x has. */
 int32_t dsa_mat_spmv_sparse(dsa_mat_t* h, int32_t transpose, const int64_t* xi, const double* xv,
                             int64_t nx, int64_t* yi, double* yv, int64_t cap, int64_t* n_out);
 /* The same product in two steps, so that the caller allocates exactly what the result needs: _begin computes (result left with the

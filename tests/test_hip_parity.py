@@ -802,6 +802,8 @@ def test_sparse_x_product_two_step_and_device_entry_points(dsa, hip, oracle, for
                 ib, vb = b.mul((xi3, xv3), transpose=tr)
                 ia, va = a.mul((xi3, xv3), transpose=tr)           # _begin + _fetch
                 assert np.array_equal(ia, ib), (cnt, tr, len(ia), len(ib))
+                # (atol=1e-13 is not derived from anything: x is unit12, not exactly summable, so the bound stays as it was.  The exact
+                # comparisons — inputs that sum to the same bits in any order — are in tests/test_sparse_x.py.)
                 np.testing.assert_allclose(va, vb, rtol=RTOL, atol=1e-13)
                 d_xi = torch.from_numpy(xi3).to(dev); d_xv = torch.from_numpy(xv3).to(dev)
                 a.mul_dev(d_xi.data_ptr(), d_xv.data_ptr(), len(xi3), d_yi.data_ptr(), d_yv.data_ptr(), d_yi.numel(), d_cnt.data_ptr(), transpose=tr)

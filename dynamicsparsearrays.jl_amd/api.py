@@ -614,6 +614,121 @@ class DynamicSparseMatrix(_Handle):
             return torch.sparse_csr_tensor(ptr, idx, val, size=(nsel, n))
         return torch.sparse_csc_tensor(ptr, idx, val, size=(m, nsel))
 
+    # ---- submatrix export (include/dsa.h: dsa_mat_submatrix_compressed[_dev]; HIP library only) ----------------------------------
+    def _require_submatrix(self):
+        if not self.b.has("mat_submatrix_compressed"):
+            raise B.DsaArgumentError(B.EARG, "the submatrix export needs the HIP product library")
+
+    def submatrix_compressed_dev(self, orientation, d_outer, nouter, d_inner, ninner, d_ptr, d_idx, d_vals, cap, index_bits=64, base=0):
+        """A[inner, outer] as CSC (COLMAJOR: outer = column keys, inner = row keys) / A[outer, inner] as CSR (ROWMAJOR) into device
+        memory: d_outer = nouter int64 outer keys (1-based, any order, repeats allowed), d_inner = ninner DISTINCT int64 inner keys
+        (1-based, any order), d_ptr = nouter + 1 indices, d_idx / d_vals = cap entries (device addresses; 0 for idx / vals with
+        cap = 0: the count-only call).  A delivered cell's index is the position of its key in the inner list + base.  Enqueued on the
+        orientation's stream (sync()).  Returns (total, fits) like select_compressed_dev."""
+        self._require_submatrix()
+        got = C.c_int64()
+        try:
+            self.b.call("mat_submatrix_compressed_dev", self.h, int(orientation), int(index_bits), int(base), C.c_void_p(int(d_outer)),
+                        int(nouter), C.c_void_p(int(d_inner)), int(ninner), C.c_void_p(int(d_ptr)), C.c_void_p(int(d_idx)),
+                        C.c_void_p(int(d_vals)), int(cap), C.byref(got))
+        except B.DsaError as e:
+            if e.code == B.ECAP:
+                return got.value, False
+            raise
+        return got.value, True
+
+    @staticmethod
+    def _submatrix_sides(rows, cols, layout):
+        if layout not in ("csr", "csc"):
+            raise B.DsaArgumentError(B.EARG, "layout must be 'csr' or 'csc'")
+        return (ROWMAJOR, rows, cols) if layout == "csr" else (COLMAJOR, cols, rows)
+
+    def _submatrix(self, rows, cols, layout, base, count_only=False):
+        self._require_submatrix()
+        orientation, outer, inner = self._submatrix_sides(rows, cols, layout)
+        out, op = _i64(outer)
+        inn, ip = _i64(inner)
+        if out.ndim != 1 or inn.ndim != 1:
+            raise B.DsaArgumentError(B.EARG, "the key lists must be one-dimensional")
+        ptr = np.empty(len(out) + 1, dtype=np.int64)
+        got = C.c_int64()
+        idx = val = None
+        for _ in range(2):              # the count-only call, then the one that fits
+            cap = 0 if idx is None else len(idx)
+            try:
+                self.b.call("mat_submatrix_compressed", self.h, int(orientation), int(base), op, len(out), ip, len(inn),
+                            ptr.ctypes.data_as(P_I64), idx.ctypes.data_as(P_I64) if cap else None,
+                            val.ctypes.data_as(P_F64) if cap else None, cap, C.byref(got))
+            except B.DsaError as e:
+                if e.code != B.ECAP or idx is not None:
+                    raise
+                if count_only:
+                    return ptr, None, None
+                idx = np.empty(got.value, dtype=np.int64)
+                val = np.empty(got.value, dtype=np.float64)
+                continue
+            break
+        if idx is None:
+            idx, val = np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
+        return ptr, idx[:got.value], val[:got.value]
+
+    def submatrix(self, rows, cols, layout="csr", base=0):
+        """A[rows, cols] as scipy-style arrays (indptr, indices, data) of a len(rows) x len(cols) matrix: CSR (layout "csr": one slice
+        per entry of `rows`, which may repeat; `cols` distinct) or CSC ("csc": one slice per entry of `cols`; `rows` distinct).  int64
+        indices = position in the other list + `base`; they ascend within a slice iff that list ascends."""
+        return self._submatrix(rows, cols, layout, base)
+
+    def count_submatrix(self, rows, cols, layout="csr"):
+        """entries of A[rows, cols] per row of `rows` (layout "csr") or per column of `cols` ("csc")"""
+        return np.diff(self._submatrix(rows, cols, layout, 0, count_only=True)[0])
+
+    def submatrix_torch(self, layout, rows, cols, index_dtype=None):
+        """A[rows, cols] as torch.sparse_csr_tensor / torch.sparse_csc_tensor of shape (len(rows), len(cols)) on the current device.
+        `rows`, `cols`: lists, numpy arrays, or int64 CUDA tensors (used in place); the arrays never leave HBM.  The inner list (cols
+        for CSR, rows for CSC) must ascend strictly, because torch expects sorted indices within a slice."""
+        import torch
+        self._require_submatrix()
+        if index_dtype is None:
+            index_dtype = torch.int64
+        if layout not in (torch.sparse_csr, torch.sparse_csc):
+            raise B.DsaArgumentError(B.EARG, "layout must be torch.sparse_csr or torch.sparse_csc")
+        if index_dtype not in (torch.int32, torch.int64):
+            raise B.DsaArgumentError(B.EARG, "index_dtype must be torch.int32 or torch.int64")
+        orientation = ROWMAJOR if layout == torch.sparse_csr else COLMAJOR
+        bits = 32 if index_dtype == torch.int32 else 64
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+        def on_device(keys):
+            if isinstance(keys, torch.Tensor):
+                if keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1:
+                    raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 CUDA tensor")
+                return keys.contiguous()
+            return torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)).to(dev)
+
+        d_rows, d_cols = on_device(rows), on_device(cols)
+        outer, inner = (d_rows, d_cols) if orientation == ROWMAJOR else (d_cols, d_rows)
+        nouter, ninner = outer.numel(), inner.numel()
+        if ninner > 1 and not bool((inner[1:] > inner[:-1]).all()):
+            raise B.DsaArgumentError(B.EARG, "the inner key list must ascend strictly (torch expects sorted indices)")
+        ptr = torch.empty(nouter + 1, dtype=index_dtype, device=dev)
+        # the stream discipline of select_torch: the keys and the fresh blocks free of torch's pending work first, torch's consumers
+        # of the result behind the export
+        torch.cuda.current_stream(dev).synchronize()
+        args = (orientation, outer.data_ptr(), nouter, inner.data_ptr(), ninner, ptr.data_ptr())
+        total, fits = self.submatrix_compressed_dev(*args, 0, 0, 0, index_bits=bits)
+        idx = torch.empty(max(total, 1), dtype=index_dtype, device=dev)
+        val = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+        if not fits:
+            torch.cuda.current_stream(dev).synchronize()
+            total, fits = self.submatrix_compressed_dev(*args, idx.data_ptr(), val.data_ptr(), total, index_bits=bits)
+            if not fits:
+                raise B.DsaErrorException(B.ECAP, "the submatrix grew between the count and the emit")
+        self.sync()
+        idx, val = idx[:total], val[:total]
+        if orientation == ROWMAJOR:
+            return torch.sparse_csr_tensor(ptr, idx, val, size=(nouter, ninner))
+        return torch.sparse_csc_tensor(ptr, idx, val, size=(ninner, nouter))
+
     def check(self, orientation):
         """device-side invariant checker (HIP library only): report[2..6] must be 0."""
         r = np.zeros(8, dtype=np.int64)

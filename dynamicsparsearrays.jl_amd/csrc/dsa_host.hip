@@ -1431,6 +1431,22 @@ int32_t dsa_mat_select_compressed(dsa_mat_t* h, int32_t orientation, int32_t ind
     API_CATCH
 }
 
+// ---- submatrix export (submatrix.hip): A[I, J] with both key lists as one CSC / CSR; read-only like the selected export
+int32_t dsa_mat_submatrix_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t index_bits, int32_t index_base,
+                                         const int64_t* d_outer, int64_t nouter, const int64_t* d_inner, int64_t ninner,
+                                         void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out) {
+    API_TRY
+    submatrix_compressed_dev(h, orientation, index_bits, index_base, d_outer, nouter, d_inner, ninner, d_ptr, d_idx, d_vals, cap, nnz_out);
+    API_CATCH
+}
+int32_t dsa_mat_submatrix_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_base,
+                                     const int64_t* outer, int64_t nouter, const int64_t* inner, int64_t ninner,
+                                     int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out) {
+    API_TRY
+    submatrix_compressed_host(h, orientation, index_base, outer, nouter, inner, ninner, ptr, idx, vals, cap, nnz_out);
+    API_CATCH
+}
+
 int32_t dsa_mat_spmv_dense_dev(dsa_mat_t* h, int32_t transpose, int32_t algo, const double* d_x, int64_t nx, double* d_y, int64_t ny) {
     API_TRY
     mat_flush(h);

@@ -1,8 +1,10 @@
-// csrc/export_dev.h — what the two export kernel units share (compress.hip: the whole orientation, select.hip: the partitions of
-// a key list): the tile both cut the slot array into, the block scan between their count and emit launches, and the end of an emit
-// kernel.  Device code only.
+// csrc/export_dev.h — what the export kernel units share (compress.hip: the whole orientation, select.hip: the partitions of
+// a key list, submatrix.hip: those partitions restricted to an inner key list): the tile they cut the slot array into, the block
+// scan between their count and emit launches, the span of an outer key (select.hip, submatrix.hip) and the end of an emit kernel.
+// Device code only.
 #pragma once
 #include "wave_dev.h"
+#include "find_dev.h"
 
 namespace dsa {
 
@@ -50,6 +52,44 @@ __device__ __forceinline__ void block_excl_scan2(const T* a, const T* b, int64_t
         __syncthreads();
     }
     tot_a = carry_o; tot_b = carry_s;
+}
+
+// occupied slots of [from, to) (0-based, from < to): the lanes stride over the words, first and last word masked
+__device__ __forceinline__ int64_t sel_span_popc(const uint64_t* __restrict__ occ, int64_t from, int64_t to, int lane) {
+    int64_t c = 0;
+    const int64_t w1 = (to - 1) >> 6;
+    for (int64_t w = (from >> 6) + lane; w <= w1; w += 64) c += popc64(occ[w] & word_range_mask(w, from, to - 1));
+    return wave_reduce_add(c);
+}
+
+// The span of the live partition whose key is `key` (one wave, the same answer in every lane): its cells are the occupied slots of
+// [lo, hi), 0-based, strictly between its semaphore and the next live semaphore (tombstoned table entries behind the partition are
+// skipped 64 at a time; the end of the slot array behind the last one).  lo = hi = 0 for a key without a live partition.
+// err: 1 the key lies outside 1..dim_out, 2 tables out of step with the slots.
+struct KeySpan { int64_t lo, hi; uint32_t err; };
+__device__ __forceinline__ KeySpan key_span(int64_t capacity, const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
+                                            const uint8_t* __restrict__ col_live, int64_t table_len, bool dense, int64_t key,
+                                            int64_t dim_out, int lane) {
+    KeySpan r{0, 0, 0u};
+    if (key < 1 || key > dim_out) {
+        r.err = 1u;
+    } else {
+        const DFoundKey f = d_find_table_fast(col_keys, col_live, table_len, key, dense);
+        if (f.has && f.key == key) {
+            const int64_t sp = sems[f.pos - 1];                  // 1-based slot of the semaphore = 0-based slot of the first cell
+            int64_t nx = 0;                                      // the next live semaphore (tombstones have none)
+            for (int64_t e0 = f.pos; e0 < table_len; e0 += 64) {
+                const int64_t e = e0 + lane;
+                const int64_t v = e < table_len ? sems[e] : 0;
+                const uint64_t m = __ballot(v != 0);
+                if (m) { nx = (int64_t)readlane64((uint64_t)v, __ffsll((unsigned long long)m) - 1); break; }
+            }
+            const int64_t end = nx ? nx - 1 : capacity;
+            if (sp < 1 || sp > capacity || end < sp || end > capacity) r.err = 2u;      // tables out of step with the slots
+            else { r.lo = sp; r.hi = end; }
+        }
+    }
+    return r;
 }
 
 // The end of an emit kernel (256 threads, every one arrives): the error bits of the workgroup go into the scratch word, and the

@@ -1,10 +1,12 @@
-// csrc/export_host.hip — host side of the two compressed exports: the whole orientation (dsa_mat_to_compressed[_dev], kernels in
-// compress.hip) and the partitions of a key list (dsa_mat_select_compressed[_dev], kernels in select.hip).  Argument checks, the
+// csrc/export_host.hip — host side of the compressed exports: the whole orientation (dsa_mat_to_compressed[_dev], kernels in
+// compress.hip), the partitions of a key list (dsa_mat_select_compressed[_dev], kernels in select.hip) and those partitions
+// restricted to an inner key list (dsa_mat_submatrix_compressed[_dev], kernels in submatrix.hip).  Argument checks, the
 // scratch and pinned words of an orientation (ExportArea), the hand-overs and the staging of the host forms.  Host-only unit.
 // Read-only: no epoch moves (a cached SpMV plan survives), nothing about an export stays on the handle between two calls.
 #include "host.h"
 #include "compress.h"
 #include "select.h"
+#include "submatrix.h"
 
 #include <algorithm>
 #include <climits>
@@ -119,6 +121,70 @@ void select_emit(const Side& e, const SelTotals& t, int32_t index_bits, int32_t 
     export_verdict(A.pin + 4, "selected export", "a stored entry of a selected partition lies outside size(m)");
 }
 
+// ---- the partitions of an outer key list, restricted to and renumbered by an inner key list
+struct SubTotals { int64_t total = 0, items = 0; };
+
+// the error word a submatrix kernel handed over (submatrix.h lists the bits)
+void submatrix_verdict(const unsigned long long* word) {
+    const unsigned long long err = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+    if (err & 2u) fail(DSA_EASSERT, "submatrix export: slot array and partition tables disagree");
+    if (err & 1u) fail(DSA_EBOUNDS, "an outer key lies outside size(m)");
+    if (err & 4u) fail(DSA_EBOUNDS, "an inner key lies outside size(m)");
+    if (err & 8u) fail(DSA_EARG, "an inner key is listed twice");
+    if (err & 16u) fail(DSA_EBOUNDS, "a stored entry of a selected partition lies outside size(m)");
+}
+
+// argument checks, the key phase, the first wait (work items), the count phase, the second wait (kept cells).  ptr is complete
+// when this returns; *nnz_out = cells kept.
+SubTotals submatrix_count(const Side& e, int32_t index_bits, int32_t index_base, const int64_t* d_outer, int64_t nouter,
+                          const int64_t* d_inner, int64_t ninner, void* d_ptr, int64_t* nnz_out) {
+    Pma& P = e.P;
+    if (!nnz_out) fail(DSA_EARG, "nnz_out is NULL");
+    check_index_format(index_bits, index_base);
+    if (nouter < 0 || nouter > INT32_MAX) fail(DSA_EARG, "nouter must lie in 0 .. 2^31 - 1");
+    if (ninner < 0 || ninner > INT32_MAX) fail(DSA_EARG, "ninner must lie in 0 .. 2^31 - 1");
+    if (!d_ptr || (nouter > 0 && !d_outer) || (ninner > 0 && !d_inner)) fail(DSA_EARG, "a key list or ptr is NULL");
+    *nnz_out = 0;
+    ExportArea& A = P.sub;
+    ExportArea& I = P.subi;
+    // pinned {error word, work items, sequence number} of the key phase, {error word, kept cells, sequence number} of the count and
+    // {error word, sequence number} of the emit
+    A.ensure(P.stream, submatrix_key_scratch_bytes(nouter, ninner), 8);
+    unsigned long long seq = A.next();
+    const Ctl& c = *P.h_ctl;
+    LAUNCH("submatrix export (keys)", launch_submatrix_keys(P.O(), c.capacity, P.sems, P.col_keys, P.col_live, c.table_len,
+                                                            c.nb_partitions == c.table_len, d_outer, nouter, e.dim_out, d_inner, ninner,
+                                                            e.dim_in, A.scratch, A.pin, seq, P.stream));
+    wait_handover(P, A.pin + 2, seq, "submatrix export (keys)");
+    submatrix_verdict(A.pin);
+    SubTotals t;
+    t.items = (int64_t)A.pin[1];
+    I.ensure(P.stream, submatrix_item_scratch_bytes(t.items), 1);
+    seq = A.next();
+    LAUNCH("submatrix export (count)", launch_submatrix_count(P.K(), P.O(), c.capacity, nouter, ninner, t.items, e.dim_in, index_bits,
+                                                              index_base, d_ptr, A.scratch, I.scratch, A.pin + 3, seq, P.stream));
+    wait_handover(P, A.pin + 5, seq, "submatrix export (count)");
+    submatrix_verdict(A.pin + 3);
+    t.total = (int64_t)A.pin[4];
+    *nnz_out = t.total;
+    if (index_bits == 32 && t.total + index_base > INT32_MAX) fail(DSA_EARG, "the kept cells do not fit 32-bit indices");
+    return t;
+}
+
+// the emit on the scratch submatrix_count left, and the third wait
+void submatrix_emit(const Side& e, const SubTotals& t, int32_t index_bits, int32_t index_base, int64_t nouter, int64_t ninner, void* d_idx,
+                    double* d_vals) {
+    if (t.total <= 0) return;
+    if (t.items <= 0) fail(DSA_EASSERT, "submatrix export: cells without a work item");
+    Pma& P = e.P;
+    ExportArea& A = P.sub;
+    const unsigned long long seq = A.next();
+    LAUNCH("submatrix export (emit)", launch_submatrix_emit(P.K(), P.V(), P.O(), P.capacity(), nouter, ninner, t.items, t.total, index_bits,
+                                                            index_base, d_idx, d_vals, A.scratch, P.subi.scratch, A.pin + 6, seq, P.stream));
+    wait_handover(P, A.pin + 7, seq, "submatrix export (emit)");
+    submatrix_verdict(A.pin + 6);
+}
+
 }  // namespace
 
 void to_compressed_dev(dsa_mat* h, int32_t o, int32_t index_bits, int32_t index_base, void* d_ptr, void* d_idx, double* d_vals,
@@ -184,6 +250,52 @@ void select_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, const int
         HIPCHK(pool_alloc(&b.p[2], cb));
         HIPCHK(pool_alloc(&b.p[3], cb));
         select_emit(e, t, 64, index_base, nsel, b.p[2], static_cast<double*>(b.p[3]));
+        HIPCHK(hipMemcpyAsync(idx, b.p[2], cb, hipMemcpyDeviceToHost, S.stream));
+        HIPCHK(hipMemcpyAsync(vals, b.p[3], cb, hipMemcpyDeviceToHost, S.stream));
+    }
+    HIPCHK(hipStreamSynchronize(S.stream));
+}
+
+void submatrix_compressed_dev(dsa_mat* h, int32_t o, int32_t index_bits, int32_t index_base, const int64_t* d_outer, int64_t nouter,
+                              const int64_t* d_inner, int64_t ninner, void* d_ptr, void* d_idx, double* d_vals, int64_t cap,
+                              int64_t* nnz_out) {
+    if (cap < 0) fail(DSA_EARG, "negative capacity");
+    if (cap > 0 && (!d_idx || !d_vals)) fail(DSA_EARG, "output pointer is NULL");
+    const Side e = export_side(h, o);
+    const SubTotals t = submatrix_count(e, index_bits, index_base, d_outer, nouter, d_inner, ninner, d_ptr, nnz_out);
+    if (cap < t.total) fail(DSA_ECAP, "output buffers too small");
+    submatrix_emit(e, t, index_bits, index_base, nouter, ninner, d_idx, d_vals);
+}
+
+void submatrix_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, const int64_t* outer, int64_t nouter, const int64_t* inner,
+                               int64_t ninner, int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out) {
+    if (cap < 0) fail(DSA_EARG, "negative capacity");
+    if (!ptr || !nnz_out || (nouter > 0 && !outer) || (ninner > 0 && !inner)) fail(DSA_EARG, "a key list, ptr or nnz_out is NULL");
+    if (cap > 0 && (!idx || !vals)) fail(DSA_EARG, "output pointer is NULL");
+    if (nouter < 0 || nouter > INT32_MAX) fail(DSA_EARG, "nouter must lie in 0 .. 2^31 - 1");
+    if (ninner < 0 || ninner > INT32_MAX) fail(DSA_EARG, "ninner must lie in 0 .. 2^31 - 1");
+    const Side e = export_side(h, o);
+    Pma& S = e.P;
+    DevStaging b(S.stream);
+    // block 0: the outer keys, then the inner keys
+    const size_t kb = (size_t)std::max<int64_t>(nouter + ninner, 1) * sizeof(int64_t), pb = (size_t)(nouter + 1) * sizeof(int64_t);
+    HIPCHK(pool_alloc(&b.p[0], kb));
+    HIPCHK(pool_alloc(&b.p[1], pb));
+    int64_t* d_outer = static_cast<int64_t*>(b.p[0]);
+    int64_t* d_inner = d_outer + nouter;
+    if (nouter > 0) HIPCHK(hipMemcpyAsync(d_outer, outer, (size_t)nouter * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
+    if (ninner > 0) HIPCHK(hipMemcpyAsync(d_inner, inner, (size_t)ninner * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
+    const SubTotals t = submatrix_count(e, 64, index_base, d_outer, nouter, d_inner, ninner, b.p[1], nnz_out);
+    HIPCHK(hipMemcpyAsync(ptr, b.p[1], pb, hipMemcpyDeviceToHost, S.stream));
+    if (cap < t.total) {
+        HIPCHK(hipStreamSynchronize(S.stream));      // ptr is the caller's to read with DSA_ECAP
+        fail(DSA_ECAP, "output buffers too small");
+    }
+    if (t.total > 0) {
+        const size_t cb = (size_t)t.total * sizeof(int64_t);
+        HIPCHK(pool_alloc(&b.p[2], cb));
+        HIPCHK(pool_alloc(&b.p[3], cb));
+        submatrix_emit(e, t, 64, index_base, nouter, ninner, b.p[2], static_cast<double*>(b.p[3]));
         HIPCHK(hipMemcpyAsync(idx, b.p[2], cb, hipMemcpyDeviceToHost, S.stream));
         HIPCHK(hipMemcpyAsync(vals, b.p[3], cb, hipMemcpyDeviceToHost, S.stream));
     }

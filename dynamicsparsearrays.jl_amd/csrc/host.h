@@ -146,6 +146,8 @@ struct Pma {
     unsigned long long* d_meta = nullptr; int64_t* h_meta = nullptr; unsigned long long meta_seq = 0; int64_t meta_inflight_epoch = -1;
     // compressed export (compress.hip): per-tile counts and prefixes; selected export (select.hip): per-key spans, counts and prefixes
     ExportArea cx, sel;
+    // submatrix export (submatrix.hip): the key block (hash table of the inner list, spans of the outer list) and the item block
+    ExportArea sub, subi;
     // reduce / scale (scale.hip): per-span records, and the pinned {error word, sequence number} of their bounds checks
     ExportArea sc;
     // thresholds  src/pma.jl:58,70,87
@@ -276,7 +278,7 @@ void spmm_dev(dsa_mat* h, int32_t transpose, const double* d_x, int64_t nx, int6
               hipStream_t s);
 void spmm_host(dsa_mat* h, int32_t transpose, const double* x, int64_t nx, int64_t k, int64_t ldx, double* y, int64_t ny, int64_t ldy);
 
-// ---- export_host.hip: the compressed form of an orientation and of selected columns / rows (d_* are device arrays; *nnz_out also
+// ---- export_host.hip: the compressed form of an orientation, of selected columns / rows and of a submatrix (d_* are device arrays; *nnz_out also
 // with DSA_ECAP), and the check of an index format that the import shares: index_bits 32 | 64, index_base 0 | 1
 void check_index_format(int32_t index_bits, int32_t index_base);
 // the verdict on the error word an export, reduce or scale kernel handed over: DSA_EASSERT (value 2 set), DSA_EBOUNDS with the text `outside` (1)
@@ -289,6 +291,14 @@ void select_compressed_dev(dsa_mat* h, int32_t orientation, int32_t index_bits, 
                            void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out);
 void select_compressed_host(dsa_mat* h, int32_t orientation, int32_t index_base, const int64_t* sel, int64_t nsel, int64_t* ptr,
                             int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out);
+
+// A[I, J] (submatrix.hip): the partitions of the outer keys restricted to and renumbered by the inner keys
+void submatrix_compressed_dev(dsa_mat* h, int32_t orientation, int32_t index_bits, int32_t index_base, const int64_t* d_outer,
+                              int64_t nouter, const int64_t* d_inner, int64_t ninner, void* d_ptr, void* d_idx, double* d_vals,
+                              int64_t cap, int64_t* nnz_out);
+void submatrix_compressed_host(dsa_mat* h, int32_t orientation, int32_t index_base, const int64_t* outer, int64_t nouter,
+                               const int64_t* inner, int64_t ninner, int64_t* ptr, int64_t* idx, double* vals, int64_t cap,
+                               int64_t* nnz_out);
 
 // ---- scale_host.hip: per-partition reductions and the in-place scaling D_r A D_c (d_* are device arrays).  A scale is two steps so
 // that the entry point can bump the content epoch between them: scale_prepare (flush, checks, the bounds pass over both orientations:

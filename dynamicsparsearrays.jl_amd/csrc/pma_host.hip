@@ -66,6 +66,8 @@ void pma_destroy(Pma& P) {
     pinned_free(P.h_meta);
     P.cx.release();
     P.sel.release();
+    P.sub.release();
+    P.subi.release();
     P.sc.release();
     if (P.tmerge.sems2) hipFree(P.tmerge.sems2);
     if (P.tmerge.keys2) hipFree(P.tmerge.keys2);
@@ -380,7 +382,8 @@ void pma_info(Pma& P, int64_t nb_partitions_or_len, int64_t* info) {
                                (P.has_sems ? c.table_cap * 8 : 0) + (P.has_cols ? c.table_cap * 9 : 0) + 2 * P.tmerge_cap * 8 +
                                (P.d_ops ? P.ops_cap * (int64_t)sizeof(Op) + (P.ops_cap / 64 + 8) * 8 : 0) + (P.d_opsrc ? P.opsrc_cap * 24 : 0) +      // op array, run-break bitmap, batch columns
                                P.plan.bytes +     // the SpMV plan: 12 B per stored cell + offsets
-                               (int64_t)P.sel.bytes;      // scratch of the selected export: 32 B per key of the longest selection so far
+                               (int64_t)P.sel.bytes +     // scratch of the selected export: 32 B per key of the longest selection so far
+                               (int64_t)(P.sub.bytes + P.subi.bytes);      // ... of the submatrix export: hash table, spans, work items
 }
 
 void export_slots(Pma& P, int64_t* keys, double* vals, uint8_t* occ, int64_t cap) {

@@ -15,15 +15,15 @@
 //                ranks; keys and values loaded and idx / vals stored non-temporally; the last workgroup hands the error word to
 //                pinned memory
 // No wave owns a whole long partition: a span is cut at the tile boundaries of the slot array, whatever its length.  No atomics on
-// the output, no floating-point arithmetic (values are copied bit for bit).  The count phase relies on popcounts only, so there is NO
-// inner-index selection or renumbering (A[I, J] with both lists): every cell of a selected partition is delivered.
+// the output, no floating-point arithmetic (values are copied bit for bit).  The count phase relies on popcounts only, so every cell
+// of a selected partition is delivered; inner-index selection and renumbering (A[I, J] with both lists) is the submatrix export
+// (submatrix.hip, dsa_mat_submatrix_compressed[_dev]), which shares the span lookup of k_sel_count (export_dev.h: key_span).
 // Bytes in: 8 * nsel selection keys, about 8 * log2(table_len) probed table bytes per key, (kb + 8) per slot of the selected spans,
 // their bitmap words twice (count and emit; the emit reads the words in front of a chunk once more to place it: for a span of c
 // chunks c / 2 times its bitmap, 1/64 of the slot bytes per pass).  Bytes out: (ib + 8) * total + ib * (nsel + 1).  Nothing is
 // proportional to the capacity.
 #include "select.h"
 #include "export_dev.h"
-#include "find_dev.h"
 #include <type_traits>
 
 namespace dsa {
@@ -50,14 +50,6 @@ static SelScratch sel_carve(void* base, int64_t nsel) {
 }
 size_t select_scratch_bytes(int64_t nsel) { return (size_t)(nsel > 0 ? nsel : 0) * 32 + 8; }
 
-// occupied slots of [from, to) (0-based, from < to): the lanes stride over the words, first and last word masked
-__device__ __forceinline__ int64_t sel_span_popc(const uint64_t* __restrict__ occ, int64_t from, int64_t to, int lane) {
-    int64_t c = 0;
-    const int64_t w1 = (to - 1) >> 6;
-    for (int64_t w = (from >> 6) + lane; w <= w1; w += 64) c += popc64(occ[w] & word_range_mask(w, from, to - 1));
-    return wave_reduce_add(c);
-}
-
 // one wave per selected key
 __global__ __launch_bounds__(256) void k_sel_count(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
                                                    const int64_t* __restrict__ col_keys, const uint8_t* __restrict__ col_live,
@@ -66,27 +58,9 @@ __global__ __launch_bounds__(256) void k_sel_count(const uint64_t* __restrict__ 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t j = (int64_t)blockIdx.x * 4 + wv;
     if (j >= nsel) return;
-    const int64_t key = sel[j];
-    int64_t lo = 0, hi = 0;
-    uint32_t err = 0;
-    if (key < 1 || key > dim_out) {
-        err = 1u;
-    } else {
-        const DFoundKey f = d_find_table_fast(col_keys, col_live, table_len, key, dense);
-        if (f.has && f.key == key) {
-            const int64_t sp = sems[f.pos - 1];                  // 1-based slot of the semaphore = 0-based slot of the first cell
-            int64_t nx = 0;                                      // the next live semaphore (tombstones have none)
-            for (int64_t e0 = f.pos; e0 < table_len; e0 += 64) {
-                const int64_t e = e0 + lane;
-                const int64_t v = e < table_len ? sems[e] : 0;
-                const uint64_t m = __ballot(v != 0);
-                if (m) { nx = (int64_t)readlane64((uint64_t)v, __ffsll((unsigned long long)m) - 1); break; }
-            }
-            const int64_t end = nx ? nx - 1 : capacity;
-            if (sp < 1 || sp > capacity || end < sp || end > capacity) err = 2u;      // tables out of step with the slots
-            else { lo = sp; hi = end; }
-        }
-    }
+    const KeySpan sp = key_span(capacity, sems, col_keys, col_live, table_len, dense, sel[j], dim_out, lane);
+    const int64_t lo = sp.lo, hi = sp.hi;
+    const uint32_t err = sp.err;
     const int64_t cnt = hi > lo ? sel_span_popc(occ, lo, hi, lane) : 0;
     if (lane != 0) return;
     s.lo[j] = lo; s.hi[j] = hi;

@@ -433,6 +433,37 @@ function Base.getindex(a::DynamicSparseMatrix{K,L}, rows::AbstractVector{<:Integ
     rowptr, colval, nzval = _select_int(a, Int32(1), rows)
     return SparseMatrixCSC(transpose(SparseMatrixCSC(_size_int(a)[2], length(rows), rowptr, colval, nzval)))
 end
+# A[rows, cols] with both key lists (dsa_mat_submatrix_compressed, colmajor, 1-based): the columns `cols` (any order, repeats allowed)
+# restricted to the rows `rows` (any order, all distinct: a repeated row key is an ArgumentError) and renumbered on the device, entry
+# (i, j) of the result = A[rows[i], cols[j]].  Count-only call first, like _select_int.  The device delivers a column in ascending
+# ORIGINAL row key; SparseMatrixCSC wants ascending positions, so the columns are sorted here unless `rows` ascends.
+function Base.getindex(a::DynamicSparseMatrix{K,L}, rows::AbstractVector{<:Integer}, cols::AbstractVector{<:Integer}) where {K,L}
+    (K <: Integer && L <: Integer) || throw(ArgumentError("a key-list selection needs integer row and column keys, got $(K), $(L)"))
+    outer = Vector{Int64}(cols); inner = Vector{Int64}(rows)
+    ptr = Vector{Int64}(undef, length(outer) + 1); idx = Int64[]; val = Float64[]
+    got = Ref{Int64}(0)
+    for _ in 1:2
+        cap = length(idx)
+        rc = GC.@preserve outer inner ptr idx val ccall((:dsa_mat_submatrix_compressed, libdsa), Int32,
+            (Ptr{Cvoid}, Int32, Int32, Ptr{Int64}, Int64, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ref{Int64}),
+            a.h, Int32(0), Int32(1), outer, length(outer), inner, length(inner), ptr, cap == 0 ? Ptr{Int64}(C_NULL) : pointer(idx),
+            cap == 0 ? Ptr{Float64}(C_NULL) : pointer(val), cap, got)
+        if rc == 8 && cap == 0                      # DSA_ECAP
+            resize!(idx, got[]); resize!(val, got[])
+            continue
+        end
+        _check(rc)
+        break
+    end
+    if !issorted(inner; lt = <=)
+        for j in 1:length(outer)
+            r = ptr[j]:(ptr[j + 1] - 1)
+            p = sortperm(view(idx, r))
+            idx[r] = idx[r][p]; val[r] = val[r][p]
+        end
+    end
+    return SparseMatrixCSC(length(inner), length(outer), ptr, idx, val)
+end
 "n getindex calls in one ccall"
 function getindex_batch(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector)
     Ii = _in(a.rows, I); Ji = _in(a.cols, J); out = Vector{Float64}(undef, length(Ii))

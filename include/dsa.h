@@ -238,7 +238,8 @@ int32_t dsa_mat_to_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_b
  * idx = key - 1 + base, values copied bit for bit (stored zeros as stored).  A key inside 1..dim_out without a live partition (never
  * written, deleted, or empty) gives an empty slice.  With repeats the result may hold more cells than nnz(m); nsel = 0 gives
  * ptr = [base].  dim_out = n (colmajor) | m (rowmajor), dim_in the other one, (m, n) = dsa_mat_size at the call.
- * There is no inner-index selection or renumbering (A[I, J] with both lists): every cell of a selected partition is delivered.
+ * Every cell of a selected partition is delivered; inner-index selection and renumbering (A[I, J] with both lists) is
+ * dsa_mat_submatrix_compressed[_dev] below.
  * _dev: every array is a device address; enqueued on the orientation's stream (dsa_mat_set_stream / dsa_mat_sync).  The host waits
  * twice: for the total, which only the device knows, and behind the emit for the bounds word.  The number of launches and waits does
  * not depend on nsel.  *nnz_out = the number of selected cells on return, also with DSA_ECAP.
@@ -258,6 +259,38 @@ int32_t dsa_mat_select_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t
 int32_t dsa_mat_select_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_base,
                                   const int64_t* sel, int64_t nsel,
                                   int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out);
+
+/* The submatrix A[I, J] in compressed form, both sides selected and renumbered on the device.  orientation DSA_COLMAJOR: outer =
+ * column keys, inner = row keys, the result is A[inner, outer] as CSC of shape (ninner, nouter); DSA_ROWMAJOR: outer = row keys,
+ * inner = column keys, the result is A[outer, inner] as CSR of shape (nouter, ninner).  The OUTER list behaves exactly as sel of
+ * dsa_mat_select_compressed: nouter keys, 1-based, in any order, repeats allowed, a key inside 1..dim_out without a live partition
+ * gives an empty slice, nouter = 0 gives ptr = [base].  The INNER list holds ninner keys, 1-based, in any order, all DISTINCT.  A
+ * cell of a selected partition is delivered iff its inner key is in the inner list; its idx is the 0-based position of that key in
+ * the inner list + base.  ptr has nouter + 1 entries, ptr[j] = base + delivered cells of the slices in front of j.  Within a slice
+ * the cells come out in slot order, i.e. by ascending ORIGINAL inner key: idx ascends within every slice iff the inner list
+ * ascends (a permuted inner list gives a valid but unsorted CSC / CSR).  Values are copied bit for bit, stored zeros as stored.
+ * ninner = 0 gives an all-empty result with a valid ptr.  The result is bit-identical from call to call.
+ * _dev: every array is a device address; enqueued on the orientation's stream (dsa_mat_set_stream / dsa_mat_sync).  Six kernel
+ * launches and three host waits (work items of the selected spans, the total, the error word behind the emit), whatever nouter,
+ * ninner and the lengths of the partitions are; pooled scratch of O(nouter + ninner + selected slots / 2048) bytes: nothing is
+ * proportional to the capacity or to dim_in.  *nnz_out = the number of delivered cells on return, also with DSA_ECAP.
+ * Capacity: as for dsa_mat_select_compressed_dev.  cap < total returns DSA_ECAP with *nnz_out = total, ptr COMPLETE AND VALID, idx /
+ * vals untouched; cap = 0 with d_idx = d_vals = NULL is the count-only call (DSA_OK when the total is 0).  Nothing about a selection
+ * stays on the handle.
+ * Errors: DSA_EMODE in fill mode.  DSA_EARG: orientation, index_bits (32 | 64) or index_base (0 | 1) invalid; nouter or ninner
+ * outside 0 .. 2^31 - 1; ptr NULL, a key list NULL with a length > 0, idx or vals NULL with cap > 0; an inner key listed twice
+ * (found on the device); with index_bits 32, ninner > INT32_MAX or total + base > INT32_MAX (dim_in need NOT fit: only positions
+ * are written).  DSA_EBOUNDS: an outer key outside 1..dim_out, an inner key outside 1..dim_in, or a cell of a SELECTED partition
+ * whose stored inner key lies outside 1..dim_in, whether it is listed or not (found by the count: also reported by the count-only
+ * call).  DSA_EASSERT: partition tables and slot array out of step.  Read-only: slots, tables and both epochs stay as they are, a
+ * cached SpMV plan survives. */
+int32_t dsa_mat_submatrix_compressed_dev(dsa_mat_t* h, int32_t orientation, int32_t index_bits, int32_t index_base,
+                                         const int64_t* d_outer, int64_t nouter, const int64_t* d_inner, int64_t ninner,
+                                         void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out);
+/* the same with host arrays and int64 indices, staged through pooled device memory (DSA_ECAP leaves ptr filled) */
+int32_t dsa_mat_submatrix_compressed(dsa_mat_t* h, int32_t orientation, int32_t index_base,
+                                     const int64_t* outer, int64_t nouter, const int64_t* inner, int64_t ninner,
+                                     int64_t* ptr, int64_t* idx, double* vals, int64_t cap, int64_t* nnz_out);
 
 /* ---- SpMV:  mat * v, transpose(mat) * v   src/operations.jl:14-60 -> _mul :107-135 ---- */
 /* dense x (every index of x is a stored entry), dense y of length ny; rows never touched are 0.

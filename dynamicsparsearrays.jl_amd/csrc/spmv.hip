@@ -802,7 +802,7 @@ hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_
 }
 
 // The product.  One wave per group, 4 independent waves per workgroup, all groups resident (<= 4096 groups, 32 KB of LDS per
-// workgroup).  Per slice the wave streams its cells 256 at a time (non-temporal: read once), gathers x, and adds each product to its
+// workgroup).  Per slice the wave streams its cells 256 at a time (plain loads, see load_round), gathers x, and adds each product to its
 // row's LDS accumulator.  A row's cells in a chunk of 64 lie on consecutive lanes; they are added one rank after the other, so every
 // row is 0.0 + its products in ascending column order — what k_spmv_gather computes for a row that one lane sums.  The first round of
 // slice s + 1 is requested behind the gathers of slice s.  At the end every row of the group is stored once, and the rows without a
@@ -825,12 +825,14 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spmv_plan(PlanDev pl, const int64_
     const double* __restrict__ vp = pl.val;
     __builtin_amdgcn_wave_barrier();
 
+    // Plain loads, not non-temporal ones: a (group, slice) starts at any cell, so neighbouring rounds share their border lines, and
+    // the one or two 0.5 MB slices the gathers read stay in L2 beside the stream (config 3, same box: 69.3 us against 84.5 us)
     auto load_round = [&](uint32_t b, uint32_t e, uint32_t (&c)[PLAN_U], double (&v)[PLAN_U]) {
 #pragma unroll
         for (int u = 0; u < PLAN_U; ++u) {
             const uint32_t i = b + u * 64 + lane;
             c[u] = PLAN_NONE; v[u] = 0.0;
-            if (i < e) { c[u] = __builtin_nontemporal_load(cp + i); v[u] = __builtin_nontemporal_load(vp + i); }
+            if (i < e) { c[u] = cp[i]; v[u] = vp[i]; }
         }
     };
     auto gather = [&](uint32_t base, const uint32_t (&c)[PLAN_U], double (&xq)[PLAN_U]) {      // (idle lanes read x[0])

@@ -302,6 +302,10 @@ class Transposed:
     def __matmul__(self, X):
         return self.array.matmul(X, transpose=True)
 
+    def matmul_selected(self, keys, X):
+        """rows `keys` of transpose(mat) * X: mat[:, keys]' * X"""
+        return self.array.matmul_selected(keys, X, transpose=True)
+
     def reduce(self, kind, per, out=None):
         """the reduction per row / column of the transpose: per column / row of the matrix"""
         if per not in ("row", "column"):
@@ -849,6 +853,69 @@ class DynamicSparseMatrix(_Handle):
         self._require_spmm()
         self.b.call("mat_spmm_dense_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_x)), int(nx), int(k),
                     int(k if ldx is None else ldx), C.c_void_p(int(d_y)), int(ny), int(k if ldy is None else ldy))
+
+    # ---- selected-key product (include/dsa.h: dsa_mat_spmm_selected[_dev]; HIP library only) -------------------------------------
+    def _require_selprod(self):
+        if not self.b.has("mat_spmm_selected"):
+            raise B.DsaArgumentError(B.EARG, "the selected-key product needs the HIP product library")
+
+    def matmul_selected(self, keys, X, transpose=False):
+        """mat[keys, :] * X / mat[:, keys]' * X (transpose=True): row j of the result is row keys[j] - 1 of matmul(X), bit for bit, at a
+        cost that follows the selected rows / columns only.  Keys are 1-based, in any order, repeats allowed; a key that owns no row /
+        column gives a zero row.
+
+        A float64 numpy X takes a list or array of keys and returns a new (len(keys), k) array.  A float64 torch tensor on the GPU
+        takes a list, an array, or an int64 CUDA tensor (used in place) and returns a new tensor on the same device (nothing leaves
+        HBM).  A 1-D X returns the 1-D product.  Inputs that are not row-contiguous are handled as in matmul."""
+        self._require_selprod()
+        tr = 1 if transpose else 0
+        if isinstance(X, np.ndarray):
+            sel, sp = _i64(keys)
+            if sel.ndim != 1:
+                raise B.DsaArgumentError(B.EARG, "the selection must be one-dimensional")
+            one_d = X.ndim == 1
+            xx = np.ascontiguousarray(X.reshape(-1, 1) if one_d else X, dtype=np.float64)
+            if xx.ndim != 2:
+                raise B.DsaArgumentError(B.EARG, "X must have one or two dimensions")
+            nx, k = xx.shape
+            y = np.empty((len(sel), k), dtype=np.float64)
+            self.b.call("mat_spmm_selected", self.h, tr, sp, len(sel), xx.ctypes.data_as(P_F64), nx, k, k, y.ctypes.data_as(P_F64), k)
+            return y[:, 0] if one_d else y
+        import torch
+        if not isinstance(X, torch.Tensor):
+            raise B.DsaArgumentError(B.EARG, "X must be a numpy array or a torch tensor")
+        if X.dtype != torch.float64 or not X.is_cuda or X.dim() not in (1, 2):
+            raise B.DsaArgumentError(B.EARG, "X must be a 1-D or 2-D float64 tensor on the GPU")
+        if isinstance(keys, torch.Tensor):
+            if keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1:
+                raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 CUDA tensor")
+            sel = keys.contiguous()
+        else:
+            sel = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)).to(X.device)
+        nsel = sel.numel()
+        one_d = X.dim() == 1
+        xx = X.unsqueeze(1) if one_d else X
+        nx, k = xx.shape
+        if k < 1:
+            raise B.DsaArgumentError(B.EARG, "X has no columns")
+        if xx.stride(1) != 1 or (nx > 1 and xx.stride(0) < k):
+            xx = xx.contiguous()
+        ldx = xx.stride(0) if nx > 1 else k
+        y = torch.empty((nsel, k), dtype=torch.float64, device=X.device)
+        # the stream discipline of matmul and select_torch: torch's pending work on the keys, X and the fresh block is over before the
+        # library starts on the orientation's stream, and torch's consumers of the result start after the product has finished
+        torch.cuda.current_stream(X.device).synchronize()
+        self.matmul_selected_dev(sel.data_ptr(), nsel, xx.data_ptr(), nx, k, y.data_ptr(), ldx=ldx, ldy=k, transpose=transpose)
+        self.sync()
+        return y[:, 0] if one_d else y
+
+    def matmul_selected_dev(self, d_sel, nsel, d_x, nx, k, d_y, ldx=None, ldy=None, transpose=False):
+        """the selected-key product with keys (nsel int64) and both operands in HBM (device addresses, e.g. tensor.data_ptr()), X and
+        Y row-major with leading dimensions ldx / ldy (default k); stream-ordered on the orientation's stream, no host wait (sync()).
+        A key without a row / column (0 and negative keys included) gives a zero row: nothing is reported."""
+        self._require_selprod()
+        self.b.call("mat_spmm_selected_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_sel)), int(nsel), C.c_void_p(int(d_x)),
+                    int(nx), int(k), int(k if ldx is None else ldx), C.c_void_p(int(d_y)), int(k if ldy is None else ldy))
 
     # ---- reductions per row / column and in-place scaling (include/dsa.h: dsa_mat_reduce[_dev], dsa_mat_scale[_dev]; HIP library only)
     RED_KINDS = {"sum": 0, "abssum": 1, "sqsum": 2, "absmax": 3, "count": 4}

@@ -5,7 +5,7 @@
 // Everything that works on ONE packed-memory array (the Pma of host.h) is in the engine units pma_host.hip (lifecycle, geometry,
 // rebalances, reads), writes_host.hip (yield loop around the sequencer, batch-parallel rounds), build_host.hip (K-build) and
 // spmv_host.hip (SpMV meta and plan); the exports, the multi-vector product and the device import sit behind three-line entry points
-// in export_host.hip, spmm_host.hip and ingest_host.hip; the sparse-x product and the parity hooks have entry points of their own in
+// in export_host.hip, spmm_host.hip, selprod_host.hip and ingest_host.hip; the sparse-x product and the parity hooks have entry points of their own in
 // sparsex_host.hip and raw_host.hip.
 //
 // Everything that touches slots runs on the GPU (rebalance.hip, sequencer.hip, spmv.hip).  The host
@@ -1484,6 +1484,22 @@ int32_t dsa_mat_spmm_dense(dsa_mat_t* h, int32_t transpose, const double* x, int
                            double* y, int64_t ny, int64_t ldy) {
     API_TRY
     spmm_host(h, transpose, x, nx, k, ldx, y, ny, ldy);
+    API_CATCH
+}
+
+int32_t dsa_mat_spmm_selected_dev(dsa_mat_t* h, int32_t transpose, const int64_t* d_sel, int64_t nsel, const double* d_x, int64_t nx,
+                                  int64_t k, int64_t ldx, double* d_y, int64_t ldy) {
+    API_TRY
+    mat_flush(h);
+    Pma& P = transpose ? h->col : h->row;
+    selprod_dev(h, transpose, d_sel, nsel, d_x, nx, k, ldx, d_y, ldy, P.stream);
+    API_CATCH
+}
+
+int32_t dsa_mat_spmm_selected(dsa_mat_t* h, int32_t transpose, const int64_t* sel, int64_t nsel, const double* x, int64_t nx,
+                              int64_t k, int64_t ldx, double* y, int64_t ldy) {
+    API_TRY
+    selprod_host(h, transpose, sel, nsel, x, nx, k, ldx, y, ldy);
     API_CATCH
 }
 

@@ -1,9 +1,9 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, pma_host.hip, writes_host.hip, build_host.hip,
-// spmv_host.hip, spmm_host.hip, scale_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
-// (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h
-// and export_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
+// spmv_host.hip, spmm_host.hip, selprod_host.hip, scale_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
+// (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
+// export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
 #pragma once
 #include "../../include/dsa.h"
@@ -277,6 +277,12 @@ dsa_mat* mat_from_compressed_dev(int32_t orientation, int32_t index_bits, int32_
 void spmm_dev(dsa_mat* h, int32_t transpose, const double* d_x, int64_t nx, int64_t k, int64_t ldx, double* d_y, int64_t ny, int64_t ldy,
               hipStream_t s);
 void spmm_host(dsa_mat* h, int32_t transpose, const double* x, int64_t nx, int64_t k, int64_t ldx, double* y, int64_t ny, int64_t ldy);
+
+// ---- selprod_host.hip: the product of the partitions of a key list with a dense block (selprod_host: keys, X and Y in host memory)
+void selprod_dev(dsa_mat* h, int32_t transpose, const int64_t* d_sel, int64_t nsel, const double* d_x, int64_t nx, int64_t k, int64_t ldx,
+                 double* d_y, int64_t ldy, hipStream_t s);
+void selprod_host(dsa_mat* h, int32_t transpose, const int64_t* sel, int64_t nsel, const double* x, int64_t nx, int64_t k, int64_t ldx,
+                  double* y, int64_t ldy);
 
 // ---- export_host.hip: the compressed form of an orientation, of selected columns / rows and of a submatrix (d_* are device arrays; *nnz_out also
 // with DSA_ECAP), and the check of an index format that the import shares: index_bits 32 | 64, index_base 0 | 1

@@ -5,7 +5,8 @@
 // all of it used (the single product fetches a line to use 8 bytes of it once x outgrows an XCD's L2), and the slot stream is read
 // once for up to 16 columns instead of once per column.  Nothing of the column-swept plan is used.
 //
-// One wave per span of 512 slots (8 occupancy words), four independent waves per workgroup, no workgroup barrier:
+// One wave per span of 512 slots (8 occupancy words), four independent waves per workgroup, no workgroup barrier (load / compact and
+// walk are mm_load_compact and mm_walk of spmm_dev.h, shared with selprod.hip):
 //   load     occupancy words, keys (physical width) and values of the span and of the word behind it, lane <-> slot, coalesced, all
 //            requested before anything waits;
 //   compact  the occupied slots go to the wave's LDS slice in slot order (ballot / popcount): 0-based X row (-1: key outside 1..nx)
@@ -28,103 +29,9 @@
 //   LDS 31 744 / 40 960 B per workgroup (per wave 576 x 8 B values + 576 x 4 | 8 B rows + 512 x 2 B semaphore list): 5 / 3 workgroups
 //   = 20 / 12 waves per CU, which is the limiter; 62 VGPRs, 80 SGPRs, no scratch in every instantiation.
 #include "spmm.h"
-#include "wave_dev.h"
-#include <type_traits>
+#include "spmm_dev.h"
 
 namespace dsa {
-
-constexpr int MM_BLOCK = 256;
-constexpr int MM_WAVES = MM_BLOCK / 64;
-constexpr int MM_OWN_WORDS = 8;                          // words of a span
-constexpr int MM_LOAD_WORDS = MM_OWN_WORDS + 1;          // ... and the word behind it
-constexpr int MM_TILE = MM_WAVES * MM_OWN_WORDS * 64;    // slots per workgroup
-constexpr int MM_CELLS = MM_LOAD_WORDS * 64;
-constexpr int MM_U = 8;                                  // X loads a lane keeps in flight
-
-template <typename key_t>
-struct MmWave {
-    double v[MM_CELLS];                  // value of a cell / partition id of a semaphore
-    key_t c[MM_CELLS];                   // 0-based row of X, -1: contributes nothing (semaphore, key outside 1..nx)
-    uint16_t sem[MM_OWN_WORDS * 64];     // compacted positions of the span's semaphores
-};
-
-// Loads words [w0, w0 + 9) of the slot array (clamped to the array) and compacts their occupied slots into S.  Semaphores of the
-// first OWN words are listed in S.sem (nsem of them); behind those words the first semaphore ends the compaction (closed = true:
-// the open row ends there).  Returns the number of compacted slots.  Executed by one full wave.
-template <bool WIDE, bool NT, int OWN>
-__device__ __forceinline__ int mm_load_compact(const typename std::conditional<WIDE, int64_t, int32_t>::type* __restrict__ kp,
-                                               const double* __restrict__ vals, const uint64_t* __restrict__ occ, int64_t nwords,
-                                               int64_t w0, int64_t nx, MmWave<typename std::conditional<WIDE, int64_t, int32_t>::type>& S,
-                                               int lane, int& nsem, bool& closed) {
-    typedef typename std::conditional<WIDE, int64_t, int32_t>::type key_t;
-    uint64_t ow[MM_LOAD_WORDS];
-    key_t k[MM_LOAD_WORDS];
-    double v[MM_LOAD_WORDS];
-#pragma unroll
-    for (int j = 0; j < MM_LOAD_WORDS; ++j) ow[j] = occ[w0 + j < nwords ? w0 + j : nwords - 1];
-#pragma unroll
-    for (int j = 0; j < MM_LOAD_WORDS; ++j) {
-        const int64_t w = w0 + j < nwords ? w0 + j : nwords - 1;
-        k[j] = NT ? __builtin_nontemporal_load(kp + (w << 6) + lane) : kp[(w << 6) + lane];
-    }
-#pragma unroll
-    for (int j = 0; j < MM_LOAD_WORDS; ++j) {
-        const int64_t w = w0 + j < nwords ? w0 + j : nwords - 1;
-        v[j] = NT ? __builtin_nontemporal_load(vals + (w << 6) + lane) : vals[(w << 6) + lane];
-    }
-    const uint64_t unx = (uint64_t)(nx > 0 ? nx : 0);
-    const uint32_t nx32 = unx < 0x7fffffffull ? (uint32_t)unx : 0x7fffffffu;
-    int n = 0;
-    nsem = 0;
-    closed = false;
-#pragma unroll
-    for (int j = 0; j < MM_LOAD_WORDS; ++j) {
-        uint64_t o = (closed || w0 + j >= nwords) ? 0ull : readfirstlane64(ow[j]);
-        const bool issem = ((o >> lane) & 1ull) && k[j] == (key_t)SEM_KEY;
-        const uint64_t sb = __ballot(issem);
-        if (j >= OWN && sb != 0ull) {                    // the open row ends in front of this semaphore
-            o &= (sb & (0ull - sb)) - 1ull;
-            closed = true;
-        }
-        if ((o >> lane) & 1ull) {
-            const int pos = n + popc64(o & mask_lt(lane));
-            const bool ok = WIDE ? (uint64_t)((int64_t)k[j] - 1) < unx : (uint32_t)k[j] - 1u < nx32;      // 1 <= key <= nx
-            S.c[pos] = ok ? (key_t)(k[j] - 1) : (key_t)-1;
-            S.v[pos] = v[j];
-            if (j < OWN && issem) S.sem[nsem + popc64(sb & mask_lt(lane))] = (uint16_t)pos;
-        }
-        if (j < OWN) nsem += popc64(sb);
-        n += popc64(o);
-    }
-    return n;
-}
-
-// sum + the terms of the compacted cells [t0, t1) for this lane's column, in order; MM_U loads of X requested per round
-template <typename key_t>
-__device__ __forceinline__ double mm_walk(double sum, int t0, int t1, const MmWave<key_t>& S, const double* __restrict__ xcol, int64_t ldx,
-                                          bool colok) {
-    for (int t = t0; t < t1; t += MM_U) {
-        double xv[MM_U], vv[MM_U];
-#pragma unroll
-        for (int u = 0; u < MM_U; ++u) {
-            const bool in = t + u < t1;
-            const int tc = in ? t + u : t0;
-            const key_t c = S.c[tc];
-            const bool ok = in && colok && c >= 0;
-            vv[u] = ok ? S.v[tc] : 0.0;
-            // straight-line: a lane with nothing to add reads X[0, 0] (nx > 0: it exists) and drops it
-            const double xl = xcol[ok ? (int64_t)c * ldx : 0];
-            xv[u] = ok ? xl : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < MM_U; ++u) {
-            // a cell that contributes nothing adds +0.0 * +0.0: a sum that started at +0.0 is never -0.0, so it keeps its bits
-            const double p = vv[u] * xv[u];
-            sum = sum + p;
-        }
-    }
-    return sum;
-}
 
 // x, y: first column of the block (the host adds the block's offset); kc <= KB columns of it exist
 template <bool WIDE, bool NT, int KB>

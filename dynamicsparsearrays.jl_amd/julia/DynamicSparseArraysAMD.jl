@@ -25,7 +25,7 @@ export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC
        deletecolumn!, deleterow!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
        keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev,
-       scale!, reduce_rows, reduce_cols
+       scale!, reduce_rows, reduce_cols, mul_rows, mul_cols
 
 const libdsa = get(ENV, "DSA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libdsa_hip.so"))
 
@@ -618,6 +618,26 @@ Base.:(*)(a::DynamicSparseMatrix, X::Transpose{Float64,Matrix{Float64}}) = trans
 Base.:(*)(a::DynamicSparseMatrix, X::Matrix{Float64}) = permutedims(_spmm(a, false, permutedims(X), _size_int(a)[1]))
 Base.:(*)(t::Transposed{<:DynamicSparseMatrix}, X::Transpose{Float64,Matrix{Float64}}) = transpose(_spmm(t.array, true, parent(X), _size_int(t.array)[2]))
 Base.:(*)(t::Transposed{<:DynamicSparseMatrix}, X::Matrix{Float64}) = permutedims(_spmm(t.array, true, permutedims(X), _size_int(t.array)[2]))
+
+# mul_rows(A, rows, X) = A[rows, :] * X and mul_cols(A, cols, X) = transpose(A[:, cols]) * X for a list of keys (include/dsa.h:
+# dsa_mat_spmm_selected, 1-based; no reference counterpart): any order, repeats allowed, a key without entries gives a zero row, a
+# key < 1 is an ArgumentError.  Row j is bit-identical to row keys[j] of A * X / transpose(A) * X, at a cost that follows the selected
+# rows / columns only.  Integer keys only, like _select_int.  X goes in as in _spmm: xt is the k x nx Julia matrix.
+function _spmm_selected(a::DynamicSparseMatrix{K,L}, tr::Bool, keys::AbstractVector{<:Integer}, xt::Matrix{Float64}) where {K,L}
+    (K <: Integer && L <: Integer) || throw(ArgumentError("a key-list product needs integer row and column keys, got $(K), $(L)"))
+    sel = Vector{Int64}(keys)
+    k, nx = size(xt)
+    yt = Matrix{Float64}(undef, k, length(sel))
+    GC.@preserve sel xt yt _check(ccall((:dsa_mat_spmm_selected, libdsa), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Int64, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64),
+        a.h, tr ? 1 : 0, sel, length(sel), xt, nx, k, k, yt, k))
+    return yt
+end
+_mul_selected(a, tr, keys, X::Transpose{Float64,Matrix{Float64}}) = transpose(_spmm_selected(a, tr, keys, parent(X)))
+_mul_selected(a, tr, keys, X::Matrix{Float64}) = permutedims(_spmm_selected(a, tr, keys, permutedims(X)))
+_mul_selected(a, tr, keys, x::Vector{Float64}) = vec(_spmm_selected(a, tr, keys, reshape(x, 1, length(x))))
+mul_rows(a::DynamicSparseMatrix, rows::AbstractVector{<:Integer}, X) = _mul_selected(a, false, rows, X)
+mul_cols(a::DynamicSparseMatrix, cols::AbstractVector{<:Integer}, X) = _mul_selected(a, true, cols, X)
 
 # Reductions over the stored cells of every row / column and the in-place scaling A <- Diagonal(rows) * (alpha * A) * Diagonal(cols)
 # (include/dsa.h: dsa_mat_reduce, dsa_mat_scale; no reference counterpart — sum(abs, A; dims), maximum(abs, ...), lmul! / rmul! of a

@@ -336,6 +336,24 @@ int32_t dsa_mat_spmm_dense_dev(dsa_mat_t* h, int32_t transpose, const double* d_
                                double* d_y, int64_t ny, int64_t ldy);
 int32_t dsa_mat_spmm_dense(dsa_mat_t* h, int32_t transpose, const double* x, int64_t nx, int64_t k, int64_t ldx,
                            double* y, int64_t ny, int64_t ldy);
+/* The same product for a LIST of outer keys only (csrc/selprod.hip): row j of Y (nsel x k, leading dimension ldy) is the product of
+ * the live partition whose key is sel[j] with X (nx x k, ldx).  transpose = 0: row keys, the rowmajor orientation, Y = A[sel, :] X;
+ * transpose = 1: column keys, colmajor, Y = A[:, sel]' X.  Keys are 1-based, in any order, and may repeat: every occurrence gets its
+ * own row.  A row is summed exactly as by dsa_mat_spmm_dense (slot order, from +0.0, one multiply then one add per term, no FMA, any
+ * length, no atomics): for a key with a live partition Y[j] is bit-identical to row sel[j] - 1 of the full product, and two calls
+ * give the same bits.  A key without a live partition (never written, deleted, beyond size(m)) gives a row of +0.0; a cell whose
+ * inner key is outside 1..nx contributes nothing.  Every row of Y is stored exactly once, columns k..ldy-1 are not written.  The
+ * cost follows the selected spans, not the capacity; k > 16 reads them once per 16 columns.
+ * _dev: every array is a device address; stream-ordered on the stream of the orientation that is walked (dsa_mat_set_stream /
+ * dsa_mat_sync): NO host wait and no hand-over, so a bad key cannot be reported: a key < 1 gives the zero row like any other key
+ * without a partition.  The host form sees the keys and rejects one < 1 with DSA_EARG before any launch; it stages through pooled
+ * device memory and waits.  Arguments are checked before anything is enqueued (Y is untouched on an error): DSA_EMODE in fill mode;
+ * DSA_EARG: k < 1, ldx < k, ldy < k, nsel outside 0 .. 2^31 - 1, nx < 0, sel or y NULL with nsel > 0, x NULL with nx > 0.
+ * nsel = 0 launches nothing; nx = 0 writes nsel rows of +0.0.  Read-only: a cached SpMV plan survives. */
+int32_t dsa_mat_spmm_selected_dev(dsa_mat_t* h, int32_t transpose, const int64_t* d_sel, int64_t nsel,
+                                  const double* d_x, int64_t nx, int64_t k, int64_t ldx, double* d_y, int64_t ldy);
+int32_t dsa_mat_spmm_selected(dsa_mat_t* h, int32_t transpose, const int64_t* sel, int64_t nsel,
+                              const double* x, int64_t nx, int64_t k, int64_t ldx, double* y, int64_t ldy);
 /* ---- reductions per row / column and in-place diagonal scaling (csrc/scale.hip).  No reference counterpart: what sum(abs, A; dims),
  * maximum(abs, ...) and SparseArrays' lmul! / rmul! with Diagonal factors do for a SparseMatrixCSC.
  *

@@ -306,6 +306,10 @@ class Transposed:
         """rows `keys` of transpose(mat) * X: mat[:, keys]' * X"""
         return self.array.matmul_selected(keys, X, transpose=True)
 
+    def matmul_sparse(self, S):
+        """transpose(mat) * S for a sparse S (CSC triple or torch.sparse_csc tensor): see DynamicSparseMatrix.matmul_sparse"""
+        return self.array.matmul_sparse(S, transpose=True)
+
     def reduce(self, kind, per, out=None):
         """the reduction per row / column of the transpose: per column / row of the matrix"""
         if per not in ("row", "column"):
@@ -916,6 +920,97 @@ class DynamicSparseMatrix(_Handle):
         self._require_selprod()
         self.b.call("mat_spmm_selected_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_sel)), int(nsel), C.c_void_p(int(d_x)),
                     int(nx), int(k), int(k if ldx is None else ldx), C.c_void_p(int(d_y)), int(k if ldy is None else ldy))
+
+    # ---- batched sparse-x product (include/dsa.h: dsa_mat_spgemm_csc[_dev]; HIP library only) ---------------------------------------
+    def _require_spgemm(self):
+        if not self.b.has("mat_spgemm_csc"):
+            raise B.DsaArgumentError(B.EARG, "the batched sparse-x product needs the HIP product library")
+
+    def matmul_sparse_dev(self, d_xptr, d_xidx, d_xval, k, nnzx, d_yptr, d_yidx, d_yval, cap, index_bits=64, base=0, transpose=False):
+        """mat * S / transpose(mat) * S for k sparse columns, S and the result CSC in device memory (device addresses, e.g.
+        tensor.data_ptr()): d_xptr = k + 1 indices, d_xidx / d_xval = nnzx entries (indices ascending strictly within a column),
+        d_yptr = k + 1 indices, d_yidx / d_yval = cap entries (0 for both with cap = 0: the count-only call).  Column j of the result
+        is mul() of column j of S, bit for bit.  Enqueued on the stream of the orientation that is walked (sync()).  Returns
+        (total, fits) like select_compressed_dev: with fits False (cap < total) only yptr has been written."""
+        self._require_spgemm()
+        got = C.c_int64()
+        try:
+            self.b.call("mat_spgemm_csc_dev", self.h, 1 if transpose else 0, int(index_bits), int(base), C.c_void_p(int(d_xptr)),
+                        C.c_void_p(int(d_xidx)), C.c_void_p(int(d_xval)), int(k), int(nnzx), C.c_void_p(int(d_yptr)),
+                        C.c_void_p(int(d_yidx)), C.c_void_p(int(d_yval)), int(cap), C.byref(got))
+        except B.DsaError as e:
+            if e.code == B.ECAP:
+                return got.value, False
+            raise
+        return got.value, True
+
+    def matmul_sparse(self, S, transpose=False, base=0):
+        """mat * S / transpose(mat) * S for a sparse S with k columns: column j of the result is mul() of column j of S (the touched
+        rows only, ascending, stored zeros kept), bit for bit and the same on every call.
+
+        S = (indptr, indices, data), scipy-style CSC counted from `base` (0 or 1), indices ascending strictly within a column: returns
+        the same triple with int64 indices.  A float64 torch.sparse_csc tensor on the GPU with int32 or int64 indices returns a
+        torch.sparse_csc_tensor of shape (size(mat, 1 | 2), k) with the same index dtype; nothing leaves HBM."""
+        self._require_spgemm()
+        tr = 1 if transpose else 0
+        m, n = self.size()
+        ny = n if transpose else m
+        if isinstance(S, (tuple, list)):
+            if len(S) != 3:
+                raise B.DsaArgumentError(B.EARG, "S must be (indptr, indices, data)")
+            xptr, xpp = _i64(S[0])
+            xidx, xip = _i64(S[1])
+            xval, xvp = _f64(S[2])
+            if xptr.ndim != 1 or len(xptr) < 1 or xidx.ndim != 1 or xval.ndim != 1 or len(xidx) != len(xval):
+                raise B.DsaArgumentError(B.EARG, "S must be (indptr[k + 1], indices[nnz], data[nnz])")
+            k = len(xptr) - 1
+            if int(xptr[k]) - int(base) != len(xidx):
+                raise B.DsaArgumentError(B.EARG, "indptr[k] - base must be the number of stored entries")
+            yptr = np.empty(k + 1, dtype=np.int64)
+            got = C.c_int64()
+            yidx = yval = None
+            for _ in range(2):              # the count-only call, then the one that fits
+                cap = 0 if yidx is None else len(yidx)
+                try:
+                    self.b.call("mat_spgemm_csc", self.h, tr, int(base), xpp, xip, xvp, k, yptr.ctypes.data_as(P_I64),
+                                yidx.ctypes.data_as(P_I64) if cap else None, yval.ctypes.data_as(P_F64) if cap else None, cap,
+                                C.byref(got))
+                except B.DsaError as e:
+                    if e.code != B.ECAP or yidx is not None:
+                        raise
+                    yidx = np.empty(got.value, dtype=np.int64)
+                    yval = np.empty(got.value, dtype=np.float64)
+                    continue
+                break
+            if yidx is None:
+                yidx, yval = np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
+            return yptr, yidx[:got.value], yval[:got.value]
+        import torch
+        if not isinstance(S, torch.Tensor) or S.layout != torch.sparse_csc:
+            raise B.DsaArgumentError(B.EARG, "S must be a CSC triple or a torch.sparse_csc tensor")
+        if S.dtype != torch.float64 or not S.is_cuda or S.dim() != 2:
+            raise B.DsaArgumentError(B.EARG, "S must be a 2-D float64 sparse_csc tensor on the GPU")
+        xptr, xidx, xval = S.ccol_indices().contiguous(), S.row_indices().contiguous(), S.values().contiguous()
+        if xptr.dtype != xidx.dtype or xptr.dtype not in (torch.int32, torch.int64):
+            raise B.DsaArgumentError(B.EARG, "the indices of S must be int32 or int64")
+        bits = 32 if xptr.dtype == torch.int32 else 64
+        k, nnzx = S.shape[1], xidx.numel()
+        dev = S.device
+        yptr = torch.empty(k + 1, dtype=xptr.dtype, device=dev)
+        # the stream discipline of select_torch: S and the fresh blocks free of torch's pending work first, torch's consumers of the
+        # result behind the product
+        torch.cuda.current_stream(dev).synchronize()
+        args = (xptr.data_ptr(), xidx.data_ptr(), xval.data_ptr(), k, nnzx, yptr.data_ptr())
+        total, fits = self.matmul_sparse_dev(*args, 0, 0, 0, index_bits=bits, transpose=transpose)
+        yidx = torch.empty(max(total, 1), dtype=xptr.dtype, device=dev)
+        yval = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+        if not fits:
+            torch.cuda.current_stream(dev).synchronize()
+            total, fits = self.matmul_sparse_dev(*args, yidx.data_ptr(), yval.data_ptr(), total, index_bits=bits, transpose=transpose)
+            if not fits:
+                raise B.DsaErrorException(B.ECAP, "the product grew between the count and the emit")
+        self.sync()
+        return torch.sparse_csc_tensor(yptr, yidx[:total], yval[:total], size=(ny, k))
 
     # ---- reductions per row / column and in-place scaling (include/dsa.h: dsa_mat_reduce[_dev], dsa_mat_scale[_dev]; HIP library only)
     RED_KINDS = {"sum": 0, "abssum": 1, "sqsum": 2, "absmax": 3, "count": 4}

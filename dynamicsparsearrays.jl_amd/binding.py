@@ -164,6 +164,8 @@ _PRODUCT_ONLY_SIGS = {
     "mat_spmm_dense": [VP, I32, P_F64, I64, I64, I64, P_F64, I64, I64],
     "mat_spmm_selected_dev": [VP, I32, VP, I64, VP, I64, I64, I64, VP, I64],
     "mat_spmm_selected": [VP, I32, P_I64, I64, P_F64, I64, I64, I64, P_F64, I64],
+    "mat_spgemm_csc_dev": [VP, I32, I32, I32, VP, VP, VP, I64, I64, VP, VP, VP, I64, P_I64],
+    "mat_spgemm_csc": [VP, I32, I32, P_I64, P_I64, P_F64, I64, P_I64, P_I64, P_F64, I64, P_I64],
     "mat_reduce_dev": [VP, I32, I32, VP, I64],
     "mat_reduce": [VP, I32, I32, P_F64, I64],
     "mat_scale_dev": [VP, F64, VP, I64, VP, I64],

@@ -1503,6 +1503,22 @@ int32_t dsa_mat_spmm_selected(dsa_mat_t* h, int32_t transpose, const int64_t* se
     API_CATCH
 }
 
+// ---- batched sparse-x product (spgemm.hip): Y = A S / A' S, operands and result CSC; read-only like the exports
+int32_t dsa_mat_spgemm_csc_dev(dsa_mat_t* h, int32_t transpose, int32_t index_bits, int32_t index_base,
+                               const void* d_xptr, const void* d_xidx, const double* d_xval, int64_t k, int64_t nnzx,
+                               void* d_yptr, void* d_yidx, double* d_yval, int64_t cap, int64_t* nnz_out) {
+    API_TRY
+    spgemm_csc_dev(h, transpose, index_bits, index_base, d_xptr, d_xidx, d_xval, k, nnzx, d_yptr, d_yidx, d_yval, cap, nnz_out);
+    API_CATCH
+}
+int32_t dsa_mat_spgemm_csc(dsa_mat_t* h, int32_t transpose, int32_t index_base,
+                           const int64_t* xptr, const int64_t* xidx, const double* xval, int64_t k,
+                           int64_t* yptr, int64_t* yidx, double* yval, int64_t cap, int64_t* nnz_out) {
+    API_TRY
+    spgemm_csc_host(h, transpose, index_base, xptr, xidx, xval, k, yptr, yidx, yval, cap, nnz_out);
+    API_CATCH
+}
+
 // ---- reductions per row / column and the in-place scaling D_r A D_c (scale.hip).  Reduce is read-only; scale changes values: both
 // SpMV plans are dropped before the first write
 int32_t dsa_mat_reduce_dev(dsa_mat_t* h, int32_t orientation, int32_t kind, double* d_out, int64_t n_out) {

@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, pma_host.hip, writes_host.hip, build_host.hip,
-// spmv_host.hip, spmm_host.hip, selprod_host.hip, scale_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
+// spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -150,6 +150,9 @@ struct Pma {
     ExportArea sub, subi;
     // reduce / scale (scale.hip): per-span records, and the pinned {error word, sequence number} of their bounds checks
     ExportArea sc;
+    // batched sparse-x product (spgemm.hip): per-entry spans and per-column counts, and the slabs of the long columns (all zero
+    // between two calls)
+    ExportArea spg, spgs;
     // thresholds  src/pma.jl:58,70,87
     double t_h = 0.7, t_0 = 0.92, p_h = 0.3, p_0 = 0.08, t_d = 0.0, p_d = 0.0;
 
@@ -283,6 +286,12 @@ void selprod_dev(dsa_mat* h, int32_t transpose, const int64_t* d_sel, int64_t ns
                  double* d_y, int64_t ldy, hipStream_t s);
 void selprod_host(dsa_mat* h, int32_t transpose, const int64_t* sel, int64_t nsel, const double* x, int64_t nx, int64_t k, int64_t ldx,
                   double* y, int64_t ldy);
+
+// ---- spgemm_host.hip: Y = A S / A' S for k sparse columns, operands and result CSC (d_* are device arrays; *nnz_out also with DSA_ECAP)
+void spgemm_csc_dev(dsa_mat* h, int32_t transpose, int32_t index_bits, int32_t index_base, const void* d_xptr, const void* d_xidx,
+                    const double* d_xval, int64_t k, int64_t nnzx, void* d_yptr, void* d_yidx, double* d_yval, int64_t cap, int64_t* nnz_out);
+void spgemm_csc_host(dsa_mat* h, int32_t transpose, int32_t index_base, const int64_t* xptr, const int64_t* xidx, const double* xval, int64_t k,
+                     int64_t* yptr, int64_t* yidx, double* yval, int64_t cap, int64_t* nnz_out);
 
 // ---- export_host.hip: the compressed form of an orientation, of selected columns / rows and of a submatrix (d_* are device arrays; *nnz_out also
 // with DSA_ECAP), and the check of an index format that the import shares: index_bits 32 | 64, index_base 0 | 1

@@ -69,6 +69,8 @@ void pma_destroy(Pma& P) {
     P.sub.release();
     P.subi.release();
     P.sc.release();
+    P.spg.release();
+    P.spgs.release();
     if (P.tmerge.sems2) hipFree(P.tmerge.sems2);
     if (P.tmerge.keys2) hipFree(P.tmerge.keys2);
     if (P.tmerge.pkey) hipFree(P.tmerge.pkey);

@@ -25,7 +25,7 @@ export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC
        deletecolumn!, deleterow!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
        keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev,
-       scale!, reduce_rows, reduce_cols, mul_rows, mul_cols
+       scale!, reduce_rows, reduce_cols, mul_rows, mul_cols, mul_sparse
 
 const libdsa = get(ENV, "DSA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libdsa_hip.so"))
 
@@ -638,6 +638,36 @@ _mul_selected(a, tr, keys, X::Matrix{Float64}) = permutedims(_spmm_selected(a, t
 _mul_selected(a, tr, keys, x::Vector{Float64}) = vec(_spmm_selected(a, tr, keys, reshape(x, 1, length(x))))
 mul_rows(a::DynamicSparseMatrix, rows::AbstractVector{<:Integer}, X) = _mul_selected(a, false, rows, X)
 mul_cols(a::DynamicSparseMatrix, cols::AbstractVector{<:Integer}, X) = _mul_selected(a, true, cols, X)
+
+# mul_sparse(A, S) = A * S and transpose(A) * S for a SparseMatrixCSC S (include/dsa.h: dsa_mat_spgemm_csc, 1-based; the k-column form of
+# the sparse-x product, src/operations.jl:62-135): column j of the result is A * S[:, j] — the touched rows only, stored zeros kept —
+# bit for bit and the same on every call.  Integer keys only, like _select_int.  The first call counts (cap = 0: DSA_ECAP leaves ptr
+# filled and the total in `got`), the second one fetches.
+function _spgemm(a::DynamicSparseMatrix{K,L}, tr::Bool, S::SparseMatrixCSC, ny::Integer) where {K,L}
+    (K <: Integer && L <: Integer) || throw(ArgumentError("a sparse-sparse product needs integer row and column keys, got $(K), $(L)"))
+    xptr = Vector{Int64}(S.colptr); xidx = Vector{Int64}(rowvals(S)); xval = Vector{Float64}(nonzeros(S))
+    k = size(S, 2)
+    ptr = Vector{Int64}(undef, k + 1); idx = Int64[]; val = Float64[]
+    got = Ref{Int64}(0)
+    for _ in 1:2
+        cap = length(idx)
+        rc = GC.@preserve xptr xidx xval ptr idx val ccall((:dsa_mat_spgemm_csc, libdsa), Int32,
+            (Ptr{Cvoid}, Int32, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ref{Int64}),
+            a.h, Int32(tr ? 1 : 0), Int32(1), xptr, xidx, xval, k, ptr, cap == 0 ? Ptr{Int64}(C_NULL) : pointer(idx),
+            cap == 0 ? Ptr{Float64}(C_NULL) : pointer(val), cap, got)
+        if rc == 8 && cap == 0                      # DSA_ECAP
+            resize!(idx, got[]); resize!(val, got[])
+            continue
+        end
+        _check(rc)
+        break
+    end
+    return SparseMatrixCSC(ny, k, ptr, idx, val)
+end
+mul_sparse(a::DynamicSparseMatrix, S::SparseMatrixCSC) = _spgemm(a, false, S, _size_int(a)[1])
+mul_sparse(t::Transposed{<:DynamicSparseMatrix}, S::SparseMatrixCSC) = _spgemm(t.array, true, S, _size_int(t.array)[2])
+Base.:(*)(a::DynamicSparseMatrix, S::SparseMatrixCSC) = mul_sparse(a, S)
+Base.:(*)(t::Transposed{<:DynamicSparseMatrix}, S::SparseMatrixCSC) = mul_sparse(t, S)
 
 # Reductions over the stored cells of every row / column and the in-place scaling A <- Diagonal(rows) * (alpha * A) * Diagonal(cols)
 # (include/dsa.h: dsa_mat_reduce, dsa_mat_scale; no reference counterpart — sum(abs, A; dims), maximum(abs, ...), lmul! / rmul! of a

@@ -354,6 +354,50 @@ int32_t dsa_mat_spmm_selected_dev(dsa_mat_t* h, int32_t transpose, const int64_t
                                   const double* d_x, int64_t nx, int64_t k, int64_t ldx, double* d_y, int64_t ldy);
 int32_t dsa_mat_spmm_selected(dsa_mat_t* h, int32_t transpose, const int64_t* sel, int64_t nsel,
                               const double* x, int64_t nx, int64_t k, int64_t ldx, double* y, int64_t ldy);
+/* The batched sparse-x product (csrc/spgemm.hip): Y = A S (transpose = 0: the colmajor orientation is walked, the indices of S are
+ * column keys of A, the indices of Y row keys, ny = m) or Y = A' S (transpose = 1: rowmajor, ny = n) for k SPARSE columns.  S and Y are
+ * CSC in the conventions of dsa_mat_to_compressed_dev: xptr[k + 1], xidx / xval[nnzx], yptr[k + 1], yidx / yval[total]; index_bits 32 |
+ * 64 covers all four index arrays, index_base 0 | 1: ptr[j] = base + entries in front of column j, idx = key - 1 + base.  The result can
+ * go straight into dsa_mat_create_from_compressed_dev.
+ * Column j of Y is what the reference's _mul (src/operations.jl:62-135) gives for column j of S: the touched rows only, ascending, a
+ * touched row whose sum is 0.0 kept.  A value is summed from +0.0 over the stored entries of the column of S in their order, each
+ * matching partition in slot order, one multiply then one add per term (no FMA), WITHOUT float atomics: it is bit-identical to what the
+ * reference computes for that column and from call to call (dsa_mat_spmv_sparse* adds with fp64 atomics and cannot promise that).  The
+ * one exception is the payload of a NaN, which IEEE 754 leaves open: 0 * Inf gives a NaN of the other sign bit on the device than on an
+ * x86 host, so a NaN of the result is a NaN of the reference, not necessarily with the same bits (still the same from call to call).  An
+ * entry of S whose key has no live partition (never written, deleted, beyond the table, below 1) contributes nothing.  A stored Inf /
+ * NaN of A counts only through a column S stores; a stored 0.0 of S times Inf is NaN.
+ * Input contract, checked on the device (DSA_EARG): xptr[0] == base, xptr does not decrease, xptr[k] - base == nnzx, xidx ascends
+ * strictly within a column (the reference's loop only moves forward).
+ * Capacity: as for dsa_mat_select_compressed_dev.  cap < total returns DSA_ECAP with *nnz_out = total, yptr COMPLETE AND VALID, yidx /
+ * yval untouched; cap = 0 with d_yidx = d_yval = NULL is the count-only call (DSA_OK when the total is 0).  The second call computes the
+ * spans again: nothing about a product stays on the handle.  *nnz_out = the entries of Y on return, also with DSA_ECAP.
+ * A column whose products visit at most 1024 stored cells is summed in an LDS hash table; a longer one in a slab of ny doubles (at
+ * most 16 slabs and 1 GiB of them per orientation, kept with the handle, all zero between two calls; csrc/spgemm.h names the four
+ * constants).  When a single slab would exceed the byte limit the call returns DSA_EARG and nothing of that size is allocated.
+ * Errors: DSA_EMODE in fill mode.  DSA_EARG: transpose, index_bits or index_base invalid; k or nnzx outside 0 .. 2^31 - 1; a NULL array
+ * of a non-empty shape (xptr and yptr always, xidx / xval with nnzx > 0, yidx / yval with cap > 0); with index_bits 32, ny or total +
+ * base above INT32_MAX; the input contract; the slab limit.  DSA_EBOUNDS: a touched row key outside 1..ny.  DSA_EASSERT: partition
+ * tables and slot array out of step, or a full hash table.  Every probe sequence on the device is bounded: a defect ends as a status.
+ * _dev: every array is a device address; enqueued on the stream of the orientation that is walked (dsa_mat_set_stream / dsa_mat_sync).
+ * One memset and at most eight kernel launches (bound, classify; count in LDS, count in slabs, scan; emit from LDS, emit from slabs,
+ * hand-over; the slab launches only with long columns) and at most three host waits through pinned words (input contract and long
+ * columns; the total; the error word behind the emit), whatever k, nnzx and the lengths of the partitions are.  A call that needs more
+ * scratch or more slab bytes than the handle holds (the first call, the first one with long columns, a larger one) adds to that: a
+ * pool allocation, a stream synchronisation before the smaller block is let go, and a second memset over the new slabs.  The slabs
+ * stay with the handle until it is destroyed (dsa_pool_trim does not see them).  classify and scan are one workgroup each, looping
+ * over the k columns: bounded, but slow for k near 2^31.
+ * Cost: the call has a fixed cost of three hand-overs, the LDS path walks the entries of a column one after the other, and the slab
+ * path is one entry at a time with a barrier in between: for columns that visit more than 1024 cells, and for a single short column,
+ * k calls of dsa_mat_spmv_sparse_dev are far faster (README.md holds the measured points).  Read-only: slots, tables and both epochs
+ * stay as they are, a cached SpMV plan survives. */
+int32_t dsa_mat_spgemm_csc_dev(dsa_mat_t* h, int32_t transpose, int32_t index_bits, int32_t index_base,
+                               const void* d_xptr, const void* d_xidx, const double* d_xval, int64_t k, int64_t nnzx,
+                               void* d_yptr, void* d_yidx, double* d_yval, int64_t cap, int64_t* nnz_out);
+/* the same with host arrays and int64 indices (nnzx = xptr[k] - base), staged through pooled device memory (DSA_ECAP leaves yptr filled) */
+int32_t dsa_mat_spgemm_csc(dsa_mat_t* h, int32_t transpose, int32_t index_base,
+                           const int64_t* xptr, const int64_t* xidx, const double* xval, int64_t k,
+                           int64_t* yptr, int64_t* yidx, double* yval, int64_t cap, int64_t* nnz_out);
 /* ---- reductions per row / column and in-place diagonal scaling (csrc/scale.hip).  No reference counterpart: what sum(abs, A; dims),
  * maximum(abs, ...) and SparseArrays' lmul! / rmul! with Diagonal factors do for a SparseMatrixCSC.
  *

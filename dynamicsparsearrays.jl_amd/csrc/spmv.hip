@@ -802,12 +802,16 @@ hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_
 }
 
 // The product.  One wave per group, 4 independent waves per workgroup, all groups resident (<= 4096 groups, 32 KB of LDS per
-// workgroup).  Per slice the wave streams its cells 256 at a time (plain loads, see load_round), gathers x, and adds each product to its
-// row's LDS accumulator.  A row's cells in a chunk of 64 lie on consecutive lanes; they are added one rank after the other, so every
-// row is 0.0 + its products in ascending column order — what k_spmv_gather computes for a row that one lane sums.  The first round of
-// slice s + 1 is requested behind the gathers of slice s.  At the end every row of the group is stored once, and the rows without a
-// partition in front of each row (behind the last one: up to ny) are zeroed, as the ZFILL gather does.  No atomics, no barriers.
-constexpr int PLAN_U = 4;          // chunks of 64 cells per round
+// workgroup).  Per slice the wave streams its cells one round at a time (plain loads, see load_round), gathers x, and adds each product
+// to its row's LDS accumulator.  A row's cells in a chunk of 64 lie on consecutive lanes; they are added one rank after the other, so
+// every row is 0.0 + its products in ascending column order — what k_spmv_gather computes for a row that one lane sums.  The stream
+// runs ONE round ahead, across the slices: behind the gathers of a round the next round is requested, the rest of this slice or the
+// first cells of the next one.  At the end every row of the group is stored once, and the rows without a partition in front of each
+// row (behind the last one: up to ny) are zeroed, as the ZFILL gather does.  No atomics, no barriers.
+// Rounds of ONE chunk: a (group, slice) of config 3 holds ~153 cells, and the fewer gathers a wave issues at once the faster the
+// kernel runs — rounds of 4 / 2 / 1 chunks with only a slice's first round requested ahead: 69.6 / 64.6 / 62.3 us on config 3; one
+// round ahead everywhere, 1 chunk: 59.9 us (profiles/planprefetch_bench_ab.json).
+constexpr int PLAN_U = 1;          // chunks of 64 cells per round
 __global__ __launch_bounds__(SP_BLOCK) void k_spmv_plan(PlanDev pl, const int64_t* __restrict__ part_keys, int64_t table_len,
                                                         const double* __restrict__ x, double* __restrict__ y, int64_t ny) {
     __shared__ double sAcc[SP_WAVES][PLAN_ROWS];
@@ -864,24 +868,23 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spmv_plan(PlanDev pl, const int64_
     for (int u = 0; u < PLAN_U; ++u) { cB[u] = PLAN_NONE; vB[u] = 0.0; }
     uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)myoff, 0), e = (uint32_t)__builtin_amdgcn_readlane((int)myoff, 1);
     load_round(b, e, cA, vA);
-    for (int s = 0; s < P; ++s) {
-        const uint32_t xbase = (uint32_t)s * W;      // < nx <= 63 * 65536
-        gather(xbase, cA, xq);
-        uint32_t nb = 0, ne = 0;
-        if (s + 1 < P) {
-            nb = (uint32_t)__builtin_amdgcn_readlane((int)myoff, s + 1);
-            ne = (uint32_t)__builtin_amdgcn_readlane((int)myoff, s + 2);
-            load_round(nb, ne, cB, vB);
+    uint32_t r = b;                                   // first cell of the round in cA, of the slice that ends at e
+    for (int s = 0;;) {
+        gather((uint32_t)s * W, cA, xq);             // s * W < nx <= 63 * 65536
+        // the next round: the rest of this slice, or the first cells of the next one (an empty slice is a round without cells)
+        uint32_t nr = r + PLAN_U * 64;
+        int ns = s;
+        if (nr >= e) {
+            ns = s + 1;
+            if (ns < P) { nr = (uint32_t)__builtin_amdgcn_readlane((int)myoff, ns); e = (uint32_t)__builtin_amdgcn_readlane((int)myoff, ns + 1); }
         }
+        const bool more = ns < P;
+        if (more) load_round(nr, e, cB, vB);
         apply(cA, vA, xq);
-        for (uint32_t r = b + PLAN_U * 64; r < e; r += PLAN_U * 64) {      // (long slices: the rest of the slice, round by round)
-            load_round(r, e, cA, vA);
-            gather(xbase, cA, xq);
-            apply(cA, vA, xq);
-        }
+        if (!more) break;
 #pragma unroll
         for (int u = 0; u < PLAN_U; ++u) { cA[u] = cB[u]; vA[u] = vB[u]; }
-        b = nb; e = ne;
+        r = nr; s = ns;
     }
     __builtin_amdgcn_wave_barrier();
     for (int i = lane; i < np; i += 64) {

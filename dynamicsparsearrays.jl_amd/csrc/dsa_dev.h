@@ -517,22 +517,27 @@ constexpr int64_t PLAN_GROUP_SLOTS = int64_t(1) << PLAN_GROUP_SHIFT;
 constexpr int PLAN_ROWS = 1024;               // rows (partitions) per group the product kernel accumulates in LDS
 constexpr int PLAN_MAX_SLICES = 63;           // offsets of a group (slices + 1) are held one per lane
 constexpr int64_t PLAN_MAX_GROUPS = 4096;     // every group resident at once: 16 waves per CU
+constexpr int PLAN_DESC = 5;                  // words of a group's descriptor row beside its `slices` first cells (PlanDev::off)
 struct PlanDev {
     uint32_t* cell; double* val;              // cap_cells entries each
-    uint32_t* off;                            // groups x (slices + 1)
+    uint32_t* off;                            // groups x (slices + PLAN_DESC): the group's descriptor row {first partition (0-based id),
+                                              // partitions, row map entry of the first partition, 1 if the group is dense (rows
+                                              // consecutive, none to zero), first cell of slice 0 .. slices (= end of the last slice)}
     uint32_t* cnt;                            // groups x slices: cells per (group, slice)
     uint32_t* gbase;                          // groups: first cell of the group
     uint32_t* pfirst;                         // groups + 1: first partition (0-based id) of the group
     uint32_t* nsem;                           // groups: partitions of the group
+    uint32_t* yrow;                           // table_len: row map, min(max(part_keys[id], 0), ny + 1) per partition id
     int64_t groups, width, cap_cells;
     int32_t slices, pad_;
 };
 // count pass + scan + scatter (three launches on `stream`, no host wait); the scan writes {ok, cells} and then `seq` to out3_pinned
-hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t table_len, int64_t nx,
-                                  const PlanDev& pl, unsigned long long* out3_pinned, unsigned long long seq, hipStream_t stream);
+// (and pass<true> fills the row map from part_keys)
+hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* part_keys,
+                                  int64_t table_len, int64_t nx, int64_t ny, const PlanDev& pl, unsigned long long* out3_pinned,
+                                  unsigned long long seq, hipStream_t stream);
 // y = P x from the plan (every row of [1, ny] written once, as the ZFILL gather does)
-hipError_t launch_spmv_plan(const PlanDev& pl, const int64_t* part_keys, int64_t table_len, const double* x, double* y, int64_t ny,
-                            hipStream_t stream);
+hipError_t launch_spmv_plan(const PlanDev& pl, int64_t table_len, const double* x, double* y, int64_t ny, hipStream_t stream);
 // y[key] += x[part_key[p]] * val, scatter form with fp64 atomics (the literal _mul loop nest)
 hipError_t launch_spmv_scatter(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
                                const int64_t* sems, const int64_t* part_keys, const uint8_t* part_live, int64_t table_len,

@@ -701,10 +701,10 @@ void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, in
             { mode |= SPMV_ZFILL; ++P.stat_spmv_nomemset; }
         if (nx * (int64_t)sizeof(double) <= (3 << 20)) mode |= SPMV_PLAIN_STREAM;      // x stays in an XCD's 4 MB L2 beside the stream
         const bool plan = spmv_plan_on() && pattern == 0 && (mode & SPMV_ZFILL) && !(mode & SPMV_PLAIN_STREAM) && s == P.stream &&
-                          nx > 0 && spmv_plan_shape_ok(P, nx);
+                          nx > 0 && spmv_plan_shape_ok(P, nx, ny);
         if (plan && spmv_plan_product(P, d_x, nx, d_y, ny, s)) return;
         e = launch_spmv_gather(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, d_x, nx, d_y, ny, pattern, mode, s);
-        if (e == hipSuccess && plan && P.plan.state == Pma::SpmvPlan::NONE && P.plan.products == 2) spmv_plan_build(P, nx, s);
+        if (e == hipSuccess && plan && P.plan.state == Pma::SpmvPlan::NONE && P.plan.products == 2) spmv_plan_build(P, nx, ny, s);
     } else if (algo == 1) {
         Pma& P = transpose ? h->row : h->col;
         e = launch_spmv_scatter(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, d_x, nx, d_y, ny, s);

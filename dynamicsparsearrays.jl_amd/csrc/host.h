@@ -136,7 +136,7 @@ struct Pma {
         enum State { NONE, PENDING, USABLE, UNUSABLE } state = NONE;
         int64_t content_epoch = -1, layout_epoch = -1, nx = -1, ny = -1, products = 0;
         PlanDev dev{};
-        void* mem[2] = {nullptr, nullptr};      // cells + values, offsets + scratch
+        void* mem[2] = {nullptr, nullptr};      // cells + values, descriptor rows + scratch + row map
         int64_t bytes = 0;
         unsigned long long seq = 0;
     } plan;
@@ -258,8 +258,8 @@ void spmv_plan_drop(Pma& P);
 void prefetch_spmv_meta(Pma& P);
 const Pma::SpmvMeta& spmv_meta(Pma& P);
 bool spmv_plan_on();
-bool spmv_plan_shape_ok(const Pma& P, int64_t nx);
-void spmv_plan_build(Pma& P, int64_t nx, hipStream_t s);
+bool spmv_plan_shape_ok(const Pma& P, int64_t nx, int64_t ny);
+void spmv_plan_build(Pma& P, int64_t nx, int64_t ny, hipStream_t s);
 bool spmv_plan_product(Pma& P, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s);
 
 // ---- dsa_host.hip: what sparsex_host.hip needs of the handle layer

@@ -383,7 +383,7 @@ void pma_info(Pma& P, int64_t nb_partitions_or_len, int64_t* info) {
     info[DSA_INFO_HBM_BYTES] = 2 * (P.cap_alloc * (int64_t)(P.kb() + sizeof(double)) + P.occ_words * 8) + (P.occ_old ? P.occ_words * 8 : 0) +
                                (P.has_sems ? c.table_cap * 8 : 0) + (P.has_cols ? c.table_cap * 9 : 0) + 2 * P.tmerge_cap * 8 +
                                (P.d_ops ? P.ops_cap * (int64_t)sizeof(Op) + (P.ops_cap / 64 + 8) * 8 : 0) + (P.d_opsrc ? P.opsrc_cap * 24 : 0) +      // op array, run-break bitmap, batch columns
-                               P.plan.bytes +     // the SpMV plan: 12 B per stored cell + offsets
+                               P.plan.bytes +     // the SpMV plan: 12 B per stored cell + descriptor rows + 4 B per partition (row map)
                                (int64_t)P.sel.bytes +     // scratch of the selected export: 32 B per key of the longest selection so far
                                (int64_t)(P.sub.bytes + P.subi.bytes);      // ... of the submatrix export: hash table, spans, work items
 }

@@ -659,13 +659,17 @@ static hipError_t launch_spmv(bool scatter, int pattern, int mode, KeyArr keys, 
 // orientation, built on the device once per content epoch: group g (the rows whose semaphore lies in slots [g * 4096, (g + 1) * 4096))
 // keeps, per column slice s, its cells of that slice in (row, column) order.  k_spmv_plan gives each group to one wave; all waves are
 // resident and walk the slices in the same order, so an XCD gathers from one or two 0.5 MB slices at a time: L2 hits.
-// Build: k_plan_pass<false> counts per (group, slice), k_plan_scan places the groups, k_plan_pass<true> scatters in slot order (stable).
+// Build: k_plan_pass<false> counts per (group, slice), k_plan_scan places the groups, k_plan_pass<true> scatters in slot order (stable),
+// writes the group's descriptor row {first partition, partitions, first row, dense flag, slice offsets} and the group's part of the
+// row map: the row keys of its partitions clamped to [0, ny + 1], 32 bits each — all the product's tail asks of a key
+// (zero_fill_front's bounds, the 1 <= row <= ny store condition, the fill up to ny) has the same answer for the clamped key.
 constexpr uint32_t PLAN_NONE = 0xffffffffu;
 
 // one wave per group: its 64 words, then — for the row that is open at the group's end — the cells up to the next semaphore
 template <bool SCATTER>
 __global__ __launch_bounds__(256) void k_plan_pass(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ,
-                                                   int64_t capacity, int64_t nx, PlanDev pl) {
+                                                   int64_t capacity, int64_t nx, PlanDev pl,
+                                                   const int64_t* __restrict__ part_keys, int64_t table_len, int64_t ny) {
     __shared__ uint32_t sPos[SP_WAVES][PLAN_MAX_SLICES + 1];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t g = (int64_t)blockIdx.x * SP_WAVES + wv;
@@ -680,7 +684,28 @@ __global__ __launch_bounds__(256) void k_plan_pass(KeyArr keys, const double* __
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
         const uint32_t start = pl.gbase[g] + incl - c;
-        if (lane <= P) { pos[lane] = start; pl.off[g * (P + 1) + lane] = start; }
+        uint32_t* __restrict__ drow = pl.off + g * (P + PLAN_DESC);
+        const uint32_t p0 = pl.pfirst[g], np = pl.pfirst[g + 1] - p0;
+        if (lane <= P) { pos[lane] = start; drow[PLAN_DESC - 1 + lane] = start; }
+        const int64_t top = ny + 1;                   // (< 2^32: spmv_plan_shape_ok)
+        auto clamped = [&](int64_t k) -> uint32_t { return (uint32_t)(k < 0 ? 0 : (k > top ? top : k)); };
+        // dense: the group's rows are row0, row0 + 1, ... within [1, ny], the first one follows the row in front of the group and
+        // the table's last partition is row ny — the product stores such a group without its row map and without any zero fill
+        bool dense = true;
+        for (uint32_t i = (uint32_t)lane; i < np; i += 64u) {
+            const int64_t id = (int64_t)p0 + i;
+            if (id < table_len) {                     // (more semaphores than partitions: the scan reports the plan unusable)
+                const uint32_t k = clamped(part_keys[id]), kp = id > 0 ? clamped(part_keys[id - 1]) : 0u;
+                pl.yrow[id] = k;
+                dense = dense && k == kp + 1u && k >= 1u && (int64_t)k <= ny && (id + 1 < table_len || (int64_t)k == ny);
+            } else dense = false;
+        }
+        const bool all_dense = __ballot(!dense) == 0ull && np > 0u;
+        if (lane == 0) {
+            drow[0] = p0; drow[1] = np;
+            drow[2] = (int64_t)p0 < table_len ? clamped(part_keys[p0]) : 0u;
+            drow[3] = all_dense ? 1u : 0u;
+        }
     } else {
         pos[lane] = 0u;
     }
@@ -790,14 +815,16 @@ __global__ __launch_bounds__(PLAN_SCAN_THREADS) void k_plan_scan(PlanDev pl, int
     }
 }
 
-hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t table_len, int64_t nx,
-                                  const PlanDev& pl, unsigned long long* out3_pinned, unsigned long long seq, hipStream_t stream) {
-    if (pl.groups <= 0 || pl.groups > PLAN_MAX_GROUPS || pl.slices <= 0 || pl.slices > PLAN_MAX_SLICES || pl.width <= 0 || pl.width > 65536)
+hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* part_keys,
+                                  int64_t table_len, int64_t nx, int64_t ny, const PlanDev& pl, unsigned long long* out3_pinned,
+                                  unsigned long long seq, hipStream_t stream) {
+    if (pl.groups <= 0 || pl.groups > PLAN_MAX_GROUPS || pl.slices <= 0 || pl.slices > PLAN_MAX_SLICES || pl.width <= 0 || pl.width > 65536 ||
+        ny < 0 || ny + 1 >= ((int64_t)1 << 32))
         return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((pl.groups + SP_WAVES - 1) / SP_WAVES);
-    hipLaunchKernelGGL(k_plan_pass<false>, dim3(grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, nx, pl);
+    hipLaunchKernelGGL(k_plan_pass<false>, dim3(grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, nx, pl, part_keys, table_len, ny);
     hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(PLAN_SCAN_THREADS), 0, stream, pl, table_len, out3_pinned, seq);
-    hipLaunchKernelGGL(k_plan_pass<true>, dim3(grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, nx, pl);
+    hipLaunchKernelGGL(k_plan_pass<true>, dim3(grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, nx, pl, part_keys, table_len, ny);
     return hipGetLastError();
 }
 
@@ -811,22 +838,37 @@ hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_
 // Rounds of ONE chunk: a (group, slice) of config 3 holds ~153 cells, and the fewer gathers a wave issues at once the faster the
 // kernel runs — rounds of 4 / 2 / 1 chunks with only a slice's first round requested ahead: 69.6 / 64.6 / 62.3 us on config 3; one
 // round ahead everywhere, 1 chunk: 59.9 us (profiles/planprefetch_bench_ab.json).
+// Head and tail (profiles/planrowmap_*): all waves start and finish together, so what a wave does before its first add and after its
+// last one is on the launch's critical path.  Head: the group's descriptor row in two loads that are in flight together, the
+// accumulators zeroed with a fixed trip count — one round trip in front of the first cell load.  Tail: a dense group (the build's
+// flag: consecutive row keys, nothing to zero) stores acc[i] to y[row0 - 1 + i] without a load; any other group reads its rows
+// from the plan's 32-bit row map.
 constexpr int PLAN_U = 1;          // chunks of 64 cells per round
-__global__ __launch_bounds__(SP_BLOCK) void k_spmv_plan(PlanDev pl, const int64_t* __restrict__ part_keys, int64_t table_len,
-                                                        const double* __restrict__ x, double* __restrict__ y, int64_t ny) {
+__global__ __launch_bounds__(SP_BLOCK) void k_spmv_plan(PlanDev pl, int64_t table_len, const double* __restrict__ x,
+                                                        double* __restrict__ y, int64_t ny) {
     __shared__ double sAcc[SP_WAVES][PLAN_ROWS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t g = (int64_t)blockIdx.x * SP_WAVES + wv;
     if (g >= pl.groups) return;
     double* acc = sAcc[wv];
-    const uint32_t p0 = pl.pfirst[g];
-    const int np = (int)(pl.pfirst[g + 1] - p0);      // <= PLAN_ROWS (checked by the build)
-    for (int i = lane; i < np; i += 64) acc[i] = 0.0;
     const int P = pl.slices;
     const uint32_t W = (uint32_t)pl.width;
-    const uint32_t myoff = lane <= P ? pl.off[g * (P + 1) + lane] : 0u;
     const uint32_t* __restrict__ cp = pl.cell;
     const double* __restrict__ vp = pl.val;
+    // the group's descriptor row — first partition, partitions, first row, dense flag, slice offsets: slices + 5 <= 68 words of
+    // neighbouring cache lines — in two loads that are in flight together (indices clamped, not predicated), and the accumulators
+    // zeroed with a fixed trip count, so that nothing in front of the first cell load waits for a second round trip
+    const uint32_t* __restrict__ drow = pl.off + g * (P + PLAN_DESC);
+    const uint32_t dH = drow[lane & 3];
+    const uint32_t myoff = drow[PLAN_DESC - 1 + (lane < P ? lane : P)];
+#pragma unroll
+    for (int k = 0; k < PLAN_ROWS / 64; ++k) acc[k * 64 + lane] = 0.0;
+    const uint32_t p0 = (uint32_t)__builtin_amdgcn_readlane((int)dH, 0);
+    const int np = __builtin_amdgcn_readlane((int)dH, 1);      // <= PLAN_ROWS (checked by the build)
+    const uint32_t row0 = (uint32_t)__builtin_amdgcn_readlane((int)dH, 2);
+    const bool dense = __builtin_amdgcn_readlane((int)dH, 3) != 0;
+    // first cell of slice j (j uniform), j == slices: the end of the last slice
+    auto off_at = [&](int j) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)myoff, j); };
     __builtin_amdgcn_wave_barrier();
 
     // Plain loads, not non-temporal ones: a (group, slice) starts at any cell, so neighbouring rounds share their border lines, and
@@ -866,7 +908,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spmv_plan(PlanDev pl, const int64_
     double vA[PLAN_U], vB[PLAN_U], xq[PLAN_U];
 #pragma unroll
     for (int u = 0; u < PLAN_U; ++u) { cB[u] = PLAN_NONE; vB[u] = 0.0; }
-    uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)myoff, 0), e = (uint32_t)__builtin_amdgcn_readlane((int)myoff, 1);
+    uint32_t b = off_at(0), e = off_at(1);
     load_round(b, e, cA, vA);
     uint32_t r = b;                                   // first cell of the round in cA, of the slice that ends at e
     for (int s = 0;;) {
@@ -876,7 +918,7 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spmv_plan(PlanDev pl, const int64_
         int ns = s;
         if (nr >= e) {
             ns = s + 1;
-            if (ns < P) { nr = (uint32_t)__builtin_amdgcn_readlane((int)myoff, ns); e = (uint32_t)__builtin_amdgcn_readlane((int)myoff, ns + 1); }
+            if (ns < P) { nr = off_at(ns); e = off_at(ns + 1); }
         }
         const bool more = ns < P;
         if (more) load_round(nr, e, cB, vB);
@@ -887,20 +929,28 @@ __global__ __launch_bounds__(SP_BLOCK) void k_spmv_plan(PlanDev pl, const int64_
         r = nr; s = ns;
     }
     __builtin_amdgcn_wave_barrier();
+    if (dense) {      // rows row0 .. row0 + np - 1, all within [1, ny], no row to zero (checked by the build)
+        for (int i = lane; i < np; i += 64) y[row0 - 1u + (uint32_t)i] = acc[i];
+        return;
+    }
+    // A group with absent rows (rare where the flag pays: config 3 has 45 empty rows in 4096 groups) walks its part of the row map.
+    // Clamped 32-bit keys (see the build): the rows in (prev, row) and, behind the table's last partition, in (row, ny] have no
+    // partition and are zeroed.  Keeping the first 8 x 64 entries in registers from the start instead (no load here either) was
+    // measured equal on config 3 beside the dense flag and is not kept (profiles/planrowmap_bench_ab.json).
+    const uint32_t ny32 = (uint32_t)ny, last_id = (uint32_t)table_len - 1u;
     for (int i = lane; i < np; i += 64) {
         const uint32_t id = p0 + (uint32_t)i;
-        const int64_t row = part_keys[id];
-        const int64_t prev = id > 0 ? part_keys[id - 1] : 0;
-        zero_fill_front(y, ny, prev, row, (int64_t)id + 1 == table_len);
-        if (row >= 1 && row <= ny) y[row - 1] = acc[i];
+        const uint32_t row = pl.yrow[id], prev = id > 0u ? pl.yrow[id - 1u] : 0u;
+        if (prev < row) for (uint32_t q = prev + 1u; q < row; ++q) y[q - 1u] = 0.0;       // (guarded: no 32-bit wrap at ny + 1 = 2^32 - 1)
+        if (id == last_id && row < ny32) for (uint32_t q = row + 1u; q <= ny32; ++q) y[q - 1u] = 0.0;
+        if (row >= 1u && row <= ny32) y[row - 1u] = acc[i];
     }
 }
 
-hipError_t launch_spmv_plan(const PlanDev& pl, const int64_t* part_keys, int64_t table_len, const double* x, double* y, int64_t ny,
-                            hipStream_t stream) {
+hipError_t launch_spmv_plan(const PlanDev& pl, int64_t table_len, const double* x, double* y, int64_t ny, hipStream_t stream) {
     if (pl.groups <= 0 || pl.groups > PLAN_MAX_GROUPS) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((pl.groups + SP_WAVES - 1) / SP_WAVES);
-    hipLaunchKernelGGL(k_spmv_plan, dim3(grid), dim3(SP_BLOCK), 0, stream, pl, part_keys, table_len, x, y, ny);
+    hipLaunchKernelGGL(k_spmv_plan, dim3(grid), dim3(SP_BLOCK), 0, stream, pl, table_len, x, y, ny);
     return hipGetLastError();
 }
 

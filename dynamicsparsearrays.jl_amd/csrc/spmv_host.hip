@@ -80,12 +80,14 @@ void spmv_plan_drop(Pma& P) {
 
 static int plan_slices(int64_t nx) { return (int)std::max<int64_t>(16, (nx + 65535) / 65536); }
 
-bool spmv_plan_shape_ok(const Pma& P, int64_t nx) {
+// (ny + 1 < 2^32: the plan's row map keeps the row keys clamped to [0, ny + 1] as 32-bit words)
+bool spmv_plan_shape_ok(const Pma& P, int64_t nx, int64_t ny) {
     const int64_t groups = (P.capacity() + PLAN_GROUP_SLOTS - 1) / PLAN_GROUP_SLOTS;
-    return groups <= PLAN_MAX_GROUPS && plan_slices(nx) <= PLAN_MAX_SLICES && P.h_ctl->nb_elements < ((int64_t)1 << 31);
+    return groups <= PLAN_MAX_GROUPS && plan_slices(nx) <= PLAN_MAX_SLICES && P.h_ctl->nb_elements < ((int64_t)1 << 31) &&
+           ny >= 0 && ny + 1 < ((int64_t)1 << 32);
 }
 
-void spmv_plan_build(Pma& P, int64_t nx, hipStream_t s) {
+void spmv_plan_build(Pma& P, int64_t nx, int64_t ny, hipStream_t s) {
     Pma::SpmvPlan& L = P.plan;
     PlanDev& d = L.dev;
     d.groups = (P.capacity() + PLAN_GROUP_SLOTS - 1) / PLAN_GROUP_SLOTS;
@@ -93,19 +95,21 @@ void spmv_plan_build(Pma& P, int64_t nx, hipStream_t s) {
     d.width = (nx + d.slices - 1) / d.slices;
     d.cap_cells = std::max<int64_t>(1, P.h_ctl->nb_elements - P.h_ctl->table_len);      // every stored entry but the semaphores
     const int64_t G = d.groups, S = d.slices;
-    const int64_t words = G * (S + 1) + G * S + G + (G + 1) + G;                          // off, cnt, gbase, pfirst, nsem (uint32)
+    const int64_t T = std::max<int64_t>(1, P.h_ctl->table_len);
+    const int64_t words = G * (S + PLAN_DESC) + G * S + G + (G + 1) + G + T;                      // off, cnt, gbase, pfirst, nsem, yrow (uint32)
     HIPCHK(pool_alloc(&L.mem[0], (size_t)d.cap_cells * (sizeof(uint32_t) + sizeof(double))));
     HIPCHK(pool_alloc(&L.mem[1], (size_t)words * sizeof(uint32_t)));
     L.bytes = d.cap_cells * 12 + words * 4;
     d.val = static_cast<double*>(L.mem[0]);
     d.cell = reinterpret_cast<uint32_t*>(d.val + d.cap_cells);
     d.off = static_cast<uint32_t*>(L.mem[1]);
-    d.cnt = d.off + G * (S + 1);
+    d.cnt = d.off + G * (S + PLAN_DESC);
     d.gbase = d.cnt + G * S;
     d.pfirst = d.gbase + G;
     d.nsem = d.pfirst + G + 1;
+    d.yrow = d.nsem + G;
     unsigned long long* out = reinterpret_cast<unsigned long long*>(P.h_meta + 6);
-    launch_check(launch_spmv_plan_build(P.K(), P.V(), P.O(), P.capacity(), P.h_ctl->table_len, nx, d, out, ++L.seq, s), "spmv plan build: ");
+    launch_check(launch_spmv_plan_build(P.K(), P.V(), P.O(), P.capacity(), P.col_keys, P.h_ctl->table_len, nx, ny, d, out, ++L.seq, s), "spmv plan build: ");
     L.state = Pma::SpmvPlan::PENDING;
     ++P.stat_spmv_plan_builds;
 }
@@ -130,7 +134,7 @@ bool spmv_plan_product(Pma& P, const double* d_x, int64_t nx, double* d_y, int64
         }
     }
     if (L.state == Pma::SpmvPlan::USABLE) {
-        LAUNCH("spmv plan", launch_spmv_plan(L.dev, P.col_keys, P.h_ctl->table_len, d_x, d_y, ny, s));
+        LAUNCH("spmv plan", launch_spmv_plan(L.dev, P.h_ctl->table_len, d_x, d_y, ny, s));
         ++P.stat_spmv_plan;
         return true;
     }

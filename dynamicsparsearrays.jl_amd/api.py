@@ -445,13 +445,91 @@ class DynamicSparseMatrix(_Handle):
     def rebalance_root(self, orientation):
         self.b.call("mat_rebalance_root", self.h, orientation)
 
-    # ---- compressed export (include/dsa.h: dsa_mat_to_compressed[_dev]; HIP library only) ----------------------------------------
-    def _require_export(self):
-        if not self.b.has("mat_to_compressed"):
-            raise B.DsaArgumentError(B.EARG, "compressed export needs the HIP product library")
+    # ---- what the HIP-only calls below share ---------------------------------------------------------------------------------------
+    def _require(self, symbol, message):
+        """DsaArgumentError(message) on a binding that does not have `symbol`"""
+        if not self.b.has(symbol):
+            raise B.DsaArgumentError(B.EARG, message)
 
+    def _fits(self, name, *args):
+        """`name`(h, *args, &total) -> (total, fits): with DSA_ECAP the total is known and the arrays of `cap` entries are untouched"""
+        got = C.c_int64()
+        try:
+            self.b.call(name, self.h, *args, C.byref(got))
+        except B.DsaError as e:
+            if e.code != B.ECAP:
+                raise
+            return got.value, False
+        return got.value, True
+
+    def _two_calls(self, name, head, nouter, count_only):
+        """the host form `name`(h, *head, ptr, idx, vals, cap, &total) of a key-list export: the count-only call, then the one that fits"""
+        ptr = np.empty(nouter + 1, dtype=np.int64)
+        total, fits = self._fits(name, *head, ptr.ctypes.data_as(P_I64), None, None, 0)
+        if count_only and not fits:
+            return ptr, None, None
+        idx, val = np.empty(total, dtype=np.int64), np.empty(total, dtype=np.float64)
+        if not fits:
+            got = C.c_int64()
+            self.b.call(name, self.h, *head, ptr.ctypes.data_as(P_I64), idx.ctypes.data_as(P_I64), val.ctypes.data_as(P_F64), total, C.byref(got))
+            total = got.value
+        return ptr, idx[:total], val[:total]
+
+    # the torch forms of the three exports: the arrays never leave HBM
+    @staticmethod
+    def _torch_format(layout, index_dtype):
+        """(orientation, index dtype, index bits, the current device) of a torch export"""
+        import torch
+        if index_dtype is None:
+            index_dtype = torch.int64
+        if layout not in (torch.sparse_csr, torch.sparse_csc):
+            raise B.DsaArgumentError(B.EARG, "layout must be torch.sparse_csr or torch.sparse_csc")
+        if index_dtype not in (torch.int32, torch.int64):
+            raise B.DsaArgumentError(B.EARG, "index_dtype must be torch.int32 or torch.int64")
+        return (ROWMAJOR if layout == torch.sparse_csr else COLMAJOR, index_dtype, 32 if index_dtype == torch.int32 else 64,
+                torch.device("cuda", torch.cuda.current_device()))
+
+    @staticmethod
+    def _torch_keys(keys, dev):
+        """a key list as a one-dimensional int64 CUDA tensor (a tensor is used in place)"""
+        import torch
+        if isinstance(keys, torch.Tensor):
+            if keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1:
+                raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 CUDA tensor")
+            return keys.contiguous()
+        return torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)).to(dev)
+
+    def _torch_arrays(self, dev, index_dtype, nouter, call, what, total=None):
+        """(ptr[nouter + 1], idx, vals) of a device export of `what` as tensors.  call(d_ptr, d_idx, d_vals, cap) -> (total, fits):
+        the count-only call (cap = 0, 0 for idx / vals) unless the total is given, then the call into arrays of `total` entries"""
+        import torch
+        ptr = torch.empty(nouter + 1, dtype=index_dtype, device=dev)
+        fits = False
+        # the library works on the orientation's stream: the keys and the fresh blocks must be free of torch's pending work first, and
+        # torch's consumers of the result must start after the export has finished
+        if total is None:
+            torch.cuda.current_stream(dev).synchronize()
+            total, fits = call(ptr.data_ptr(), 0, 0, 0)
+        idx = torch.empty(max(total, 1), dtype=index_dtype, device=dev)
+        val = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+        if not fits:
+            torch.cuda.current_stream(dev).synchronize()
+            total, fits = call(ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), total)
+            if not fits:
+                raise B.DsaErrorException(B.ECAP, "the %s grew between the count and the emit" % what)
+        self.sync()
+        return ptr, idx[:total], val[:total]
+
+    @staticmethod
+    def _torch_tensor(orientation, arrays, nouter, ninner):
+        import torch
+        if orientation == ROWMAJOR:
+            return torch.sparse_csr_tensor(*arrays, size=(nouter, ninner))
+        return torch.sparse_csc_tensor(*arrays, size=(ninner, nouter))
+
+    # ---- compressed export (include/dsa.h: dsa_mat_to_compressed[_dev]; HIP library only) ----------------------------------------
     def _compressed(self, orientation, base):
-        self._require_export()
+        self._require("mat_to_compressed", "compressed export needs the HIP product library")
         m, n = self.size()
         outer = m if orientation == ROWMAJOR else n
         cap = self.nnz()
@@ -480,7 +558,7 @@ class DynamicSparseMatrix(_Handle):
     def to_compressed_dev(self, orientation, d_ptr, d_idx, d_vals, cap, index_bits=64, base=0):
         """the compressed form into device memory (device addresses, e.g. tensor.data_ptr()); enqueued on the orientation's stream
         (sync()); returns nnz"""
-        self._require_export()
+        self._require("mat_to_compressed", "compressed export needs the HIP product library")
         got = C.c_int64()
         self.b.call("mat_to_compressed_dev", self.h, int(orientation), int(index_bits), int(base), C.c_void_p(int(d_ptr)),
                     C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)), int(cap), C.byref(got))
@@ -489,80 +567,30 @@ class DynamicSparseMatrix(_Handle):
     def to_torch(self, layout, index_dtype=None):
         """torch.sparse_csr_tensor (layout torch.sparse_csr, from rowmajor) or torch.sparse_csc_tensor (torch.sparse_csc, from
         colmajor) of size(m) on the current device; the arrays never leave HBM"""
-        import torch
-        self._require_export()
-        if index_dtype is None:
-            index_dtype = torch.int64
-        if layout not in (torch.sparse_csr, torch.sparse_csc):
-            raise B.DsaArgumentError(B.EARG, "layout must be torch.sparse_csr or torch.sparse_csc")
-        if index_dtype not in (torch.int32, torch.int64):
-            raise B.DsaArgumentError(B.EARG, "index_dtype must be torch.int32 or torch.int64")
-        orientation = ROWMAJOR if layout == torch.sparse_csr else COLMAJOR
+        self._require("mat_to_compressed", "compressed export needs the HIP product library")
+        orientation, index_dtype, bits, dev = self._torch_format(layout, index_dtype)
         m, n = self.size()
-        outer = m if orientation == ROWMAJOR else n
-        nnz = self.nnz()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        ptr = torch.empty(outer + 1, dtype=index_dtype, device=dev)
-        idx = torch.empty(max(nnz, 1), dtype=index_dtype, device=dev)
-        val = torch.empty(max(nnz, 1), dtype=torch.float64, device=dev)
-        # the library writes on the orientation's stream: the fresh blocks must be free of torch's pending work first, and torch's
-        # consumers of the result must start after the export has finished
-        torch.cuda.current_stream(dev).synchronize()
-        got = self.to_compressed_dev(orientation, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nnz,
-                                     index_bits=32 if index_dtype == torch.int32 else 64)
-        self.sync()
-        idx, val = idx[:got], val[:got]
-        if orientation == ROWMAJOR:
-            return torch.sparse_csr_tensor(ptr, idx, val, size=(m, n))
-        return torch.sparse_csc_tensor(ptr, idx, val, size=(m, n))
+        outer, inner = (m, n) if orientation == ROWMAJOR else (n, m)
+        arrays = self._torch_arrays(dev, index_dtype, outer, what="matrix", total=self.nnz(), call=lambda d_ptr, d_idx, d_vals, cap: (
+            self.to_compressed_dev(orientation, d_ptr, d_idx, d_vals, cap, index_bits=bits), True))
+        return self._torch_tensor(orientation, arrays, outer, inner)
 
     # ---- selected export (include/dsa.h: dsa_mat_select_compressed[_dev]; HIP library only) --------------------------------------
-    def _require_select(self):
-        if not self.b.has("mat_select_compressed"):
-            raise B.DsaArgumentError(B.EARG, "the selected export needs the HIP product library")
-
     def select_compressed_dev(self, orientation, d_sel, nsel, d_ptr, d_idx, d_vals, cap, index_bits=64, base=0):
         """A[:, sel] (COLMAJOR) / A[sel, :] (ROWMAJOR) in compressed form into device memory: d_sel = nsel int64 outer keys (1-based,
         any order, repeats allowed), d_ptr = nsel + 1 indices, d_idx / d_vals = cap entries (device addresses, e.g. tensor.data_ptr();
         0 for idx / vals with cap = 0: the count-only call).  Enqueued on the orientation's stream (sync()).  Returns (total, fits):
         the number of selected cells and whether they were delivered; with fits False (cap < total) only ptr has been written."""
-        self._require_select()
-        got = C.c_int64()
-        try:
-            self.b.call("mat_select_compressed_dev", self.h, int(orientation), int(index_bits), int(base), C.c_void_p(int(d_sel)),
-                        int(nsel), C.c_void_p(int(d_ptr)), C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)), int(cap), C.byref(got))
-        except B.DsaError as e:
-            if e.code == B.ECAP:
-                return got.value, False
-            raise
-        return got.value, True
+        self._require("mat_select_compressed", "the selected export needs the HIP product library")
+        return self._fits("mat_select_compressed_dev", int(orientation), int(index_bits), int(base), C.c_void_p(int(d_sel)), int(nsel),
+                          C.c_void_p(int(d_ptr)), C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)), int(cap))
 
     def _select(self, orientation, keys, base, count_only=False):
-        self._require_select()
+        self._require("mat_select_compressed", "the selected export needs the HIP product library")
         sel, sp = _i64(keys)
         if sel.ndim != 1:
             raise B.DsaArgumentError(B.EARG, "the selection must be one-dimensional")
-        nsel = len(sel)
-        ptr = np.empty(nsel + 1, dtype=np.int64)
-        got = C.c_int64()
-        idx = val = None
-        for _ in range(2):              # the count-only call, then the one that fits
-            cap = 0 if idx is None else len(idx)
-            try:
-                self.b.call("mat_select_compressed", self.h, int(orientation), int(base), sp, nsel, ptr.ctypes.data_as(P_I64),
-                            idx.ctypes.data_as(P_I64) if cap else None, val.ctypes.data_as(P_F64) if cap else None, cap, C.byref(got))
-            except B.DsaError as e:
-                if e.code != B.ECAP or idx is not None:
-                    raise
-                if count_only:
-                    return ptr, None, None
-                idx = np.empty(got.value, dtype=np.int64)
-                val = np.empty(got.value, dtype=np.float64)
-                continue
-            break
-        if idx is None:
-            idx, val = np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
-        return ptr, idx[:got.value], val[:got.value]
+        return self._two_calls("mat_select_compressed", (int(orientation), int(base), sp, len(sel)), len(sel), count_only)
 
     def select_columns(self, cols, base=0):
         """A[:, cols] as scipy-style CSC arrays (indptr, indices, data) with len(cols) columns: int64 indices counted from `base`"""
@@ -584,66 +612,26 @@ class DynamicSparseMatrix(_Handle):
         """A[:, keys] as torch.sparse_csc_tensor of shape (m, len(keys)) (layout torch.sparse_csc) or A[keys, :] as
         torch.sparse_csr_tensor of shape (len(keys), n) (torch.sparse_csr) on the current device.  `keys`: a list, a numpy array, or
         an int64 CUDA tensor (used in place); the arrays never leave HBM."""
-        import torch
-        self._require_select()
-        if index_dtype is None:
-            index_dtype = torch.int64
-        if layout not in (torch.sparse_csr, torch.sparse_csc):
-            raise B.DsaArgumentError(B.EARG, "layout must be torch.sparse_csr or torch.sparse_csc")
-        if index_dtype not in (torch.int32, torch.int64):
-            raise B.DsaArgumentError(B.EARG, "index_dtype must be torch.int32 or torch.int64")
-        orientation = ROWMAJOR if layout == torch.sparse_csr else COLMAJOR
-        bits = 32 if index_dtype == torch.int32 else 64
-        dev = torch.device("cuda", torch.cuda.current_device())
-        if isinstance(keys, torch.Tensor):
-            if keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1:
-                raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 CUDA tensor")
-            sel = keys.contiguous()
-        else:
-            sel = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)).to(dev)
+        self._require("mat_select_compressed", "the selected export needs the HIP product library")
+        orientation, index_dtype, bits, dev = self._torch_format(layout, index_dtype)
+        sel = self._torch_keys(keys, dev)
         nsel = sel.numel()
         m, n = self.size()
-        ptr = torch.empty(nsel + 1, dtype=index_dtype, device=dev)
-        # the library works on the orientation's stream: the keys and the fresh blocks must be free of torch's pending work first, and
-        # torch's consumers of the result must start after the selection has finished (the stream discipline of to_torch)
-        torch.cuda.current_stream(dev).synchronize()
-        total, fits = self.select_compressed_dev(orientation, sel.data_ptr(), nsel, ptr.data_ptr(), 0, 0, 0, index_bits=bits)
-        idx = torch.empty(max(total, 1), dtype=index_dtype, device=dev)
-        val = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
-        if not fits:
-            torch.cuda.current_stream(dev).synchronize()
-            total, fits = self.select_compressed_dev(orientation, sel.data_ptr(), nsel, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(),
-                                                     total, index_bits=bits)
-            if not fits:
-                raise B.DsaErrorException(B.ECAP, "the selection grew between the count and the emit")
-        self.sync()
-        idx, val = idx[:total], val[:total]
-        if orientation == ROWMAJOR:
-            return torch.sparse_csr_tensor(ptr, idx, val, size=(nsel, n))
-        return torch.sparse_csc_tensor(ptr, idx, val, size=(m, nsel))
+        arrays = self._torch_arrays(dev, index_dtype, nsel, what="selection", call=lambda d_ptr, d_idx, d_vals, cap: (
+            self.select_compressed_dev(orientation, sel.data_ptr(), nsel, d_ptr, d_idx, d_vals, cap, index_bits=bits)))
+        return self._torch_tensor(orientation, arrays, nsel, n if orientation == ROWMAJOR else m)
 
     # ---- submatrix export (include/dsa.h: dsa_mat_submatrix_compressed[_dev]; HIP library only) ----------------------------------
-    def _require_submatrix(self):
-        if not self.b.has("mat_submatrix_compressed"):
-            raise B.DsaArgumentError(B.EARG, "the submatrix export needs the HIP product library")
-
     def submatrix_compressed_dev(self, orientation, d_outer, nouter, d_inner, ninner, d_ptr, d_idx, d_vals, cap, index_bits=64, base=0):
         """A[inner, outer] as CSC (COLMAJOR: outer = column keys, inner = row keys) / A[outer, inner] as CSR (ROWMAJOR) into device
         memory: d_outer = nouter int64 outer keys (1-based, any order, repeats allowed), d_inner = ninner DISTINCT int64 inner keys
         (1-based, any order), d_ptr = nouter + 1 indices, d_idx / d_vals = cap entries (device addresses; 0 for idx / vals with
         cap = 0: the count-only call).  A delivered cell's index is the position of its key in the inner list + base.  Enqueued on the
         orientation's stream (sync()).  Returns (total, fits) like select_compressed_dev."""
-        self._require_submatrix()
-        got = C.c_int64()
-        try:
-            self.b.call("mat_submatrix_compressed_dev", self.h, int(orientation), int(index_bits), int(base), C.c_void_p(int(d_outer)),
-                        int(nouter), C.c_void_p(int(d_inner)), int(ninner), C.c_void_p(int(d_ptr)), C.c_void_p(int(d_idx)),
-                        C.c_void_p(int(d_vals)), int(cap), C.byref(got))
-        except B.DsaError as e:
-            if e.code == B.ECAP:
-                return got.value, False
-            raise
-        return got.value, True
+        self._require("mat_submatrix_compressed", "the submatrix export needs the HIP product library")
+        return self._fits("mat_submatrix_compressed_dev", int(orientation), int(index_bits), int(base), C.c_void_p(int(d_outer)), int(nouter),
+                          C.c_void_p(int(d_inner)), int(ninner), C.c_void_p(int(d_ptr)), C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)),
+                          int(cap))
 
     @staticmethod
     def _submatrix_sides(rows, cols, layout):
@@ -652,33 +640,13 @@ class DynamicSparseMatrix(_Handle):
         return (ROWMAJOR, rows, cols) if layout == "csr" else (COLMAJOR, cols, rows)
 
     def _submatrix(self, rows, cols, layout, base, count_only=False):
-        self._require_submatrix()
+        self._require("mat_submatrix_compressed", "the submatrix export needs the HIP product library")
         orientation, outer, inner = self._submatrix_sides(rows, cols, layout)
         out, op = _i64(outer)
         inn, ip = _i64(inner)
         if out.ndim != 1 or inn.ndim != 1:
             raise B.DsaArgumentError(B.EARG, "the key lists must be one-dimensional")
-        ptr = np.empty(len(out) + 1, dtype=np.int64)
-        got = C.c_int64()
-        idx = val = None
-        for _ in range(2):              # the count-only call, then the one that fits
-            cap = 0 if idx is None else len(idx)
-            try:
-                self.b.call("mat_submatrix_compressed", self.h, int(orientation), int(base), op, len(out), ip, len(inn),
-                            ptr.ctypes.data_as(P_I64), idx.ctypes.data_as(P_I64) if cap else None,
-                            val.ctypes.data_as(P_F64) if cap else None, cap, C.byref(got))
-            except B.DsaError as e:
-                if e.code != B.ECAP or idx is not None:
-                    raise
-                if count_only:
-                    return ptr, None, None
-                idx = np.empty(got.value, dtype=np.int64)
-                val = np.empty(got.value, dtype=np.float64)
-                continue
-            break
-        if idx is None:
-            idx, val = np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
-        return ptr, idx[:got.value], val[:got.value]
+        return self._two_calls("mat_submatrix_compressed", (int(orientation), int(base), op, len(out), ip, len(inn)), len(out), count_only)
 
     def submatrix(self, rows, cols, layout="csr", base=0):
         """A[rows, cols] as scipy-style arrays (indptr, indices, data) of a len(rows) x len(cols) matrix: CSR (layout "csr": one slice
@@ -694,48 +662,17 @@ class DynamicSparseMatrix(_Handle):
         """A[rows, cols] as torch.sparse_csr_tensor / torch.sparse_csc_tensor of shape (len(rows), len(cols)) on the current device.
         `rows`, `cols`: lists, numpy arrays, or int64 CUDA tensors (used in place); the arrays never leave HBM.  The inner list (cols
         for CSR, rows for CSC) must ascend strictly, because torch expects sorted indices within a slice."""
-        import torch
-        self._require_submatrix()
-        if index_dtype is None:
-            index_dtype = torch.int64
-        if layout not in (torch.sparse_csr, torch.sparse_csc):
-            raise B.DsaArgumentError(B.EARG, "layout must be torch.sparse_csr or torch.sparse_csc")
-        if index_dtype not in (torch.int32, torch.int64):
-            raise B.DsaArgumentError(B.EARG, "index_dtype must be torch.int32 or torch.int64")
-        orientation = ROWMAJOR if layout == torch.sparse_csr else COLMAJOR
-        bits = 32 if index_dtype == torch.int32 else 64
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-        def on_device(keys):
-            if isinstance(keys, torch.Tensor):
-                if keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1:
-                    raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 CUDA tensor")
-                return keys.contiguous()
-            return torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)).to(dev)
-
-        d_rows, d_cols = on_device(rows), on_device(cols)
+        self._require("mat_submatrix_compressed", "the submatrix export needs the HIP product library")
+        orientation, index_dtype, bits, dev = self._torch_format(layout, index_dtype)
+        d_rows, d_cols = self._torch_keys(rows, dev), self._torch_keys(cols, dev)
         outer, inner = (d_rows, d_cols) if orientation == ROWMAJOR else (d_cols, d_rows)
         nouter, ninner = outer.numel(), inner.numel()
         if ninner > 1 and not bool((inner[1:] > inner[:-1]).all()):
             raise B.DsaArgumentError(B.EARG, "the inner key list must ascend strictly (torch expects sorted indices)")
-        ptr = torch.empty(nouter + 1, dtype=index_dtype, device=dev)
-        # the stream discipline of select_torch: the keys and the fresh blocks free of torch's pending work first, torch's consumers
-        # of the result behind the export
-        torch.cuda.current_stream(dev).synchronize()
-        args = (orientation, outer.data_ptr(), nouter, inner.data_ptr(), ninner, ptr.data_ptr())
-        total, fits = self.submatrix_compressed_dev(*args, 0, 0, 0, index_bits=bits)
-        idx = torch.empty(max(total, 1), dtype=index_dtype, device=dev)
-        val = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
-        if not fits:
-            torch.cuda.current_stream(dev).synchronize()
-            total, fits = self.submatrix_compressed_dev(*args, idx.data_ptr(), val.data_ptr(), total, index_bits=bits)
-            if not fits:
-                raise B.DsaErrorException(B.ECAP, "the submatrix grew between the count and the emit")
-        self.sync()
-        idx, val = idx[:total], val[:total]
-        if orientation == ROWMAJOR:
-            return torch.sparse_csr_tensor(ptr, idx, val, size=(nouter, ninner))
-        return torch.sparse_csc_tensor(ptr, idx, val, size=(ninner, nouter))
+        arrays = self._torch_arrays(dev, index_dtype, nouter, what="submatrix", call=lambda d_ptr, d_idx, d_vals, cap: (
+            self.submatrix_compressed_dev(orientation, outer.data_ptr(), nouter, inner.data_ptr(), ninner, d_ptr, d_idx, d_vals, cap,
+                                          index_bits=bits)))
+        return self._torch_tensor(orientation, arrays, nouter, ninner)
 
     def check(self, orientation):
         """device-side invariant checker (HIP library only): report[2..6] must be 0."""
@@ -804,17 +741,13 @@ class DynamicSparseMatrix(_Handle):
                     C.c_void_p(int(d_yi)), C.c_void_p(int(d_yv)), int(cap), C.c_void_p(int(d_count)))
 
     # ---- dense multi-vector product (include/dsa.h: dsa_mat_spmm_dense[_dev]; HIP library only) ------------------------------------
-    def _require_spmm(self):
-        if not self.b.has("mat_spmm_dense"):
-            raise B.DsaArgumentError(B.EARG, "the multi-vector product needs the HIP product library")
-
     def matmul(self, X, transpose=False):
         """mat * X / transpose(mat) * X for k right-hand sides: column j of the result is mul(X[:, j]).
 
         A 2-D float64 numpy array returns a new (size(mat, 1 | 2), k) array; a 2-D float64 torch tensor on the GPU returns a new
         tensor on the same device (the operands never leave HBM); a 1-D input returns the 1-D product.  Inputs that are not
         row-contiguous are copied into that form first."""
-        self._require_spmm()
+        self._require("mat_spmm_dense", "the multi-vector product needs the HIP product library")
         tr = 1 if transpose else 0
         m, n = self.size()
         ny = n if transpose else m
@@ -854,15 +787,11 @@ class DynamicSparseMatrix(_Handle):
     def matmul_dev(self, d_x, nx, k, d_y, ny, ldx=None, ldy=None, transpose=False):
         """the multi-vector product with both operands in HBM (device addresses, e.g. tensor.data_ptr()), row-major with leading
         dimensions ldx / ldy (default k); stream-ordered on the orientation's stream, no host wait (sync())"""
-        self._require_spmm()
+        self._require("mat_spmm_dense", "the multi-vector product needs the HIP product library")
         self.b.call("mat_spmm_dense_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_x)), int(nx), int(k),
                     int(k if ldx is None else ldx), C.c_void_p(int(d_y)), int(ny), int(k if ldy is None else ldy))
 
     # ---- selected-key product (include/dsa.h: dsa_mat_spmm_selected[_dev]; HIP library only) -------------------------------------
-    def _require_selprod(self):
-        if not self.b.has("mat_spmm_selected"):
-            raise B.DsaArgumentError(B.EARG, "the selected-key product needs the HIP product library")
-
     def matmul_selected(self, keys, X, transpose=False):
         """mat[keys, :] * X / mat[:, keys]' * X (transpose=True): row j of the result is row keys[j] - 1 of matmul(X), bit for bit, at a
         cost that follows the selected rows / columns only.  Keys are 1-based, in any order, repeats allowed; a key that owns no row /
@@ -871,7 +800,7 @@ class DynamicSparseMatrix(_Handle):
         A float64 numpy X takes a list or array of keys and returns a new (len(keys), k) array.  A float64 torch tensor on the GPU
         takes a list, an array, or an int64 CUDA tensor (used in place) and returns a new tensor on the same device (nothing leaves
         HBM).  A 1-D X returns the 1-D product.  Inputs that are not row-contiguous are handled as in matmul."""
-        self._require_selprod()
+        self._require("mat_spmm_selected", "the selected-key product needs the HIP product library")
         tr = 1 if transpose else 0
         if isinstance(X, np.ndarray):
             sel, sp = _i64(keys)
@@ -917,14 +846,13 @@ class DynamicSparseMatrix(_Handle):
         """the selected-key product with keys (nsel int64) and both operands in HBM (device addresses, e.g. tensor.data_ptr()), X and
         Y row-major with leading dimensions ldx / ldy (default k); stream-ordered on the orientation's stream, no host wait (sync()).
         A key without a row / column (0 and negative keys included) gives a zero row: nothing is reported."""
-        self._require_selprod()
+        self._require("mat_spmm_selected", "the selected-key product needs the HIP product library")
         self.b.call("mat_spmm_selected_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_sel)), int(nsel), C.c_void_p(int(d_x)),
                     int(nx), int(k), int(k if ldx is None else ldx), C.c_void_p(int(d_y)), int(k if ldy is None else ldy))
 
     # ---- batched sparse-x product (include/dsa.h: dsa_mat_spgemm_csc[_dev]; HIP library only) ---------------------------------------
     def _require_spgemm(self):
-        if not self.b.has("mat_spgemm_csc"):
-            raise B.DsaArgumentError(B.EARG, "the batched sparse-x product needs the HIP product library")
+        self._require("mat_spgemm_csc", "the batched sparse-x product needs the HIP product library")
 
     def matmul_sparse_dev(self, d_xptr, d_xidx, d_xval, k, nnzx, d_yptr, d_yidx, d_yval, cap, index_bits=64, base=0, transpose=False):
         """mat * S / transpose(mat) * S for k sparse columns, S and the result CSC in device memory (device addresses, e.g.
@@ -933,16 +861,9 @@ class DynamicSparseMatrix(_Handle):
         is mul() of column j of S, bit for bit.  Enqueued on the stream of the orientation that is walked (sync()).  Returns
         (total, fits) like select_compressed_dev: with fits False (cap < total) only yptr has been written."""
         self._require_spgemm()
-        got = C.c_int64()
-        try:
-            self.b.call("mat_spgemm_csc_dev", self.h, 1 if transpose else 0, int(index_bits), int(base), C.c_void_p(int(d_xptr)),
-                        C.c_void_p(int(d_xidx)), C.c_void_p(int(d_xval)), int(k), int(nnzx), C.c_void_p(int(d_yptr)),
-                        C.c_void_p(int(d_yidx)), C.c_void_p(int(d_yval)), int(cap), C.byref(got))
-        except B.DsaError as e:
-            if e.code == B.ECAP:
-                return got.value, False
-            raise
-        return got.value, True
+        return self._fits("mat_spgemm_csc_dev", 1 if transpose else 0, int(index_bits), int(base), C.c_void_p(int(d_xptr)),
+                          C.c_void_p(int(d_xidx)), C.c_void_p(int(d_xval)), int(k), int(nnzx), C.c_void_p(int(d_yptr)),
+                          C.c_void_p(int(d_yidx)), C.c_void_p(int(d_yval)), int(cap))
 
     def matmul_sparse(self, S, transpose=False, base=0):
         """mat * S / transpose(mat) * S for a sparse S with k columns: column j of the result is mul() of column j of S (the touched
@@ -1015,12 +936,8 @@ class DynamicSparseMatrix(_Handle):
     # ---- reductions per row / column and in-place scaling (include/dsa.h: dsa_mat_reduce[_dev], dsa_mat_scale[_dev]; HIP library only)
     RED_KINDS = {"sum": 0, "abssum": 1, "sqsum": 2, "absmax": 3, "count": 4}
 
-    def _require_scale(self):
-        if not self.b.has("mat_reduce"):
-            raise B.DsaArgumentError(B.EARG, "reduce and scale need the HIP product library")
-
     def _reduce_args(self, kind, per):
-        self._require_scale()
+        self._require("mat_reduce", "reduce and scale need the HIP product library")
         if kind not in self.RED_KINDS:
             raise B.DsaArgumentError(B.EARG, "kind must be one of %s" % ", ".join(sorted(self.RED_KINDS)))
         if per not in ("row", "column"):
@@ -1075,7 +992,7 @@ class DynamicSparseMatrix(_Handle):
         """A <- diag(rows) * (alpha * A) * diag(cols) in place: every stored value v becomes ((v * alpha) * rows[i]) * cols[j].
         Structure is preserved: a zero factor leaves stored zeros (nnz unchanged).  rows / cols: numpy arrays (or sequences), or
         float64 tensors on the GPU (any stride; made contiguous first) — both of the same kind; None = factor absent."""
-        self._require_scale()
+        self._require("mat_reduce", "reduce and scale need the HIP product library")
         ops = [x for x in (rows, cols) if x is not None]
         is_t = [type(x).__module__.split(".")[0] == "torch" for x in ops]
         if any(is_t):
@@ -1108,7 +1025,7 @@ class DynamicSparseMatrix(_Handle):
     def scale_dev(self, alpha, d_r, nr, d_c, nc):
         """scale with the factors in HBM (device addresses, 0 = factor absent): they are read on both orientations' streams and
         must stay valid and unchanged until sync()"""
-        self._require_scale()
+        self._require("mat_reduce", "reduce and scale need the HIP product library")
         self.b.call("mat_scale_dev", self.h, float(alpha), C.c_void_p(int(d_r)) if d_r else None, int(nr),
                     C.c_void_p(int(d_c)) if d_c else None, int(nc))
 

@@ -1,10 +1,13 @@
 // csrc/export_dev.h — what the export kernel units share (compress.hip: the whole orientation, select.hip: the partitions of
 // a key list, submatrix.hip: those partitions restricted to an inner key list): the tile they cut the slot array into, the block
-// scan between their count and emit launches, the span of an outer key (select.hip, submatrix.hip) and the end of an emit kernel.
-// Device code only.
+// scan between their count and emit launches, and the ends of a scan and of an emit kernel.  For the two key-list exports also the
+// whole work-item pipeline: the span kernel of the outer keys (k_key_spans), the owner of a work item (item_past, item_owner), its part of the
+// span and its bitmap words (span_chunk, chunk_word), the grid of the item kernels (ex_grid) and the choice of an emit instantiation (dispatch_wide_it).
+// Device code, and the two host helpers of its launches.
 #pragma once
 #include "wave_dev.h"
 #include "find_dev.h"
+#include <type_traits>
 
 namespace dsa {
 
@@ -13,6 +16,25 @@ constexpr int64_t EX_TILE = int64_t(1) << EX_TILE_SHIFT;
 constexpr int EX_WORDS = (int)(EX_TILE >> 6);
 constexpr int EX_U = 8;                                  // bitmap words whose keys and values a wave requests at once
 constexpr int EX_SCAN_THREADS = 1024;
+constexpr int64_t EX_BLOCKS_MAX = 4096;                  // grid cap of the work-item kernels: beyond it a thread or wave strides over several
+                                                         // units (one ticket per workgroup at the end of an emit: a million of them on one
+                                                         // address cost more than the cells)
+static inline unsigned ex_grid(int64_t units, int64_t per_block) {
+    const int64_t blocks = (units + per_block - 1) / per_block;
+    return (unsigned)(blocks < EX_BLOCKS_MAX ? blocks : EX_BLOCKS_MAX);
+}
+
+// f(std::bool_constant<WIDE>, IT()) for the key width of the slot array and the caller's index type: the emit kernels are <WIDE, IT>
+template <typename F>
+static inline void dispatch_wide_it(bool wide, int32_t index_bits, F f) {
+    if (wide) {
+        if (index_bits == 32) f(std::true_type(), int32_t());
+        else f(std::true_type(), int64_t());
+    } else {
+        if (index_bits == 32) f(std::false_type(), int32_t());
+        else f(std::false_type(), int64_t());
+    }
+}
 
 // One workgroup of EX_SCAN_THREADS: exclusive prefixes of a[0..n) and b[0..n), 8192 entries per step, the sums of the steps in
 // front carried along.  put(i, pa, pb) gets the two prefixes of entry i (it may overwrite a[i] and b[i]); the totals come back in
@@ -92,6 +114,76 @@ __device__ __forceinline__ KeySpan key_span(int64_t capacity, const int64_t* __r
     return r;
 }
 
+// One wave per outer key (4 per workgroup): span j = [lo[j], hi[j]), chunks[j] = 2048-slot tiles of the slot array it touches (0 for a
+// span without cells), with CELLS cells[j] = its occupied slots; the error bits of key_span are ORed into *err.
+template <bool CELLS>
+__global__ __launch_bounds__(256) void k_key_spans(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
+                                                   const int64_t* __restrict__ col_keys, const uint8_t* __restrict__ col_live,
+                                                   int64_t table_len, bool dense, const int64_t* __restrict__ keys, int64_t nkeys,
+                                                   int64_t dim_out, int64_t* lo, int64_t* hi, int64_t* chunks, int64_t* cells, uint32_t* err) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t j = (int64_t)blockIdx.x * 4 + wv;
+    if (j >= nkeys) return;
+    const KeySpan sp = key_span(capacity, sems, col_keys, col_live, table_len, dense, keys[j], dim_out, lane);
+    const int64_t cnt = sp.hi > sp.lo ? sel_span_popc(occ, sp.lo, sp.hi, lane) : 0;
+    if (lane != 0) return;
+    lo[j] = sp.lo; hi[j] = sp.hi;
+    if (CELLS) cells[j] = cnt;
+    chunks[j] = cnt > 0 ? ((sp.hi - 1) >> EX_TILE_SHIFT) - (sp.lo >> EX_TILE_SHIFT) + 1 : 0;
+    if (sp.err) atomicOr(err, sp.err);
+}
+
+// The first key whose item prefix choff[j] exceeds w (n if there is none).  A 64-ary search, one probe per lane and round: prefixes in
+// front of L are <= w, the one at H is > w (or H = n).
+__device__ __forceinline__ int64_t item_past(const int64_t* __restrict__ choff, int64_t n, int64_t w, int lane) {
+    int64_t L = 0, H = n;
+    while (H - L > 64) {
+        const int64_t width = H - L;
+        const int64_t p = L + (width * (lane + 1)) / 64;         // ascending with the lane, lane 63 probes H
+        const bool le = p < n && choff[p] <= w;
+        const uint64_t nb = ~__ballot(le);
+        const int f = nb ? __ffsll((unsigned long long)nb) - 1 : 63;
+        H = L + (width * (f + 1)) / 64;
+        if (f > 0) L = L + (width * f) / 64 + 1;
+    }
+    const bool le = L + lane <= H && L + lane < n && choff[L + lane] <= w;
+    const uint64_t nb = ~__ballot(le);
+    return L + (nb ? __ffsll((unsigned long long)nb) - 1 : 64);
+}
+// The key that owns work item w: the one in front of item_past (-1 if there is none; choff[0] = 0).  k_sel_emit subtracts the one
+// itself: that is the form for which the compiler gives it the instructions of the search it had inline.
+__device__ __forceinline__ int64_t item_owner(const int64_t* __restrict__ choff, int64_t n, int64_t w, int lane) {
+    return item_past(choff, n, w, lane) - 1;
+}
+
+// the part of span [lo, hi) that lies in tile `tile` of the slot array: slots [cs, ce) (ce <= cs: none, the tile is not the span's);
+// w0 = the first bitmap word of the tile
+struct SpanChunk { int64_t cs, ce, w0; };
+__device__ __forceinline__ SpanChunk span_chunk(int64_t lo, int64_t hi, int64_t tile) {
+    const int64_t t0 = tile << EX_TILE_SHIFT;
+    return SpanChunk{lo > t0 ? lo : t0, hi < t0 + EX_TILE ? hi : t0 + EX_TILE, tile * EX_WORDS};
+}
+// this lane's bitmap word of the chunk's tile masked to [cs, ce) (0 for a chunk without slots); nz = the words with a cell (a short
+// span leaves most groups of a chunk empty)
+__device__ __forceinline__ uint64_t chunk_word(const uint64_t* __restrict__ occ, const SpanChunk& c, int lane, uint32_t& nz) {
+    uint64_t myword = 0ull;
+    if (c.ce > c.cs && lane < EX_WORDS && ((c.w0 + lane) << 6) < c.ce) myword = occ[c.w0 + lane] & word_range_mask(c.w0 + lane, c.cs, c.ce - 1);
+    nz = (uint32_t)__ballot(myword != 0ull);
+    return myword;
+}
+
+// The hand-over at the end of a scan or emit kernel (one thread).  The pinned words by n, the number of totals the host expects:
+//   n = 0  {error word, seq}     n = 1  {error word, t0, seq}     n = 2  {error word, t0, t1, seq}
+// n must be the literal the host side's wait_handover(pin + n + 1) goes with: seq lands behind the totals.
+__device__ __forceinline__ void hand_over(const uint32_t* err_word, unsigned long long* pinned, unsigned long long seq, int n = 0,
+                                          unsigned long long t0 = 0, unsigned long long t1 = 0) {
+    const uint32_t e = __hip_atomic_load(err_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (n > 0) __hip_atomic_store(pinned + 1, t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (n > 1) __hip_atomic_store(pinned + 2, t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_seq(pinned + n + 1, seq);
+}
+
 // The end of an emit kernel (256 threads, every one arrives): the error bits of the workgroup go into the scratch word, and the
 // workgroup that takes the last ticket hands {error word, seq} to pinned memory.
 __device__ __forceinline__ void emit_epilogue(uint32_t err, int lane, int wv, uint32_t* err_word, uint32_t* ticket,
@@ -106,10 +198,7 @@ __device__ __forceinline__ void emit_epilogue(uint32_t err, int lane, int wv, ui
     __builtin_amdgcn_s_waitcnt(0);
     const uint32_t tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (tk != gridDim.x - 1) return;
-    // the last workgroup: every other one has added its bits before taking its ticket
-    const uint32_t e = __hip_atomic_load(err_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    publish_seq(pinned + 1, seq);
+    hand_over(err_word, pinned, seq);                            // the last workgroup: every other one has added its bits before its ticket
 }
 
 }  // namespace dsa

@@ -78,11 +78,56 @@ void compress_side(const Side& e, int32_t index_bits, int32_t index_base, void* 
     export_verdict(A.pin, "compressed export", "a stored entry lies outside size(m)");
 }
 
-// ---- the partitions of a key list
-struct SelTotals { int64_t total = 0, items = 0; };
+// ---- the key-list exports: what the count phase of either leaves for its emit
+struct KeyTotals { int64_t total = 0, items = 0; };       // cells to deliver, 2048-slot work items
 
+// The shape of a key-list export into device memory: count(e) completes ptr and gives the totals, DSA_ECAP if the cells do not fit,
+// else emit(e, totals).
+template <typename Count, typename Emit>
+void keylist_dev(dsa_mat* h, int32_t o, const void* d_idx, const double* d_vals, int64_t cap, Count count, Emit emit) {
+    if (cap < 0) fail(DSA_EARG, "negative capacity");
+    if (cap > 0 && (!d_idx || !d_vals)) fail(DSA_EARG, "output pointer is NULL");
+    const Side e = export_side(h, o);
+    const KeyTotals t = count(e);
+    if (cap < t.total) fail(DSA_ECAP, "output buffers too small");
+    emit(e, t);
+}
+
+// The shape of a key-list export into host memory, 64-bit indices: the keys staged in one block (the outer list, then the inner list
+// if there is one), count(d_outer, d_inner, d_ptr), ptr down, DSA_ECAP if the cells do not fit, else idx / vals allocated,
+// emit(totals, d_idx, d_vals) and both down.
+template <typename Count, typename Emit>
+void keylist_host(const Side& e, const int64_t* outer, int64_t nouter, const int64_t* inner, int64_t ninner, int64_t* ptr, int64_t* idx,
+                  double* vals, int64_t cap, Count count, Emit emit) {
+    Pma& S = e.P;
+    DevStaging b(S.stream);
+    const size_t kb = (size_t)std::max<int64_t>(nouter + ninner, 1) * sizeof(int64_t), pb = (size_t)(nouter + 1) * sizeof(int64_t);
+    HIPCHK(pool_alloc(&b.p[0], kb));
+    HIPCHK(pool_alloc(&b.p[1], pb));
+    int64_t* d_outer = static_cast<int64_t*>(b.p[0]);
+    int64_t* d_inner = d_outer + nouter;
+    if (nouter > 0) HIPCHK(hipMemcpyAsync(d_outer, outer, (size_t)nouter * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
+    if (ninner > 0) HIPCHK(hipMemcpyAsync(d_inner, inner, (size_t)ninner * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
+    const KeyTotals t = count(d_outer, d_inner, b.p[1]);
+    HIPCHK(hipMemcpyAsync(ptr, b.p[1], pb, hipMemcpyDeviceToHost, S.stream));
+    if (cap < t.total) {
+        HIPCHK(hipStreamSynchronize(S.stream));      // ptr is the caller's to read with DSA_ECAP
+        fail(DSA_ECAP, "output buffers too small");
+    }
+    if (t.total > 0) {
+        const size_t cb = (size_t)t.total * sizeof(int64_t);
+        HIPCHK(pool_alloc(&b.p[2], cb));
+        HIPCHK(pool_alloc(&b.p[3], cb));
+        emit(t, b.p[2], static_cast<double*>(b.p[3]));
+        HIPCHK(hipMemcpyAsync(idx, b.p[2], cb, hipMemcpyDeviceToHost, S.stream));
+        HIPCHK(hipMemcpyAsync(vals, b.p[3], cb, hipMemcpyDeviceToHost, S.stream));
+    }
+    HIPCHK(hipStreamSynchronize(S.stream));
+}
+
+// ---- the partitions of a key list
 // argument checks, count + scan, the first wait.  ptr is complete when this returns; *nnz_out = cells selected.
-SelTotals select_count(const Side& e, int32_t index_bits, int32_t index_base, const int64_t* d_sel, int64_t nsel, void* d_ptr,
+KeyTotals select_count(const Side& e, int32_t index_bits, int32_t index_base, const int64_t* d_sel, int64_t nsel, void* d_ptr,
                        int64_t* nnz_out) {
     Pma& P = e.P;
     if (!nnz_out) fail(DSA_EARG, "nnz_out is NULL");
@@ -101,7 +146,7 @@ SelTotals select_count(const Side& e, int32_t index_bits, int32_t index_base, co
                                                           d_ptr, A.scratch, A.pin, seq, P.stream));
     wait_handover(P, A.pin + 3, seq, "selected export (count)");
     export_verdict(A.pin, "selected export", "a selected key lies outside size(m)");
-    SelTotals t;
+    KeyTotals t;
     t.total = (int64_t)A.pin[1]; t.items = (int64_t)A.pin[2];
     *nnz_out = t.total;
     if (index_bits == 32 && t.total + index_base > INT32_MAX) fail(DSA_EARG, "the selected cells do not fit 32-bit indices");
@@ -109,7 +154,7 @@ SelTotals select_count(const Side& e, int32_t index_bits, int32_t index_base, co
 }
 
 // the emit on the scratch select_count left, and the second wait
-void select_emit(const Side& e, const SelTotals& t, int32_t index_bits, int32_t index_base, int64_t nsel, void* d_idx, double* d_vals) {
+void select_emit(const Side& e, const KeyTotals& t, int32_t index_bits, int32_t index_base, int64_t nsel, void* d_idx, double* d_vals) {
     if (t.total <= 0) return;
     if (t.items <= 0) fail(DSA_EASSERT, "selected export: cells without a work item");
     Pma& P = e.P;
@@ -122,7 +167,6 @@ void select_emit(const Side& e, const SelTotals& t, int32_t index_bits, int32_t 
 }
 
 // ---- the partitions of an outer key list, restricted to and renumbered by an inner key list
-struct SubTotals { int64_t total = 0, items = 0; };
 
 // the error word a submatrix kernel handed over (submatrix.h lists the bits)
 void submatrix_verdict(const unsigned long long* word) {
@@ -136,7 +180,7 @@ void submatrix_verdict(const unsigned long long* word) {
 
 // argument checks, the key phase, the first wait (work items), the count phase, the second wait (kept cells).  ptr is complete
 // when this returns; *nnz_out = cells kept.
-SubTotals submatrix_count(const Side& e, int32_t index_bits, int32_t index_base, const int64_t* d_outer, int64_t nouter,
+KeyTotals submatrix_count(const Side& e, int32_t index_bits, int32_t index_base, const int64_t* d_outer, int64_t nouter,
                           const int64_t* d_inner, int64_t ninner, void* d_ptr, int64_t* nnz_out) {
     Pma& P = e.P;
     if (!nnz_out) fail(DSA_EARG, "nnz_out is NULL");
@@ -157,7 +201,7 @@ SubTotals submatrix_count(const Side& e, int32_t index_bits, int32_t index_base,
                                                             e.dim_in, A.scratch, A.pin, seq, P.stream));
     wait_handover(P, A.pin + 2, seq, "submatrix export (keys)");
     submatrix_verdict(A.pin);
-    SubTotals t;
+    KeyTotals t;
     t.items = (int64_t)A.pin[1];
     I.ensure(P.stream, submatrix_item_scratch_bytes(t.items), 1);
     seq = A.next();
@@ -172,7 +216,7 @@ SubTotals submatrix_count(const Side& e, int32_t index_bits, int32_t index_base,
 }
 
 // the emit on the scratch submatrix_count left, and the third wait
-void submatrix_emit(const Side& e, const SubTotals& t, int32_t index_bits, int32_t index_base, int64_t nouter, int64_t ninner, void* d_idx,
+void submatrix_emit(const Side& e, const KeyTotals& t, int32_t index_bits, int32_t index_base, int64_t nouter, int64_t ninner, void* d_idx,
                     double* d_vals) {
     if (t.total <= 0) return;
     if (t.items <= 0) fail(DSA_EASSERT, "submatrix export: cells without a work item");
@@ -218,12 +262,9 @@ void to_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, int64_t* ptr,
 
 void select_compressed_dev(dsa_mat* h, int32_t o, int32_t index_bits, int32_t index_base, const int64_t* d_sel, int64_t nsel,
                            void* d_ptr, void* d_idx, double* d_vals, int64_t cap, int64_t* nnz_out) {
-    if (cap < 0) fail(DSA_EARG, "negative capacity");
-    if (cap > 0 && (!d_idx || !d_vals)) fail(DSA_EARG, "output pointer is NULL");
-    const Side e = export_side(h, o);
-    const SelTotals t = select_count(e, index_bits, index_base, d_sel, nsel, d_ptr, nnz_out);
-    if (cap < t.total) fail(DSA_ECAP, "output buffers too small");
-    select_emit(e, t, index_bits, index_base, nsel, d_idx, d_vals);
+    keylist_dev(h, o, d_idx, d_vals, cap,
+                [&](const Side& e) { return select_count(e, index_bits, index_base, d_sel, nsel, d_ptr, nnz_out); },
+                [&](const Side& e, const KeyTotals& t) { select_emit(e, t, index_bits, index_base, nsel, d_idx, d_vals); });
 }
 
 void select_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, const int64_t* sel, int64_t nsel, int64_t* ptr, int64_t* idx,
@@ -233,38 +274,17 @@ void select_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, const int
     if (cap > 0 && (!idx || !vals)) fail(DSA_EARG, "output pointer is NULL");
     if (nsel < 0 || nsel > INT32_MAX) fail(DSA_EARG, "nsel must lie in 0 .. 2^31 - 1");
     const Side e = export_side(h, o);
-    Pma& S = e.P;
-    DevStaging b(S.stream);
-    const size_t sb = (size_t)std::max<int64_t>(nsel, 1) * sizeof(int64_t), pb = (size_t)(nsel + 1) * sizeof(int64_t);
-    HIPCHK(pool_alloc(&b.p[0], sb));
-    HIPCHK(pool_alloc(&b.p[1], pb));
-    if (nsel > 0) HIPCHK(hipMemcpyAsync(b.p[0], sel, (size_t)nsel * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
-    const SelTotals t = select_count(e, 64, index_base, static_cast<const int64_t*>(b.p[0]), nsel, b.p[1], nnz_out);
-    HIPCHK(hipMemcpyAsync(ptr, b.p[1], pb, hipMemcpyDeviceToHost, S.stream));
-    if (cap < t.total) {
-        HIPCHK(hipStreamSynchronize(S.stream));      // ptr is the caller's to read with DSA_ECAP
-        fail(DSA_ECAP, "output buffers too small");
-    }
-    if (t.total > 0) {
-        const size_t cb = (size_t)t.total * sizeof(int64_t);
-        HIPCHK(pool_alloc(&b.p[2], cb));
-        HIPCHK(pool_alloc(&b.p[3], cb));
-        select_emit(e, t, 64, index_base, nsel, b.p[2], static_cast<double*>(b.p[3]));
-        HIPCHK(hipMemcpyAsync(idx, b.p[2], cb, hipMemcpyDeviceToHost, S.stream));
-        HIPCHK(hipMemcpyAsync(vals, b.p[3], cb, hipMemcpyDeviceToHost, S.stream));
-    }
-    HIPCHK(hipStreamSynchronize(S.stream));
+    keylist_host(e, sel, nsel, nullptr, 0, ptr, idx, vals, cap,
+                 [&](const int64_t* d_sel, const int64_t*, void* d_ptr) { return select_count(e, 64, index_base, d_sel, nsel, d_ptr, nnz_out); },
+                 [&](const KeyTotals& t, void* d_idx, double* d_vals) { select_emit(e, t, 64, index_base, nsel, d_idx, d_vals); });
 }
 
 void submatrix_compressed_dev(dsa_mat* h, int32_t o, int32_t index_bits, int32_t index_base, const int64_t* d_outer, int64_t nouter,
                               const int64_t* d_inner, int64_t ninner, void* d_ptr, void* d_idx, double* d_vals, int64_t cap,
                               int64_t* nnz_out) {
-    if (cap < 0) fail(DSA_EARG, "negative capacity");
-    if (cap > 0 && (!d_idx || !d_vals)) fail(DSA_EARG, "output pointer is NULL");
-    const Side e = export_side(h, o);
-    const SubTotals t = submatrix_count(e, index_bits, index_base, d_outer, nouter, d_inner, ninner, d_ptr, nnz_out);
-    if (cap < t.total) fail(DSA_ECAP, "output buffers too small");
-    submatrix_emit(e, t, index_bits, index_base, nouter, ninner, d_idx, d_vals);
+    keylist_dev(h, o, d_idx, d_vals, cap,
+                [&](const Side& e) { return submatrix_count(e, index_bits, index_base, d_outer, nouter, d_inner, ninner, d_ptr, nnz_out); },
+                [&](const Side& e, const KeyTotals& t) { submatrix_emit(e, t, index_bits, index_base, nouter, ninner, d_idx, d_vals); });
 }
 
 void submatrix_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, const int64_t* outer, int64_t nouter, const int64_t* inner,
@@ -275,31 +295,11 @@ void submatrix_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, const 
     if (nouter < 0 || nouter > INT32_MAX) fail(DSA_EARG, "nouter must lie in 0 .. 2^31 - 1");
     if (ninner < 0 || ninner > INT32_MAX) fail(DSA_EARG, "ninner must lie in 0 .. 2^31 - 1");
     const Side e = export_side(h, o);
-    Pma& S = e.P;
-    DevStaging b(S.stream);
-    // block 0: the outer keys, then the inner keys
-    const size_t kb = (size_t)std::max<int64_t>(nouter + ninner, 1) * sizeof(int64_t), pb = (size_t)(nouter + 1) * sizeof(int64_t);
-    HIPCHK(pool_alloc(&b.p[0], kb));
-    HIPCHK(pool_alloc(&b.p[1], pb));
-    int64_t* d_outer = static_cast<int64_t*>(b.p[0]);
-    int64_t* d_inner = d_outer + nouter;
-    if (nouter > 0) HIPCHK(hipMemcpyAsync(d_outer, outer, (size_t)nouter * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
-    if (ninner > 0) HIPCHK(hipMemcpyAsync(d_inner, inner, (size_t)ninner * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
-    const SubTotals t = submatrix_count(e, 64, index_base, d_outer, nouter, d_inner, ninner, b.p[1], nnz_out);
-    HIPCHK(hipMemcpyAsync(ptr, b.p[1], pb, hipMemcpyDeviceToHost, S.stream));
-    if (cap < t.total) {
-        HIPCHK(hipStreamSynchronize(S.stream));      // ptr is the caller's to read with DSA_ECAP
-        fail(DSA_ECAP, "output buffers too small");
-    }
-    if (t.total > 0) {
-        const size_t cb = (size_t)t.total * sizeof(int64_t);
-        HIPCHK(pool_alloc(&b.p[2], cb));
-        HIPCHK(pool_alloc(&b.p[3], cb));
-        submatrix_emit(e, t, 64, index_base, nouter, ninner, b.p[2], static_cast<double*>(b.p[3]));
-        HIPCHK(hipMemcpyAsync(idx, b.p[2], cb, hipMemcpyDeviceToHost, S.stream));
-        HIPCHK(hipMemcpyAsync(vals, b.p[3], cb, hipMemcpyDeviceToHost, S.stream));
-    }
-    HIPCHK(hipStreamSynchronize(S.stream));
+    keylist_host(e, outer, nouter, inner, ninner, ptr, idx, vals, cap,
+                 [&](const int64_t* d_outer, const int64_t* d_inner, void* d_ptr) {
+                     return submatrix_count(e, 64, index_base, d_outer, nouter, d_inner, ninner, d_ptr, nnz_out);
+                 },
+                 [&](const KeyTotals& t, void* d_idx, double* d_vals) { submatrix_emit(e, t, 64, index_base, nouter, ninner, d_idx, d_vals); });
 }
 
 }  // namespace host

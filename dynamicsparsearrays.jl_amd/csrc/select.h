@@ -8,7 +8,7 @@ namespace dsa {
 // scratch of a selection of nsel keys (pooled, nothing to initialise)
 size_t select_scratch_bytes(int64_t nsel);
 
-// Phase 1 (k_sel_count, k_sel_scan): looks the keys up, writes ptr[nsel + 1] (index_bits 32 | 64, ptr[j] = base + cells of the
+// Phase 1 (k_key_spans of export_dev.h, k_sel_scan): looks the keys up, writes ptr[nsel + 1] (index_bits 32 | 64, ptr[j] = base + cells of the
 // selections in front of j) and hands {error bits, cells in all, work items of the emit} and then `seq` to pinned4.  Error bits:
 // 1 a selected key outside 1..dim_out, 2 tables and slots out of step.
 hipError_t launch_select_count(const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,

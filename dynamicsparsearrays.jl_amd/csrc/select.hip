@@ -4,7 +4,7 @@
 // The j-th outer slice of the result is the live partition whose key is sel[j] (any order, repeats allowed; a key without a live
 // partition gives an empty slice).  The cells of a partition are the occupied slots strictly between its semaphore and the next live
 // semaphore (the end of the slot array behind the last one): its SPAN.  Three launches, two host waits:
-//   k_sel_count  one wave per selected key: range check, wave-parallel table search (find_dev.h), the span (tombstoned table entries
+//   k_key_spans  one wave per selected key: range check, wave-parallel table search (find_dev.h), the span (tombstoned table entries
 //                behind the partition are skipped 64 at a time), cnt[j] = popcount of the span's bitmap words,
 //                nchunk[j] = 2048-slot tiles of the slot array the span touches (0 for a span without cells)
 //   k_sel_scan   one workgroup: exclusive prefixes of cnt (-> ptr in the caller's index type, and off[] for the emit) and of nchunk
@@ -17,24 +17,22 @@
 // No wave owns a whole long partition: a span is cut at the tile boundaries of the slot array, whatever its length.  No atomics on
 // the output, no floating-point arithmetic (values are copied bit for bit).  The count phase relies on popcounts only, so every cell
 // of a selected partition is delivered; inner-index selection and renumbering (A[I, J] with both lists) is the submatrix export
-// (submatrix.hip, dsa_mat_submatrix_compressed[_dev]), which shares the span lookup of k_sel_count (export_dev.h: key_span).
+// (submatrix.hip, dsa_mat_submatrix_compressed[_dev]).  It runs the same work-item pipeline, so what the two have in common is in
+// export_dev.h: the span kernel (k_key_spans), the search for the owner of a work item (item_past, item_owner), the part of the span a work item
+// covers (span_chunk, chunk_word), the hand-over at the end of a scan (hand_over), the emit grid (ex_grid) and the choice of <WIDE, IT>.
 // Bytes in: 8 * nsel selection keys, about 8 * log2(table_len) probed table bytes per key, (kb + 8) per slot of the selected spans,
 // their bitmap words twice (count and emit; the emit reads the words in front of a chunk once more to place it: for a span of c
 // chunks c / 2 times its bitmap, 1/64 of the slot bytes per pass).  Bytes out: (ib + 8) * total + ib * (nsel + 1).  Nothing is
 // proportional to the capacity.
 #include "select.h"
 #include "export_dev.h"
-#include <type_traits>
 
 namespace dsa {
-
-constexpr int64_t SEL_EMIT_BLOCKS_MAX = 4096;            // emit grid: beyond 16384 work items a wave strides over several (one ticket per
-                                                         // workgroup at the end: a million of them on one address cost more than the cells)
 
 // scratch: four arrays of nsel entries, then the error word and the ticket of the emit (one 8-byte memset)
 struct SelScratch {
     int64_t* lo; int64_t* hi;                            // span of selection j: slots [lo, hi), 0-based
-    int64_t* off;                                        // cells (k_sel_count), then their exclusive prefix (k_sel_scan)
+    int64_t* off;                                        // cells (k_key_spans), then their exclusive prefix (k_sel_scan)
     int64_t* choff;                                      // chunks, then their exclusive prefix
     uint32_t* err; uint32_t* ticket;
 };
@@ -50,25 +48,6 @@ static SelScratch sel_carve(void* base, int64_t nsel) {
 }
 size_t select_scratch_bytes(int64_t nsel) { return (size_t)(nsel > 0 ? nsel : 0) * 32 + 8; }
 
-// one wave per selected key
-__global__ __launch_bounds__(256) void k_sel_count(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
-                                                   const int64_t* __restrict__ col_keys, const uint8_t* __restrict__ col_live,
-                                                   int64_t table_len, bool dense, const int64_t* __restrict__ sel, int64_t nsel,
-                                                   int64_t dim_out, SelScratch s) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t j = (int64_t)blockIdx.x * 4 + wv;
-    if (j >= nsel) return;
-    const KeySpan sp = key_span(capacity, sems, col_keys, col_live, table_len, dense, sel[j], dim_out, lane);
-    const int64_t lo = sp.lo, hi = sp.hi;
-    const uint32_t err = sp.err;
-    const int64_t cnt = hi > lo ? sel_span_popc(occ, lo, hi, lane) : 0;
-    if (lane != 0) return;
-    s.lo[j] = lo; s.hi[j] = hi;
-    s.off[j] = cnt;
-    s.choff[j] = cnt > 0 ? ((hi - 1) >> EX_TILE_SHIFT) - (lo >> EX_TILE_SHIFT) + 1 : 0;
-    if (err) atomicOr(s.err, err);
-}
-
 // one workgroup: off / choff become exclusive prefixes in place, ptr[j] = base + off[j], ptr[nsel] = base + total
 template <typename IT>
 __global__ __launch_bounds__(EX_SCAN_THREADS) void k_sel_scan(SelScratch s, int64_t nsel, int64_t base, IT* __restrict__ ptr,
@@ -81,11 +60,7 @@ __global__ __launch_bounds__(EX_SCAN_THREADS) void k_sel_scan(SelScratch s, int6
                      carry_o, carry_s);
     if (threadIdx.x != 0) return;
     ptr[nsel] = (IT)(base + (int64_t)carry_o);
-    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(pinned + 1, carry_o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(pinned + 2, carry_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    publish_seq(pinned + 3, seq);
+    hand_over(s.err, pinned, seq, 2, carry_o, carry_s);
 }
 
 struct SelArgs {
@@ -108,31 +83,14 @@ __global__ __launch_bounds__(256) void k_sel_emit(KeyArr keys, const double* __r
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     uint32_t err = 0;
     for (int64_t w = (int64_t)blockIdx.x * 4 + wv; w < a.items; w += nwaves) {
-        // the first selection F whose chunk prefix exceeds w (nsel if none): a 64-ary search, one probe per lane and round.  Prefixes
-        // in front of L are <= w, the one at H is > w (or H = nsel).  The selection in front of F owns w (choff[0] = 0 <= w).
-        int64_t L = 0, H = a.nsel;
-        while (H - L > 64) {
-            const int64_t width = H - L;
-            const int64_t p = L + (width * (lane + 1)) / 64;     // ascending with the lane, lane 63 probes H
-            const bool le = p < a.nsel && s.choff[p] <= w;
-            const uint64_t nb = ~__ballot(le);
-            const int f = nb ? __ffsll((unsigned long long)nb) - 1 : 63;
-            H = L + (width * (f + 1)) / 64;
-            if (f > 0) L = L + (width * f) / 64 + 1;
-        }
-        const bool le = L + lane <= H && L + lane < a.nsel && s.choff[L + lane] <= w;
-        const uint64_t nb = ~__ballot(le);
-        const int64_t j = L + (nb ? __ffsll((unsigned long long)nb) - 1 : 64) - 1;
+        const int64_t j = item_past(s.choff, a.nsel, w, lane) - 1;       // the selection in front of the first whose prefix exceeds w owns it
         if (j < 0 || j >= a.nsel) { err |= 2u; continue; }
         const int64_t lo = s.lo[j], hi = s.hi[j];
-        const int64_t tile = (lo >> EX_TILE_SHIFT) + (w - s.choff[j]);
-        const int64_t t0 = tile << EX_TILE_SHIFT;
-        const int64_t cs = lo > t0 ? lo : t0, ce = hi < t0 + EX_TILE ? hi : t0 + EX_TILE;
-        if (ce <= cs) { err |= 2u; continue; }
-        int64_t run = s.off[j] + (cs > lo ? sel_span_popc(occ, lo, cs, lane) : 0);      // output position of the chunk's first cell
-        const int64_t w0 = tile * EX_WORDS;
-        const uint64_t myword = lane < EX_WORDS && ((w0 + lane) << 6) < ce ? occ[w0 + lane] & word_range_mask(w0 + lane, cs, ce - 1) : 0ull;
-        const uint32_t nz = (uint32_t)__ballot(myword != 0ull);  // words with a cell: a short span leaves most groups of a chunk empty
+        const SpanChunk c = span_chunk(lo, hi, (lo >> EX_TILE_SHIFT) + (w - s.choff[j]));
+        if (c.ce <= c.cs) { err |= 2u; continue; }
+        int64_t run = s.off[j] + (c.cs > lo ? sel_span_popc(occ, lo, c.cs, lane) : 0);      // output position of the chunk's first cell
+        uint32_t nz;
+        const uint64_t myword = chunk_word(occ, c, lane, nz);
         for (int q = 0; q < EX_WORDS; q += EX_U) {
             if (((nz >> q) & ((1u << EX_U) - 1u)) == 0u) continue;
             uint64_t wd[EX_U];
@@ -141,7 +99,7 @@ __global__ __launch_bounds__(256) void k_sel_emit(KeyArr keys, const double* __r
 #pragma unroll
             for (int u = 0; u < EX_U; ++u) {
                 wd[u] = readlane64(myword, q + u);
-                const int64_t i = ((w0 + q + u) << 6) + lane;
+                const int64_t i = ((c.w0 + q + u) << 6) + lane;
                 k[u] = -1; v[u] = 0.0;
                 if ((wd[u] >> lane) & 1ull) { k[u] = (int64_t)__builtin_nontemporal_load(kp + i); v[u] = __builtin_nontemporal_load(vals + i); }
             }
@@ -173,19 +131,13 @@ hipError_t launch_select_count(const uint64_t* occ, int64_t capacity, const int6
     hipError_t e = hipMemsetAsync(s.err, 0, 8, stream);
     if (e != hipSuccess) return e;
     if (nsel > 0)
-        hipLaunchKernelGGL(k_sel_count, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, occ, capacity, sems, col_keys, col_live,
-                           table_len, dense || col_live == nullptr, d_sel, nsel, dim_out, s);
+        hipLaunchKernelGGL(k_key_spans<true>, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, occ, capacity, sems, col_keys, col_live,
+                           table_len, dense || col_live == nullptr, d_sel, nsel, dim_out, s.lo, s.hi, s.choff, s.off, s.err);
     if (index_bits == 32)
         hipLaunchKernelGGL(k_sel_scan<int32_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, nsel, base, static_cast<int32_t*>(d_ptr), pinned4, seq);
     else
         hipLaunchKernelGGL(k_sel_scan<int64_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, nsel, base, static_cast<int64_t*>(d_ptr), pinned4, seq);
     return hipGetLastError();
-}
-
-template <bool WIDE, typename IT>
-static void launch_sel_emit_t(unsigned grid, hipStream_t stream, KeyArr keys, const double* vals, const uint64_t* occ, const SelScratch& s,
-                              const SelArgs& a) {
-    hipLaunchKernelGGL((k_sel_emit<WIDE, IT>), dim3(grid), dim3(256), 0, stream, keys, vals, occ, s, a);
 }
 
 hipError_t launch_select_emit(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t nsel, int64_t items,
@@ -194,15 +146,9 @@ hipError_t launch_select_emit(KeyArr keys, const double* vals, const uint64_t* o
     if (capacity < 0 || nsel < 1 || items < 1 || total < 1 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
     const SelScratch s = sel_carve(scratch, nsel);
     const SelArgs a{d_idx, d_vals, nsel, items, total, dim_in, base, pinned2, seq};
-    const int64_t blocks = (items + 3) / 4;
-    const unsigned grid = (unsigned)(blocks < SEL_EMIT_BLOCKS_MAX ? blocks : SEL_EMIT_BLOCKS_MAX);
-    if (keys.wide) {
-        if (index_bits == 32) launch_sel_emit_t<true, int32_t>(grid, stream, keys, vals, occ, s, a);
-        else launch_sel_emit_t<true, int64_t>(grid, stream, keys, vals, occ, s, a);
-    } else {
-        if (index_bits == 32) launch_sel_emit_t<false, int32_t>(grid, stream, keys, vals, occ, s, a);
-        else launch_sel_emit_t<false, int64_t>(grid, stream, keys, vals, occ, s, a);
-    }
+    dispatch_wide_it(keys.wide, index_bits, [&](auto wide, auto ix) {
+        hipLaunchKernelGGL((k_sel_emit<decltype(wide)::value, decltype(ix)>), dim3(ex_grid(items, 4)), dim3(256), 0, stream, keys, vals, occ, s, a);
+    });
     return hipGetLastError();
 }
 

@@ -315,16 +315,11 @@ __global__ __launch_bounds__(EX_SCAN_THREADS) void k_spg_scan(SpgScratch s, int6
     if (threadIdx.x != 0) return;
     s.cnt[k] = (int64_t)tot;
     yptr[k] = (IT)(base + (int64_t)tot);
-    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(pinned + 1, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    publish_seq(pinned + 2, seq);
+    hand_over(s.err, pinned, seq, 1, tot);
 }
 
 __global__ void k_spg_done(SpgScratch s, unsigned long long* pinned, unsigned long long seq) {
-    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    publish_seq(pinned + 1, seq);
+    hand_over(s.err, pinned, seq);
 }
 
 // ---- launches ---------------------------------------------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ size_t submatrix_item_scratch_bytes(int64_t items);
 // Error bits of the three phases: 1 an outer key outside 1..dim_out, 2 tables and slots out of step, 4 an inner key outside
 // 1..dim_in, 8 an inner key listed twice, 16 a cell of a selected partition whose stored inner key lies outside 1..dim_in.
 
-// Phase 1 (k_sub_hash, k_sub_spans, k_sub_scan_items): fills the hash table of the inner list, looks the outer keys up and cuts
+// Phase 1 (k_sub_hash, k_key_spans of export_dev.h, k_sub_scan_items): fills the hash table of the inner list, looks the outer keys up and cuts
 // their spans into 2048-slot work items; hands {error bits, work items} and then `seq` to pinned3.
 hipError_t launch_submatrix_keys(const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,
                                  int64_t table_len, bool dense, const int64_t* d_outer, int64_t nouter, int64_t dim_out,

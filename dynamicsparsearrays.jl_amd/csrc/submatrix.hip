@@ -14,12 +14,13 @@
 // Six launches, three host waits, whatever nouter, ninner and the span lengths are:
 //   k_sub_hash        grid-wide over the inner list: range check, 64-bit atomicCAS on the key word of the probed entry; a CAS that
 //                     meets its own key again is the repeated-key error
-//   k_sub_spans       one wave per outer key: the span (export_dev.h: key_span, shared with k_sel_count) and the 2048-slot tiles of
-//                     the slot array it touches (0 for a span without cells)
+//   k_key_spans       one wave per outer key: the span and the 2048-slot tiles of the slot array it touches (0 for a span without
+//                     cells); the kernel of the selected export (export_dev.h), without its cell counts
 //   k_sub_scan_items  one workgroup: exclusive prefix of the tiles -> the first work item of every outer key; {error word, items}
 //                     go to pinned memory
 //   (host: waits for the item count, sizes the item block)
-//   k_sub_count       one wave per work item (outer j, tile c), j by an upper-bound search over the item prefix: loads the keys of
+//   k_sub_count       one wave per work item (outer j, tile c), j by an upper-bound search over the item prefix (item_owner), its
+//                     slots and bitmap words by span_chunk / chunk_word (all in export_dev.h, shared with k_sel_emit): loads the keys of
 //                     the occupied slots, probes the table, counts the kept cells by ballot / popcount; stored keys outside
 //                     1..dim_in are found here.  Writes kept[w] and owner[w]
 //   k_sub_scan_cells  one workgroup: exclusive prefix of kept[] -> the output offset of every work item; ptr[j] = base + the offset
@@ -36,11 +37,9 @@
 // (ib + 8) * total + ib * (nouter + 1).
 #include "submatrix.h"
 #include "export_dev.h"
-#include <type_traits>
 
 namespace dsa {
 
-constexpr int64_t SUB_BLOCKS_MAX = 4096;                 // grid cap of the grid-strided kernels (the reason SEL_EMIT_BLOCKS_MAX has)
 constexpr uint64_t SUB_NONE = ~0ull;
 
 // key block: {error word, ticket of the emit, 8 bytes of padding}, the table's key words (the memset ends behind them), its
@@ -49,7 +48,7 @@ struct SubKeys {
     uint32_t* err; uint32_t* ticket;
     int64_t* tkey; int32_t* tpos; uint64_t tmask; int tshift;      // entry p of the table; p = (key * phi) >> tshift
     int64_t* lo; int64_t* hi;                            // span of outer key j: slots [lo, hi), 0-based
-    int64_t* choff;                                      // work items of j (k_sub_spans), then their exclusive prefix
+    int64_t* choff;                                      // work items of j (k_key_spans), then their exclusive prefix
 };
 // item block
 struct SubItems {
@@ -119,22 +118,6 @@ __global__ __launch_bounds__(256) void k_sub_hash(const int64_t* __restrict__ in
     if (err) atomicOr(s.err, err);
 }
 
-// one wave per outer key
-__global__ __launch_bounds__(256) void k_sub_spans(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
-                                                   const int64_t* __restrict__ col_keys, const uint8_t* __restrict__ col_live,
-                                                   int64_t table_len, bool dense, const int64_t* __restrict__ outer, int64_t nouter,
-                                                   int64_t dim_out, SubKeys s) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t j = (int64_t)blockIdx.x * 4 + wv;
-    if (j >= nouter) return;
-    const KeySpan sp = key_span(capacity, sems, col_keys, col_live, table_len, dense, outer[j], dim_out, lane);
-    const int64_t cnt = sp.hi > sp.lo ? sel_span_popc(occ, sp.lo, sp.hi, lane) : 0;
-    if (lane != 0) return;
-    s.lo[j] = sp.lo; s.hi[j] = sp.hi;
-    s.choff[j] = cnt > 0 ? ((sp.hi - 1) >> EX_TILE_SHIFT) - (sp.lo >> EX_TILE_SHIFT) + 1 : 0;
-    if (sp.err) atomicOr(s.err, sp.err);
-}
-
 // one workgroup: choff becomes its exclusive prefix in place
 __global__ __launch_bounds__(EX_SCAN_THREADS) void k_sub_scan_items(SubKeys s, int64_t nouter, unsigned long long* pinned,
                                                                     unsigned long long seq) {
@@ -142,43 +125,7 @@ __global__ __launch_bounds__(EX_SCAN_THREADS) void k_sub_scan_items(SubKeys s, i
     block_excl_scan2(s.choff, s.choff, nouter, [&](int64_t i, unsigned long long r, unsigned long long) { s.choff[i] = (int64_t)r; },
                      items, same);
     if (threadIdx.x != 0) return;
-    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(pinned + 1, items, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    publish_seq(pinned + 2, seq);
-}
-
-// The outer index that owns work item w: the last j whose item prefix is <= w (-1 if there is none).  A 64-ary search, one probe per
-// lane and round: prefixes in front of L are <= w, the one at H is > w (or H = n).  The search k_sel_emit makes over its chunk prefix.
-__device__ __forceinline__ int64_t sub_item_owner(const int64_t* __restrict__ choff, int64_t n, int64_t w, int lane) {
-    int64_t L = 0, H = n;
-    while (H - L > 64) {
-        const int64_t width = H - L;
-        const int64_t p = L + (width * (lane + 1)) / 64;         // ascending with the lane, lane 63 probes H
-        const bool le = p < n && choff[p] <= w;
-        const uint64_t nb = ~__ballot(le);
-        const int f = nb ? __ffsll((unsigned long long)nb) - 1 : 63;
-        H = L + (width * (f + 1)) / 64;
-        if (f > 0) L = L + (width * f) / 64 + 1;
-    }
-    const bool le = L + lane <= H && L + lane < n && choff[L + lane] <= w;
-    const uint64_t nb = ~__ballot(le);
-    return L + (nb ? __ffsll((unsigned long long)nb) - 1 : 64) - 1;
-}
-
-// the part of span [lo, hi) that lies in tile `tile` of the slot array: slots [cs, ce), this lane's bitmap word of the tile masked
-// to them, and the words with a cell
-struct SubChunk { int64_t cs, ce, w0; uint64_t myword; uint32_t nz; };
-__device__ __forceinline__ SubChunk sub_chunk(const uint64_t* __restrict__ occ, int64_t lo, int64_t hi, int64_t tile, int lane) {
-    SubChunk c;
-    const int64_t t0 = tile << EX_TILE_SHIFT;
-    c.cs = lo > t0 ? lo : t0;
-    c.ce = hi < t0 + EX_TILE ? hi : t0 + EX_TILE;
-    c.w0 = tile * EX_WORDS;
-    c.myword = 0ull;
-    if (c.ce > c.cs && lane < EX_WORDS && ((c.w0 + lane) << 6) < c.ce) c.myword = occ[c.w0 + lane] & word_range_mask(c.w0 + lane, c.cs, c.ce - 1);
-    c.nz = (uint32_t)__ballot(c.myword != 0ull);
-    return c;
+    hand_over(s.err, pinned, seq, 1, items);
 }
 
 // one wave per work item
@@ -192,22 +139,24 @@ __global__ __launch_bounds__(256) void k_sub_count(KeyArr keys, const uint64_t* 
     const int64_t nwaves = (int64_t)gridDim.x * 4;
     uint32_t err = 0;
     for (int64_t w = (int64_t)blockIdx.x * 4 + wv; w < items; w += nwaves) {
-        int64_t j = sub_item_owner(s.choff, nouter, w, lane);
+        int64_t j = item_owner(s.choff, nouter, w, lane);
         int64_t cnt = 0;
         if (j < 0 || j >= nouter) {
             err |= 2u; j = 0;
         } else {
             const int64_t lo = s.lo[j], hi = s.hi[j];
-            const SubChunk c = sub_chunk(occ, lo, hi, (lo >> EX_TILE_SHIFT) + (w - s.choff[j]), lane);
+            const SpanChunk c = span_chunk(lo, hi, (lo >> EX_TILE_SHIFT) + (w - s.choff[j]));
+            uint32_t nz;
+            const uint64_t myword = chunk_word(occ, c, lane, nz);
             if (c.ce <= c.cs) err |= 2u;
             for (int q = 0; q < EX_WORDS; q += EX_U) {
-                if (((c.nz >> q) & ((1u << EX_U) - 1u)) == 0u) continue;
+                if (((nz >> q) & ((1u << EX_U) - 1u)) == 0u) continue;
                 int64_t k[EX_U], t[EX_U];
                 uint64_t p[EX_U];
                 bool ok[EX_U];
 #pragma unroll
                 for (int u = 0; u < EX_U; ++u) {
-                    const bool cell = (readlane64(c.myword, q + u) >> lane) & 1ull;
+                    const bool cell = (readlane64(myword, q + u) >> lane) & 1ull;
                     k[u] = 0;
                     if (cell) k[u] = (int64_t)kp[((c.w0 + q + u) << 6) + lane];
                     ok[u] = cell && k[u] >= 1 && k[u] <= dim_in;
@@ -245,10 +194,7 @@ __global__ __launch_bounds__(EX_SCAN_THREADS) void k_sub_scan_cells(SubKeys s, S
     }
     if (threadIdx.x != 0) return;
     ptr[nouter] = (IT)(base + (int64_t)total);
-    const uint32_t e = __hip_atomic_load(s.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(pinned + 0, (unsigned long long)e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(pinned + 1, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    publish_seq(pinned + 2, seq);
+    hand_over(s.err, pinned, seq, 1, total);
 }
 
 struct SubArgs {
@@ -277,9 +223,11 @@ __global__ __launch_bounds__(256) void k_sub_emit(KeyArr keys, const double* __r
         const int64_t j = it.owner[w];
         if (j < 0 || j >= a.nouter || end > a.total) { err |= 2u; continue; }
         const int64_t lo = s.lo[j], hi = s.hi[j];
-        const SubChunk c = sub_chunk(occ, lo, hi, (lo >> EX_TILE_SHIFT) + (w - s.choff[j]), lane);
+        const SpanChunk c = span_chunk(lo, hi, (lo >> EX_TILE_SHIFT) + (w - s.choff[j]));
+        uint32_t nz;
+        const uint64_t myword = chunk_word(occ, c, lane, nz);
         for (int q = 0; q < EX_WORDS; q += EX_U) {
-            if (((c.nz >> q) & ((1u << EX_U) - 1u)) == 0u) continue;
+            if (((nz >> q) & ((1u << EX_U) - 1u)) == 0u) continue;
             int64_t k[EX_U], t[EX_U], out[EX_U];
             uint64_t p[EX_U];
             int32_t pos[EX_U];
@@ -287,7 +235,7 @@ __global__ __launch_bounds__(256) void k_sub_emit(KeyArr keys, const double* __r
 #pragma unroll
             for (int u = 0; u < EX_U; ++u) {
                 k[u] = 0;
-                if ((readlane64(c.myword, q + u) >> lane) & 1ull) k[u] = (int64_t)__builtin_nontemporal_load(kp + ((c.w0 + q + u) << 6) + lane);
+                if ((readlane64(myword, q + u) >> lane) & 1ull) k[u] = (int64_t)__builtin_nontemporal_load(kp + ((c.w0 + q + u) << 6) + lane);
             }
 #pragma unroll
             for (int u = 0; u < EX_U; ++u) {                     // every first probe is on its way before one is looked at
@@ -323,11 +271,6 @@ __global__ __launch_bounds__(256) void k_sub_emit(KeyArr keys, const double* __r
     emit_epilogue(err, lane, wv, s.err, s.ticket, a.pinned, a.seq);
 }
 
-static unsigned sub_grid(int64_t units, int64_t per_block) {
-    const int64_t blocks = (units + per_block - 1) / per_block;
-    return (unsigned)(blocks < SUB_BLOCKS_MAX ? blocks : SUB_BLOCKS_MAX);
-}
-
 hipError_t launch_submatrix_keys(const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,
                                  int64_t table_len, bool dense, const int64_t* d_outer, int64_t nouter, int64_t dim_out,
                                  const int64_t* d_inner, int64_t ninner, int64_t dim_in, void* key_scratch, unsigned long long* pinned3,
@@ -336,10 +279,10 @@ hipError_t launch_submatrix_keys(const uint64_t* occ, int64_t capacity, const in
     const SubKeys s = sub_carve(key_scratch, nouter, ninner);
     hipError_t e = hipMemsetAsync(key_scratch, 0, 16 + (size_t)(s.tmask + 1) * 8, stream);      // error word, ticket, every key word
     if (e != hipSuccess) return e;
-    if (ninner > 0) hipLaunchKernelGGL(k_sub_hash, dim3(sub_grid(ninner, 256)), dim3(256), 0, stream, d_inner, ninner, dim_in, s);
+    if (ninner > 0) hipLaunchKernelGGL(k_sub_hash, dim3(ex_grid(ninner, 256)), dim3(256), 0, stream, d_inner, ninner, dim_in, s);
     if (nouter > 0)
-        hipLaunchKernelGGL(k_sub_spans, dim3((unsigned)((nouter + 3) / 4)), dim3(256), 0, stream, occ, capacity, sems, col_keys, col_live,
-                           table_len, dense || col_live == nullptr, d_outer, nouter, dim_out, s);
+        hipLaunchKernelGGL(k_key_spans<false>, dim3((unsigned)((nouter + 3) / 4)), dim3(256), 0, stream, occ, capacity, sems, col_keys, col_live,
+                           table_len, dense || col_live == nullptr, d_outer, nouter, dim_out, s.lo, s.hi, s.choff, (int64_t*)nullptr, s.err);
     hipLaunchKernelGGL(k_sub_scan_items, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, nouter, pinned3, seq);
     return hipGetLastError();
 }
@@ -351,7 +294,7 @@ hipError_t launch_submatrix_count(KeyArr keys, const uint64_t* occ, int64_t capa
     const SubKeys s = sub_carve(key_scratch, nouter, ninner);
     const SubItems it = sub_carve_items(item_scratch, items);
     if (items > 0) {
-        const unsigned grid = sub_grid(items, 4);
+        const unsigned grid = ex_grid(items, 4);
         if (keys.wide) hipLaunchKernelGGL(k_sub_count<true>, dim3(grid), dim3(256), 0, stream, keys, occ, s, it, nouter, items, dim_in);
         else hipLaunchKernelGGL(k_sub_count<false>, dim3(grid), dim3(256), 0, stream, keys, occ, s, it, nouter, items, dim_in);
     }
@@ -364,12 +307,6 @@ hipError_t launch_submatrix_count(KeyArr keys, const uint64_t* occ, int64_t capa
     return hipGetLastError();
 }
 
-template <bool WIDE, typename IT>
-static void launch_sub_emit_t(unsigned grid, hipStream_t stream, KeyArr keys, const double* vals, const uint64_t* occ, const SubKeys& s,
-                              const SubItems& it, const SubArgs& a) {
-    hipLaunchKernelGGL((k_sub_emit<WIDE, IT>), dim3(grid), dim3(256), 0, stream, keys, vals, occ, s, it, a);
-}
-
 hipError_t launch_submatrix_emit(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t nouter, int64_t ninner,
                                  int64_t items, int64_t total, int32_t index_bits, int64_t base, void* d_idx, double* d_vals,
                                  void* key_scratch, void* item_scratch, unsigned long long* pinned2, unsigned long long seq,
@@ -378,14 +315,9 @@ hipError_t launch_submatrix_emit(KeyArr keys, const double* vals, const uint64_t
     const SubKeys s = sub_carve(key_scratch, nouter, ninner);
     const SubItems it = sub_carve_items(item_scratch, items);
     const SubArgs a{d_idx, d_vals, nouter, items, total, base, pinned2, seq};
-    const unsigned grid = sub_grid(items, 4);
-    if (keys.wide) {
-        if (index_bits == 32) launch_sub_emit_t<true, int32_t>(grid, stream, keys, vals, occ, s, it, a);
-        else launch_sub_emit_t<true, int64_t>(grid, stream, keys, vals, occ, s, it, a);
-    } else {
-        if (index_bits == 32) launch_sub_emit_t<false, int32_t>(grid, stream, keys, vals, occ, s, it, a);
-        else launch_sub_emit_t<false, int64_t>(grid, stream, keys, vals, occ, s, it, a);
-    }
+    dispatch_wide_it(keys.wide, index_bits, [&](auto wide, auto ix) {
+        hipLaunchKernelGGL((k_sub_emit<decltype(wide)::value, decltype(ix)>), dim3(ex_grid(items, 4)), dim3(256), 0, stream, keys, vals, occ, s, it, a);
+    });
     return hipGetLastError();
 }
 

@@ -215,6 +215,31 @@ def test_scan_carry_and_tiny_selections(dsa, long_case):
     assert len(a.count_columns([])) == 0
 
 
+OWNER_LENGTHS = (63, 64, 65, 4096, 4097)          # no narrowing round of the 64-ary owner search, the first round, the step past one round
+
+
+def owner_search_selections(E, n):
+    """column selections of `long_case` with n keys for the work-item owner search (export_dev.h: item_owner): short columns with
+    cells everywhere but at one position, which in turn holds the long column 150 first, in the middle and last (an owner of several
+    work items at either end) and an absent key first and last (tied item prefixes at both ends)"""
+    every = np.arange(1, E.dim_out + 1, dtype=np.int64)
+    short = every[(E.counts(every) > 0) & (every != 150)]
+    fill = np.random.default_rng(n).choice(short, n)
+    for pos, key in ((0, 150), (n // 2, 150), (n - 1, 150), (0, 17), (n - 1, 40)):
+        sel = fill.copy()
+        sel[pos] = key
+        yield sel
+
+
+@pytest.mark.gpu
+def test_owner_search_boundaries(dsa, long_case):
+    a, E, _ = long_case
+    assert E[COLMAJOR].counts([150, 17, 40]).tolist() == [5004, 0, 0]
+    for n in OWNER_LENGTHS:
+        for sel in owner_search_selections(E[COLMAJOR], n):
+            _check_dev(dsa, a, E[COLMAJOR], COLMAJOR, sel, bits=(32, 64), bases=(0,))
+
+
 @pytest.mark.gpu
 def test_selection_right_after_a_batch_sees_it(dsa, hip, oracle):
     rng = np.random.default_rng(8)

@@ -13,8 +13,9 @@ import numpy as np
 import pytest
 
 from scenario import run_scenario
-from test_select import (COLMAJOR, EARG, EBOUNDS, ECAP, EMODE, LONG_COLS, MATRIX_CASES, ROOT, ROWMAJOR, Expect, _assert_same, _in_fill_mode,
-                         long_case)  # noqa: F401  (long_case: the module-scoped fixture, instantiated once more for this module)
+from test_select import (COLMAJOR, EARG, EBOUNDS, ECAP, EMODE, LONG_COLS, MATRIX_CASES, OWNER_LENGTHS, ROOT, ROWMAJOR, Expect, _assert_same,
+                         _in_fill_mode, long_case, owner_search_selections)  # noqa: F401  (long_case: the module-scoped fixture,
+#                                                                              instantiated once more for this module)
 
 NAMES = ("mat_submatrix_compressed", "mat_submatrix_compressed_dev")
 
@@ -200,6 +201,16 @@ def test_empty_lists_and_scan_carry(dsa, long_case):
     _check(dsa, a, E[COLMAJOR], COLMAJOR, outer, inner, bits=(32, 64), bases=(1,))
     for k in (8192, 8193):                                  # one full step of the prefix loop, and one entry more
         _check(dsa, a, E[COLMAJOR], COLMAJOR, outer[:k], inner, bits=(64,), bases=(0,))
+
+
+@pytest.mark.gpu
+def test_owner_search_boundaries(dsa, long_case):
+    """the outer lists of test_select.py's case of this name (the owner search is the same function), the inner list every other row"""
+    a, E, _ = long_case
+    inner = np.arange(1, 6001, 2, dtype=np.int64)
+    for n in OWNER_LENGTHS:
+        for outer in owner_search_selections(E[COLMAJOR], n):
+            _check(dsa, a, E[COLMAJOR], COLMAJOR, outer, inner, bits=(32, 64), bases=(0,))
 
 
 @pytest.mark.gpu

@@ -9,9 +9,8 @@ namespace dsa {
 // (pooled, nothing to initialise); the last kernel writes {error bits: 1 an entry outside size(m), 2 slots and tables disagree} and then
 // `seq` to out2_pinned.  Reads the slot array and the tables only.
 size_t compress_scratch_bytes(int64_t capacity);
-hipError_t launch_to_compressed(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems,
-                                const int64_t* col_keys, const uint8_t* col_live, int64_t table_len, int64_t nparts, int64_t nnz,
-                                int64_t dim_out, int64_t dim_in, int32_t index_bits, int64_t base, void* d_ptr, void* d_idx, double* d_vals,
-                                void* scratch, unsigned long long* out2_pinned, unsigned long long seq, hipStream_t stream);
+hipError_t launch_to_compressed(const SlotView& V, int64_t nparts, int64_t nnz, int64_t dim_out, int64_t dim_in, int32_t index_bits, int64_t base,
+                                void* d_ptr, void* d_idx, double* d_vals, void* scratch, unsigned long long* out2_pinned,
+                                unsigned long long seq, hipStream_t stream);
 
 }  // namespace dsa

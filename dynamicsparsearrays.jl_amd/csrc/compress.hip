@@ -206,37 +206,36 @@ __global__ __launch_bounds__(256) void k_cx_emit(KeyArr keys, const double* __re
 }
 
 template <bool WIDE, typename IT>
-static void launch_emit_t(unsigned grid, hipStream_t stream, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                          const int64_t* sems, const int64_t* col_keys, int64_t table_len, const CxScratch& s, const CxArgs& a) {
-    hipLaunchKernelGGL((k_cx_emit<WIDE, IT>), dim3(grid), dim3(256), 0, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
+static void launch_emit_t(unsigned grid, hipStream_t stream, const SlotView& V, const CxScratch& s, const CxArgs& a) {
+    hipLaunchKernelGGL((k_cx_emit<WIDE, IT>), dim3(grid), dim3(256), 0, stream, V.keys, V.vals, V.occ, V.capacity, V.sems, V.part_keys, V.table_len,
+                       s, a);
 }
 
-hipError_t launch_to_compressed(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems,
-                                const int64_t* col_keys, const uint8_t* col_live, int64_t table_len, int64_t nparts, int64_t nnz,
-                                int64_t dim_out, int64_t dim_in, int32_t index_bits, int64_t base, void* d_ptr, void* d_idx, double* d_vals,
-                                void* scratch, unsigned long long* out2_pinned, unsigned long long seq, hipStream_t stream) {
-    if (capacity < 0 || table_len < 0 || dim_out < 0 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
-    const int64_t tiles = cx_tiles(capacity);
+hipError_t launch_to_compressed(const SlotView& V, int64_t nparts, int64_t nnz, int64_t dim_out, int64_t dim_in, int32_t index_bits, int64_t base,
+                                void* d_ptr, void* d_idx, double* d_vals, void* scratch, unsigned long long* out2_pinned,
+                                unsigned long long seq, hipStream_t stream) {
+    if (V.capacity < 0 || V.table_len < 0 || dim_out < 0 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
+    const int64_t tiles = cx_tiles(V.capacity);
     const CxScratch s = cx_carve(scratch, tiles);
     hipError_t e = hipMemsetAsync(s.sem_cnt, 0, (size_t)tiles * sizeof(uint32_t) + 8, stream);
     if (e != hipSuccess) return e;
-    const int64_t tile_blocks = (tiles + 3) / 4, table_blocks = (table_len + 255) / 256;
-    hipLaunchKernelGGL(k_cx_count, dim3((unsigned)(tile_blocks + table_blocks)), dim3(256), 0, stream, occ, capacity, sems, col_live,
-                       table_len, tile_blocks, s);
+    const int64_t tile_blocks = (tiles + 3) / 4, table_blocks = (V.table_len + 255) / 256;
+    hipLaunchKernelGGL(k_cx_count, dim3((unsigned)(tile_blocks + table_blocks)), dim3(256), 0, stream, V.occ, V.capacity, V.sems, V.part_live,
+                       V.table_len, tile_blocks, s);
     if (index_bits == 32)
-        hipLaunchKernelGGL(k_cx_scan<int32_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, sems, col_keys, table_len, nparts, nnz, dim_out,
-                           base, static_cast<int32_t*>(d_ptr));
+        hipLaunchKernelGGL(k_cx_scan<int32_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, V.sems, V.part_keys, V.table_len, nparts, nnz,
+                           dim_out, base, static_cast<int32_t*>(d_ptr));
     else
-        hipLaunchKernelGGL(k_cx_scan<int64_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, sems, col_keys, table_len, nparts, nnz, dim_out,
-                           base, static_cast<int64_t*>(d_ptr));
+        hipLaunchKernelGGL(k_cx_scan<int64_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, V.sems, V.part_keys, V.table_len, nparts, nnz,
+                           dim_out, base, static_cast<int64_t*>(d_ptr));
     CxArgs a{d_ptr, d_idx, d_vals, dim_out, dim_in, nnz, base, out2_pinned, seq};
     const unsigned grid = (unsigned)tile_blocks;
-    if (keys.wide) {
-        if (index_bits == 32) launch_emit_t<true, int32_t>(grid, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
-        else launch_emit_t<true, int64_t>(grid, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
+    if (V.keys.wide) {
+        if (index_bits == 32) launch_emit_t<true, int32_t>(grid, stream, V, s, a);
+        else launch_emit_t<true, int64_t>(grid, stream, V, s, a);
     } else {
-        if (index_bits == 32) launch_emit_t<false, int32_t>(grid, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
-        else launch_emit_t<false, int64_t>(grid, stream, keys, vals, occ, capacity, sems, col_keys, table_len, s, a);
+        if (index_bits == 32) launch_emit_t<false, int32_t>(grid, stream, V, s, a);
+        else launch_emit_t<false, int64_t>(grid, stream, V, s, a);
     }
     return hipGetLastError();
 }

@@ -23,7 +23,7 @@ constexpr int MAX_LEVELS = 48;
 // partition-table entries a batch may leave unmerged at the END of the tables (Ctl::n_pending): the one limit the sequencer's LDS
 // list (sequencer.hip), the batch-parallel rounds (parbatch.hip) and the grid-wide merge (tables.hip) share
 constexpr int TABLE_PEND_MAX = 1024;
-// slot ranges up to this size are packed by ONE launch of one workgroup (sequencer.hip: k_view_small): column views, slices, small vectors
+// slot ranges up to this size are packed by ONE launch of one workgroup (read.hip: k_view_small): column views, slices, small vectors
 constexpr int64_t VIEW_SMALL_SLOTS = 65536;
 
 // ---- physical key storage ---------------------------------------------------------------------------
@@ -71,6 +71,17 @@ struct KeyArr {
 #endif
 };
 static inline bool key_fits32(int64_t k) { return k >= INT32_MIN && k <= INT32_MAX; }
+
+// ---- read-only view of one orientation ----------------------------------------------------------------
+// What every kernel that only READS a structure sees of it, in one field order; the host builds it in one place (host.h:
+// Pma::view) and every read-only launch wrapper takes it.  sems / part_keys / part_live are nullptr on a structure without
+// the tables.  dense: no entry of [0, table_len) is tombstoned, part_live need not be read.  Writers keep their own
+// argument lists (non-const arrays, DevBufs).
+struct SlotView {
+    KeyArr keys; const double* vals; const uint64_t* occ; int64_t capacity;
+    const int64_t* sems; const int64_t* part_keys; const uint8_t* part_live;
+    int64_t table_len; bool dense;
+};
 
 // ---- control block shared by host and the sequencer kernel (one per PMA) ----------------------
 enum SeqStatus : int32_t {
@@ -287,9 +298,11 @@ hipError_t launch_compact_range(KeyArr keys, const double* vals, const uint64_t*
                                 KeyArr out_keys, double* out_vals, int64_t out_cap, RebalanceWork* work, int64_t* count,
                                 hipStream_t stream);
 // sparse-x product (sparsex.hip): accumulate driven by x's stored entries, touched-row bitmap of a pattern pass, count + emit
-hipError_t launch_spx_accum(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys,
-                            const uint8_t* col_live, int64_t table_len, const int64_t* xi, const double* xv, int64_t nx, double* acc,
-                            uint64_t* bm, int64_t ny, hipStream_t stream);
+hipError_t launch_spx_accum(const SlotView& V, const int64_t* xi, const double* xv, int64_t nx, double* acc, uint64_t* bm, int64_t ny,
+                            hipStream_t stream);
+// the repair pass of the dense-ish branch over the twin orientation (k_spx_repair)
+hipError_t launch_spx_repair(const SlotView& V, const double* xd, const double* xf, int64_t nx, const double* pattern, double* y, int64_t ny,
+                             hipStream_t stream);
 hipError_t launch_spx_pattern_bits(const double* pattern, int64_t ny, uint64_t* bm, hipStream_t stream);
 hipError_t launch_spx_finish(uint64_t* bm, int64_t ny, uint32_t* tile_cnt, uint32_t* tile_off, unsigned int* ticket, double* src, int clear_src,
                              int64_t* out_i, double* out_v, int64_t cap, int64_t* d_count, long long* host, int64_t pin_cells,
@@ -466,14 +479,10 @@ hipError_t launch_local_rounds(const DevBufs* bufs, Ctl* ctl, const Op* ops, Rou
 
 // batched read-only lookups.  mode 0: getindex(pma, key) ; 1: getindex(pcsc, key, partition) ;
 // 2: getindex(mpcsc, row, col).  err_out: first error code (0 if none)
-hipError_t launch_get_batch(int mode, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                            const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live, int64_t table_len,
-                            const int64_t* qa, const int64_t* qb, int64_t n, double* out, int32_t* err_out,
+hipError_t launch_get_batch(int mode, const SlotView& V, const int64_t* qa, const int64_t* qb, int64_t n, double* out, int32_t* err_out,
                             hipStream_t stream);
 // up to 64 lookups through a pinned landing area (no copy commands; see k_get_small)
-hipError_t launch_get_small(int mode, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems,
-                            const int64_t* col_keys, const uint8_t* col_live, int64_t table_len, int64_t* io, int n, unsigned long long seq,
-                            hipStream_t stream);
+hipError_t launch_get_small(int mode, const SlotView& V, int64_t* io, int n, unsigned long long seq, hipStream_t stream);
 // parity hooks (include/dsa.h: dsa_dbg_raw_*): ONE slot-array primitive on a raw slot array of `len` slots; out = 6 x int64 device
 // scratch {error, position, flag, found key, found value bits, cells purged}.  _block: the sequencer's workgroup primitives
 // (sequencer.hip), _wave: the wave-level primitives of the batch-parallel rounds (parbatch.hip).  *_FAST: K-find in its
@@ -485,30 +494,22 @@ hipError_t launch_dbg_raw_block(KeyArr keys, double* vals, uint64_t* occ, int64_
 hipError_t launch_dbg_raw_wave(KeyArr keys, double* vals, uint64_t* occ, int64_t* sems, int64_t len, int op, int64_t key, double val,
                                int64_t from, int64_t to, int64_t m, int64_t* out, hipStream_t stream);
 // device-side invariant checker; report[0..5] as documented at k_check_slots (8 x uint64 device scratch)
-hipError_t launch_check(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t occ_words,
-                        const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live, int64_t table_len,
-                        unsigned long long* report, hipStream_t stream);
+hipError_t launch_check(const SlotView& V, int64_t occ_words, unsigned long long* report, hipStream_t stream);
 // view of one partition in one launch (ranges up to 16384 slots): meta = {from, to, err, partition id, cells or -1 = use the general path}
-hipError_t launch_view_small(KeyArr keys, const double* vals, const uint64_t* occ, const int64_t* sems, const int64_t* col_keys,
-                             const uint8_t* col_live, int64_t table_len, int64_t capacity, int64_t col, KeyArr out_k, double* out_v,
-                             int64_t out_cap, int64_t* meta, int64_t* host, int64_t host_cells, unsigned long long seq, int64_t range_from,
-                             int64_t range_to, hipStream_t stream);
+hipError_t launch_view_small(const SlotView& V, int64_t col, KeyArr out_k, double* out_v, int64_t out_cap, int64_t* meta, int64_t* host,
+                             int64_t host_cells, unsigned long long seq, int64_t range_from, int64_t range_to, hipStream_t stream);
 // partition slot range lookup for views: out[0] = from (first slot after the semaphore), out[1] = to, or 0,0 if missing
-hipError_t launch_partition_range(const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,
-                                  int64_t table_len, int64_t capacity, int64_t col, int64_t* out, hipStream_t stream);
+hipError_t launch_partition_range(const SlotView& V, int64_t col, int64_t* out, hipStream_t stream);
 
 // y = P x over one orientation P, gather form: y[part_key[p]] = sum over partition p of val * x[key]
-hipError_t launch_spmv_gather(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                              const int64_t* sems, const int64_t* part_keys, const uint8_t* part_live, int64_t table_len,
-                              const double* x, int64_t nx, double* y, int64_t ny, int pattern, int mode, hipStream_t stream);
+hipError_t launch_spmv_gather(const SlotView& V, const double* x, int64_t nx, double* y, int64_t ny, int pattern, int mode, hipStream_t stream);
 constexpr int SPMV_ZFILL = 1;          // launch_spmv_gather mode bits (spmv.hip)
 constexpr int SPMV_PLAIN_STREAM = 2;
 constexpr int64_t SPMV_SPAN_SLOTS = 512;      // slots one wave of k_spmv_gather owns
 constexpr int SPMV_META_BLOCKS = 1024;        // workgroups of k_spmv_meta at most (four table entries per thread and step)
 constexpr int SPMV_META_WORDS = 3 * SPMV_META_BLOCKS + 1;     // its device scratch (zeroed once): partials, ticket
 // out6_pinned: six words of PINNED host memory — the five results, then `seq` (written last, system scope: the host polls for it)
-hipError_t launch_spmv_meta(const int64_t* sems, const int64_t* part_keys, int64_t table_len, int64_t capacity,
-                            unsigned long long* scratch, unsigned long long* out6_pinned, unsigned long long seq, hipStream_t stream);
+hipError_t launch_spmv_meta(const SlotView& V, unsigned long long* scratch, unsigned long long* out6_pinned, unsigned long long seq, hipStream_t stream);
 // ---- column-swept plan of the gather orientation (spmv.hip: k_plan_pass, k_plan_scan, k_spmv_plan) ---------------------
 // Groups of PLAN_GROUP_SLOTS slots own the rows whose semaphore lies in them; slices of at most 65 536 columns.  Per (group, slice)
 // the group's cells of that slice in (row, column) order: (row index within the group << 16 | column - slice base), the value apart.
@@ -533,17 +534,11 @@ struct PlanDev {
 };
 // count pass + scan + scatter (three launches on `stream`, no host wait); the scan writes {ok, cells} and then `seq` to out3_pinned
 // (and pass<true> fills the row map from part_keys)
-hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* part_keys,
-                                  int64_t table_len, int64_t nx, int64_t ny, const PlanDev& pl, unsigned long long* out3_pinned,
+hipError_t launch_spmv_plan_build(const SlotView& V, int64_t nx, int64_t ny, const PlanDev& pl, unsigned long long* out3_pinned,
                                   unsigned long long seq, hipStream_t stream);
 // y = P x from the plan (every row of [1, ny] written once, as the ZFILL gather does)
 hipError_t launch_spmv_plan(const PlanDev& pl, int64_t table_len, const double* x, double* y, int64_t ny, hipStream_t stream);
 // y[key] += x[part_key[p]] * val, scatter form with fp64 atomics (the literal _mul loop nest)
-hipError_t launch_spmv_scatter(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                               const int64_t* sems, const int64_t* part_keys, const uint8_t* part_live, int64_t table_len,
-                               const double* x, int64_t nx, double* y, int64_t ny, hipStream_t stream);
-
-// sparse x driven by its stored entries over the orientation whose partitions are x's index space (colmajor for mat*v):
-// y (dense, zeroed here) += x_j * column j ; touched[row] = 1 for every row that received a term
+hipError_t launch_spmv_scatter(const SlotView& V, const double* x, int64_t nx, double* y, int64_t ny, hipStream_t stream);
 
 }  // namespace dsa

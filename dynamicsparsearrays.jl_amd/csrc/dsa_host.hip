@@ -411,8 +411,7 @@ void mat_apply_sets(dsa_mat* h, const int64_t* I, const int64_t* J, const double
     // Without tombstones an OP_MPCSC_SET cannot fail (the reference's assert / bounds paths of addpartition! need a
     // deleted partition, App. A.6 (3)), so the two orientations can be updated concurrently; otherwise the colmajor
     // batch runs first and the rowmajor batch is cut at the failing op, like the reference's statement order.
-    const bool no_tombstones = h->col.h_ctl->nb_partitions == h->col.h_ctl->table_len &&
-                               h->row.h_ctl->nb_partitions == h->row.h_ctl->table_len;
+    const bool no_tombstones = h->col.view().dense && h->row.view().dense;
     static const bool par = [] { const char* e = dev_env("DSA_PARBATCH"); return !(e && e[0] == '0'); }();
     // With tombstones a write can only fail while it CREATES a partition in the middle of the table (addpartition!(pcsc, prev),
     // src/pcsr.jl:114-146: the two asserts, and the lookup behind a tombstoned tail).  A batch whose partition keys never decrease and start
@@ -422,7 +421,7 @@ void mat_apply_sets(dsa_mat* h, const int64_t* I, const int64_t* J, const double
     // 445 -> 330 ms).  Anything else with tombstones keeps the reference's statement order below.
     auto cannot_fail = [&](Pma& P, const int64_t* part_keys_of_ops) -> bool {
         const Ctl& c = *P.h_ctl;
-        if (c.nb_partitions == c.table_len) return true;
+        if (P.view().dense) return true;
         if (c.table_len <= 0 || c.n_pending != 0) return false;
         uint8_t live = 0; int64_t last_key = 0;
         HIPCHK(hipMemcpyAsync(&live, P.col_live + (c.table_len - 1), 1, hipMemcpyDeviceToHost, P.stream));
@@ -703,11 +702,11 @@ void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, in
         const bool plan = spmv_plan_on() && pattern == 0 && (mode & SPMV_ZFILL) && !(mode & SPMV_PLAIN_STREAM) && s == P.stream &&
                           nx > 0 && spmv_plan_shape_ok(P, nx, ny);
         if (plan && spmv_plan_product(P, d_x, nx, d_y, ny, s)) return;
-        e = launch_spmv_gather(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, d_x, nx, d_y, ny, pattern, mode, s);
+        e = launch_spmv_gather(P.view(), d_x, nx, d_y, ny, pattern, mode, s);
         if (e == hipSuccess && plan && P.plan.state == Pma::SpmvPlan::NONE && P.plan.products == 2) spmv_plan_build(P, nx, ny, s);
     } else if (algo == 1) {
         Pma& P = transpose ? h->row : h->col;
-        e = launch_spmv_scatter(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, d_x, nx, d_y, ny, s);
+        e = launch_spmv_scatter(P.view(), d_x, nx, d_y, ny, s);
     } else {
         fail(DSA_EARG, "algo must be 0 (gather) or 1 (scatter)");
     }

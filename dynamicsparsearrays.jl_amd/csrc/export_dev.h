@@ -1,7 +1,7 @@
 // csrc/export_dev.h — what the export kernel units share (compress.hip: the whole orientation, select.hip: the partitions of
 // a key list, submatrix.hip: those partitions restricted to an inner key list): the tile they cut the slot array into, the block
 // scan between their count and emit launches, and the ends of a scan and of an emit kernel.  For the two key-list exports also the
-// whole work-item pipeline: the span kernel of the outer keys (k_key_spans), the owner of a work item (item_past, item_owner), its part of the
+// whole work-item pipeline: the span kernel of the outer keys (k_key_spans, around key_span of find_dev.h), the owner of a work item (item_past, item_owner), its part of the
 // span and its bitmap words (span_chunk, chunk_word), the grid of the item kernels (ex_grid) and the choice of an emit instantiation (dispatch_wide_it).
 // Device code, and the two host helpers of its launches.
 #pragma once
@@ -84,48 +84,16 @@ __device__ __forceinline__ int64_t sel_span_popc(const uint64_t* __restrict__ oc
     return wave_reduce_add(c);
 }
 
-// The span of the live partition whose key is `key` (one wave, the same answer in every lane): its cells are the occupied slots of
-// [lo, hi), 0-based, strictly between its semaphore and the next live semaphore (tombstoned table entries behind the partition are
-// skipped 64 at a time; the end of the slot array behind the last one).  lo = hi = 0 for a key without a live partition.
-// err: 1 the key lies outside 1..dim_out, 2 tables out of step with the slots.
-struct KeySpan { int64_t lo, hi; uint32_t err; };
-__device__ __forceinline__ KeySpan key_span(int64_t capacity, const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
-                                            const uint8_t* __restrict__ col_live, int64_t table_len, bool dense, int64_t key,
-                                            int64_t dim_out, int lane) {
-    KeySpan r{0, 0, 0u};
-    if (key < 1 || key > dim_out) {
-        r.err = 1u;
-    } else {
-        const DFoundKey f = d_find_table_fast(col_keys, col_live, table_len, key, dense);
-        if (f.has && f.key == key) {
-            const int64_t sp = sems[f.pos - 1];                  // 1-based slot of the semaphore = 0-based slot of the first cell
-            int64_t nx = 0;                                      // the next live semaphore (tombstones have none)
-            for (int64_t e0 = f.pos; e0 < table_len; e0 += 64) {
-                const int64_t e = e0 + lane;
-                const int64_t v = e < table_len ? sems[e] : 0;
-                const uint64_t m = __ballot(v != 0);
-                if (m) { nx = (int64_t)readlane64((uint64_t)v, __ffsll((unsigned long long)m) - 1); break; }
-            }
-            const int64_t end = nx ? nx - 1 : capacity;
-            if (sp < 1 || sp > capacity || end < sp || end > capacity) r.err = 2u;      // tables out of step with the slots
-            else { r.lo = sp; r.hi = end; }
-        }
-    }
-    return r;
-}
-
 // One wave per outer key (4 per workgroup): span j = [lo[j], hi[j]), chunks[j] = 2048-slot tiles of the slot array it touches (0 for a
-// span without cells), with CELLS cells[j] = its occupied slots; the error bits of key_span are ORed into *err.
+// span without cells), with CELLS cells[j] = its occupied slots; the error bits of key_span (find_dev.h) are ORed into *err.
 template <bool CELLS>
-__global__ __launch_bounds__(256) void k_key_spans(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
-                                                   const int64_t* __restrict__ col_keys, const uint8_t* __restrict__ col_live,
-                                                   int64_t table_len, bool dense, const int64_t* __restrict__ keys, int64_t nkeys,
-                                                   int64_t dim_out, int64_t* lo, int64_t* hi, int64_t* chunks, int64_t* cells, uint32_t* err) {
+__global__ __launch_bounds__(256) void k_key_spans(SlotView V, const int64_t* __restrict__ keys, int64_t nkeys, int64_t dim_out, int64_t* lo,
+                                                   int64_t* hi, int64_t* chunks, int64_t* cells, uint32_t* err) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t j = (int64_t)blockIdx.x * 4 + wv;
     if (j >= nkeys) return;
-    const KeySpan sp = key_span(capacity, sems, col_keys, col_live, table_len, dense, keys[j], dim_out, lane);
-    const int64_t cnt = sp.hi > sp.lo ? sel_span_popc(occ, sp.lo, sp.hi, lane) : 0;
+    const KeySpan sp = key_span(V, keys[j], dim_out, lane);
+    const int64_t cnt = sp.hi > sp.lo ? sel_span_popc(V.occ, sp.lo, sp.hi, lane) : 0;
     if (lane != 0) return;
     lo[j] = sp.lo; hi[j] = sp.hi;
     if (CELLS) cells[j] = cnt;

@@ -72,7 +72,7 @@ void compress_side(const Side& e, int32_t index_bits, int32_t index_base, void* 
     ExportArea& A = P.cx;
     A.ensure(P.stream, compress_scratch_bytes(P.capacity()), 2);      // pinned {error word, sequence number}
     const unsigned long long seq = A.next();
-    LAUNCH("compressed export", launch_to_compressed(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, parts, nnz,
+    LAUNCH("compressed export", launch_to_compressed(P.view(), parts, nnz,
                                                      e.dim_out, e.dim_in, index_bits, index_base, d_ptr, d_idx, d_vals, A.scratch, A.pin, seq, P.stream));
     wait_handover(P, A.pin + 1, seq, "compressed export");
     export_verdict(A.pin, "compressed export", "a stored entry lies outside size(m)");
@@ -140,10 +140,8 @@ KeyTotals select_count(const Side& e, int32_t index_bits, int32_t index_base, co
     // pinned {error word, cells, work items, sequence number} of the count and {error word, sequence number} of the emit
     A.ensure(P.stream, select_scratch_bytes(nsel), 6);
     const unsigned long long seq = A.next();
-    const Ctl& c = *P.h_ctl;
-    LAUNCH("selected export (count)", launch_select_count(P.O(), c.capacity, P.sems, P.col_keys, P.col_live, c.table_len,
-                                                          c.nb_partitions == c.table_len, d_sel, nsel, e.dim_out, index_bits, index_base,
-                                                          d_ptr, A.scratch, A.pin, seq, P.stream));
+    LAUNCH("selected export (count)", launch_select_count(P.view(), d_sel, nsel, e.dim_out, index_bits, index_base, d_ptr, A.scratch, A.pin,
+                                                          seq, P.stream));
     wait_handover(P, A.pin + 3, seq, "selected export (count)");
     export_verdict(A.pin, "selected export", "a selected key lies outside size(m)");
     KeyTotals t;
@@ -160,7 +158,7 @@ void select_emit(const Side& e, const KeyTotals& t, int32_t index_bits, int32_t 
     Pma& P = e.P;
     ExportArea& A = P.sel;
     const unsigned long long seq = A.next();
-    LAUNCH("selected export (emit)", launch_select_emit(P.K(), P.V(), P.O(), P.capacity(), nsel, t.items, t.total, e.dim_in, index_bits,
+    LAUNCH("selected export (emit)", launch_select_emit(P.view(), nsel, t.items, t.total, e.dim_in, index_bits,
                                                         index_base, d_idx, d_vals, A.scratch, A.pin + 4, seq, P.stream));
     wait_handover(P, A.pin + 5, seq, "selected export (emit)");
     export_verdict(A.pin + 4, "selected export", "a stored entry of a selected partition lies outside size(m)");
@@ -195,17 +193,15 @@ KeyTotals submatrix_count(const Side& e, int32_t index_bits, int32_t index_base,
     // {error word, sequence number} of the emit
     A.ensure(P.stream, submatrix_key_scratch_bytes(nouter, ninner), 8);
     unsigned long long seq = A.next();
-    const Ctl& c = *P.h_ctl;
-    LAUNCH("submatrix export (keys)", launch_submatrix_keys(P.O(), c.capacity, P.sems, P.col_keys, P.col_live, c.table_len,
-                                                            c.nb_partitions == c.table_len, d_outer, nouter, e.dim_out, d_inner, ninner,
-                                                            e.dim_in, A.scratch, A.pin, seq, P.stream));
+    LAUNCH("submatrix export (keys)", launch_submatrix_keys(P.view(), d_outer, nouter, e.dim_out, d_inner, ninner, e.dim_in, A.scratch, A.pin,
+                                                            seq, P.stream));
     wait_handover(P, A.pin + 2, seq, "submatrix export (keys)");
     submatrix_verdict(A.pin);
     KeyTotals t;
     t.items = (int64_t)A.pin[1];
     I.ensure(P.stream, submatrix_item_scratch_bytes(t.items), 1);
     seq = A.next();
-    LAUNCH("submatrix export (count)", launch_submatrix_count(P.K(), P.O(), c.capacity, nouter, ninner, t.items, e.dim_in, index_bits,
+    LAUNCH("submatrix export (count)", launch_submatrix_count(P.view(), nouter, ninner, t.items, e.dim_in, index_bits,
                                                               index_base, d_ptr, A.scratch, I.scratch, A.pin + 3, seq, P.stream));
     wait_handover(P, A.pin + 5, seq, "submatrix export (count)");
     submatrix_verdict(A.pin + 3);
@@ -223,7 +219,7 @@ void submatrix_emit(const Side& e, const KeyTotals& t, int32_t index_bits, int32
     Pma& P = e.P;
     ExportArea& A = P.sub;
     const unsigned long long seq = A.next();
-    LAUNCH("submatrix export (emit)", launch_submatrix_emit(P.K(), P.V(), P.O(), P.capacity(), nouter, ninner, t.items, t.total, index_bits,
+    LAUNCH("submatrix export (emit)", launch_submatrix_emit(P.view(), nouter, ninner, t.items, t.total, index_bits,
                                                             index_base, d_idx, d_vals, A.scratch, P.subi.scratch, A.pin + 6, seq, P.stream));
     wait_handover(P, A.pin + 7, seq, "submatrix export (emit)");
     submatrix_verdict(A.pin + 6);

@@ -1,7 +1,9 @@
-// csrc/find_dev.h — device helpers shared by the write sequencer (sequencer.hip) and the batch-parallel insert path
-// (parbatch.hip): bitmap scans and the two forms of K-find.  Positions are 1-based like the reference.
+// csrc/find_dev.h — the lookups every kernel unit shares: bitmap scans, the two forms of K-find on slots, the two forms of the
+// partition-table search, and the slot span of a partition in its two forms — part_span, serial, for the single-lane callers that
+// replay the reference's probes (read.hip), and key_span / live_span, wave-parallel, for the exports and the products.  The 64-ary search over
+// the partition table exists only here.  Positions are 1-based like the reference unless a comment says otherwise.
 #pragma once
-#include "dsa_dev.h"
+#include "wave_dev.h"
 
 namespace dsa {
 
@@ -166,7 +168,7 @@ static __device__ DFoundKey d_find_table(const int64_t* ck, const uint8_t* live,
 }
 
 // wave-parallel form of d_find_table (live column keys are strictly ascending)
-// dense = true: the caller knows that no entry of [0, len) is tombstoned (nb_partitions == table_len): live[] is not read
+// dense = true: the caller knows that no entry of [0, len) is tombstoned (SlotView::dense): live[] is not read
 static __device__ DFoundKey d_find_table_fast(const int64_t* ck, const uint8_t* live, int64_t len, int64_t key, bool dense = false) {
     const int lane = lane_id();
     int64_t L = 0, H = len;
@@ -221,6 +223,47 @@ static __device__ int64_t d_next_live_sem(const int64_t* sems, int64_t from, int
         ++pos;
     }
     return 0;
+}
+
+// The slot range of partition `id` (1-based table index, 1 <= id <= V.table_len), one lane, the reference's own probes
+// (_pos_of_partition_start / _pos_of_partition_end, src/pcsr.jl): from = the slot of its semaphore, to = the slot in front of the
+// next live semaphore or the capacity, both 1-based; the cells are the occupied slots of [from + 1, to].  err = E_ASSERT (and
+// from = to = 0) for a partition without a semaphore.
+struct PartSpan { int64_t from, to; int32_t err; };
+static __device__ PartSpan part_span(const SlotView& V, int64_t id) {
+    const int64_t from = V.sems[id - 1];
+    if (from == 0) return PartSpan{0, 0, E_ASSERT};
+    const int64_t next = d_next_live_sem(V.sems, id, V.table_len);
+    return PartSpan{from, next != 0 ? V.sems[next - 1] - 1 : V.capacity, E_OK};
+}
+
+// The span of the live partition whose key is `key` (one wave, the same answer in every lane): its cells are the occupied slots of
+// [lo, hi), 0-based, strictly between its semaphore and the next live semaphore (tombstoned table entries behind the partition are
+// skipped 64 at a time; the end of the slot array behind the last one).  lo = hi = 0 for a key without a live partition.
+// err: 1 the key lies outside 1..dim_out, 2 tables out of step with the slots.
+struct KeySpan { int64_t lo, hi; uint32_t err; };
+// ... of any key the table holds, also one below 1 (the sparse-x product: a matrix may own such a column); err is 0 or 2
+__device__ __forceinline__ KeySpan live_span(const SlotView& V, int64_t key, int lane) {
+    KeySpan r{0, 0, 0u};
+    const DFoundKey f = d_find_table_fast(V.part_keys, V.part_live, V.table_len, key, V.dense);
+    if (f.has && f.key == key) {
+        const int64_t sp = V.sems[f.pos - 1];                    // 1-based slot of the semaphore = 0-based slot of the first cell
+        int64_t nx = 0;                                          // the next live semaphore (tombstones have none)
+        for (int64_t e0 = f.pos; e0 < V.table_len; e0 += 64) {
+            const int64_t e = e0 + lane;
+            const int64_t v = e < V.table_len ? V.sems[e] : 0;
+            const uint64_t m = __ballot(v != 0);
+            if (m) { nx = (int64_t)readlane64((uint64_t)v, __ffsll((unsigned long long)m) - 1); break; }
+        }
+        const int64_t end = nx ? nx - 1 : V.capacity;
+        if (sp < 1 || sp > V.capacity || end < sp || end > V.capacity) r.err = 2u;          // tables out of step with the slots
+        else { r.lo = sp; r.hi = end; }
+    }
+    return r;
+}
+__device__ __forceinline__ KeySpan key_span(const SlotView& V, int64_t key, int64_t dim_out, int lane) {
+    if (key < 1 || key > dim_out) return KeySpan{0, 0, 1u};
+    return live_span(V, key, lane);
 }
 
 }  // namespace dsa

@@ -162,6 +162,13 @@ struct Pma {
     size_t kb() const { return wide ? sizeof(int64_t) : sizeof(int32_t); }
     double* V() const { return vals[cur]; }
     uint64_t* O() const { return occ[cur]; }
+    // what the read-only kernels see (dsa_dev.h: SlotView): the current buffers and the control block's mirror, nothing else
+    SlotView view() const {
+        const Ctl& c = *h_ctl;
+        const uint8_t* live = has_cols ? col_live : nullptr;
+        return SlotView{K(), V(), O(), c.capacity, has_sems ? sems : nullptr, has_cols ? col_keys : nullptr, live,
+                        c.table_len, c.nb_partitions == c.table_len || live == nullptr};
+    }
 };
 
 // A batch of ops as the host hands it to a structure: a ready-made Op array (small batches, mixed kinds), or the caller's COLUMNS —

@@ -420,8 +420,7 @@ void pma_check(Pma& P, int64_t* report) {
     unsigned long long* d = nullptr;
     HIPCHK(hipMalloc(&d, 8 * sizeof(unsigned long long)));
     unsigned long long r[8] = {0};
-    hipError_t e = launch_check(P.K(), P.V(), P.O(), P.capacity(), P.occ_words, P.has_sems ? P.sems : nullptr,
-                                P.has_cols ? P.col_keys : nullptr, P.has_cols ? P.col_live : nullptr, P.h_ctl->table_len, d, P.stream);
+    hipError_t e = launch_check(P.view(), P.occ_words, d, P.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(r, d, sizeof(r), hipMemcpyDeviceToHost, P.stream);
     // no table entry may be pending outside a batch (tables.hip): the DEVICE copy of the counter is the one the kernels trust
     int64_t dev_pending = 0, merge_fault = 0;
@@ -455,7 +454,7 @@ void get_batch(Pma& P, int mode, const int64_t* qa, const int64_t* qb, int64_t n
         for (int64_t i = 0; i < n; ++i) { P.h_get[i] = qa[i]; P.h_get[64 + i] = qb ? qb[i] : 0; }
         const unsigned long long seq = ++P.get_seq;
         __atomic_thread_fence(__ATOMIC_RELEASE);
-        LAUNCH("get", launch_get_small(mode, P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, P.h_get, (int)n, seq, P.stream));
+        LAUNCH("get", launch_get_small(mode, P.view(), P.h_get, (int)n, seq, P.stream));
         wait_handover(P, P.h_get + 193, seq, "get");
         std::memcpy(out, P.h_get + 128, (size_t)n * sizeof(double));
         const int32_t err = (int32_t)P.h_get[192];
@@ -469,8 +468,7 @@ void get_batch(Pma& P, int mode, const int64_t* qa, const int64_t* qb, int64_t n
     HIPCHK(hipMemcpyAsync(d_qa, qa, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, P.stream));
     if (qb) HIPCHK(hipMemcpyAsync(d_qb, qb, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, P.stream));
     HIPCHK(hipMemsetAsync(P.d_err, 0, sizeof(int32_t), P.stream));
-    LAUNCH("get", launch_get_batch(mode, P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len,
-                                   d_qa, d_qb, n, d_out, P.d_err, P.stream));
+    LAUNCH("get", launch_get_batch(mode, P.view(), d_qa, d_qb, n, d_out, P.d_err, P.stream));
     int32_t err = 0;
     HIPCHK(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, P.stream));
     HIPCHK(hipMemcpyAsync(&err, P.d_err, sizeof(int32_t), hipMemcpyDeviceToHost, P.stream));
@@ -516,8 +514,8 @@ static void view_small(Pma& P, int64_t col, int64_t range_from, int64_t range_to
         // polls for it — no copy command, no stream synchronisation (60 -> 20 us per view)
         ViewAreaLease lease(P);
         const unsigned long long seq = ++P.view_seq;
-        LAUNCH("view", launch_view_small(P.K(), P.V(), P.O(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, P.capacity(), col,
-                                         P.KA(alt), P.vals[alt], out_cap, P.d_small, P.h_view, SPEC, seq, range_from, range_to, P.stream));
+        LAUNCH("view", launch_view_small(P.view(), col, P.KA(alt), P.vals[alt], out_cap, P.d_small, P.h_view, SPEC, seq, range_from, range_to,
+                                         P.stream));
         wait_handover(P, P.h_view + 5, seq, "view");
         for (int q = 0; q < 5; ++q) r[q] = P.h_view[q];
         const int64_t have = std::max<int64_t>(0, std::min<int64_t>(r[4], spec));
@@ -559,8 +557,7 @@ DevView view_dev(Pma& P, int64_t col) {
     {   // (the landing area is leased for the hand-over only)
         ViewAreaLease lease(P);
         const unsigned long long seq = ++P.view_seq;
-        LAUNCH("view", launch_view_small(P.K(), P.V(), P.O(), P.sems, P.col_keys, P.col_live, P.h_ctl->table_len, P.capacity(), col,
-                                         P.KA(alt), P.vals[alt], out_cap, P.d_small, P.h_view, 0, seq, 0, 0, P.stream));
+        LAUNCH("view", launch_view_small(P.view(), col, P.KA(alt), P.vals[alt], out_cap, P.d_small, P.h_view, 0, seq, 0, 0, P.stream));
         wait_handover(P, P.h_view + 5, seq, "view");
         for (int q = 0; q < 5; ++q) r[q] = P.h_view[q];
         r[5] = P.h_view[6];
@@ -587,7 +584,8 @@ int64_t pack_small(Pma& P, KeyArr k, const double* v, const uint64_t* occ, int64
     if (to < from || from < 1 || to - from + 1 > VIEW_SMALL_SLOTS || to - from + 1 > out_cap) return -1;
     ViewAreaLease lease(P);
     const unsigned long long seq = ++P.view_seq;
-    LAUNCH("pack", launch_view_small(k, v, occ, nullptr, nullptr, nullptr, 0, to, 0, ok, ov, out_cap, P.d_small, P.h_view, 0, seq, from, to, P.stream));
+    const SlotView raw{k, v, occ, to, nullptr, nullptr, nullptr, 0, true};      // a bare slot range: no tables, nothing is looked up
+    LAUNCH("pack", launch_view_small(raw, 0, ok, ov, out_cap, P.d_small, P.h_view, 0, seq, from, to, P.stream));
     wait_handover(P, P.h_view + 5, seq, "pack");
     return P.h_view[4];
 }

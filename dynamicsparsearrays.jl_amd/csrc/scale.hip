@@ -352,10 +352,9 @@ struct ScScratch {
 };
 
 template <bool WIDE, bool NT>
-static void launch_reduce_kind(unsigned grid, hipStream_t stream, int32_t kind, KeyArr keys, const double* vals, const uint64_t* occ,
-                               int64_t capacity, const int64_t* part_keys, int64_t table_len, double* out, int64_t n_out, const ScScratch& S) {
-#define DSA_RED_CASE(K_) hipLaunchKernelGGL((k_reduce<WIDE, NT, K_>), dim3(grid), dim3(SC_BLOCK), 0, stream, keys, vals, occ, capacity, part_keys, \
-                                            table_len, out, n_out, S.hdr, static_cast<double*>(S.a0), static_cast<double*>(S.a1), static_cast<int64_t*>(S.a2))
+static void launch_reduce_kind(unsigned grid, hipStream_t stream, int32_t kind, const SlotView& V, double* out, int64_t n_out, const ScScratch& S) {
+#define DSA_RED_CASE(K_) hipLaunchKernelGGL((k_reduce<WIDE, NT, K_>), dim3(grid), dim3(SC_BLOCK), 0, stream, V.keys, V.vals, V.occ, V.capacity, V.part_keys, \
+                                            V.table_len, out, n_out, S.hdr, static_cast<double*>(S.a0), static_cast<double*>(S.a1), static_cast<int64_t*>(S.a2))
     switch (kind) {
         case RED_SUM: DSA_RED_CASE(RED_SUM); break;
         case RED_ABSSUM: DSA_RED_CASE(RED_ABSSUM); break;
@@ -366,43 +365,42 @@ static void launch_reduce_kind(unsigned grid, hipStream_t stream, int32_t kind, 
 #undef DSA_RED_CASE
 }
 
-hipError_t launch_reduce(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* part_keys, int64_t table_len,
-                         int32_t kind, double* out, int64_t n_out, bool nt, void* scratch, unsigned long long* pinned,
+hipError_t launch_reduce(const SlotView& V, int32_t kind, double* out, int64_t n_out, bool nt, void* scratch, unsigned long long* pinned,
                          unsigned long long seq, hipStream_t stream) {
-    if (capacity <= 0 || kind < RED_SUM || kind > RED_COUNT) return hipErrorInvalidValue;
-    const ScScratch S(scratch, capacity);
+    if (V.capacity <= 0 || kind < RED_SUM || kind > RED_COUNT) return hipErrorInvalidValue;
+    const ScScratch S(scratch, V.capacity);
     hipError_t e = hipMemsetAsync(S.hdr, 0, sizeof(ScHeader), stream);
     if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)((S.nspans + SC_WAVES - 1) / SC_WAVES);
-    switch ((keys.wide ? 2 : 0) | (nt ? 1 : 0)) {
-        case 0: launch_reduce_kind<false, false>(grid, stream, kind, keys, vals, occ, capacity, part_keys, table_len, out, n_out, S); break;
-        case 1: launch_reduce_kind<false, true>(grid, stream, kind, keys, vals, occ, capacity, part_keys, table_len, out, n_out, S); break;
-        case 2: launch_reduce_kind<true, false>(grid, stream, kind, keys, vals, occ, capacity, part_keys, table_len, out, n_out, S); break;
-        default: launch_reduce_kind<true, true>(grid, stream, kind, keys, vals, occ, capacity, part_keys, table_len, out, n_out, S); break;
+    switch ((V.keys.wide ? 2 : 0) | (nt ? 1 : 0)) {
+        case 0: launch_reduce_kind<false, false>(grid, stream, kind, V, out, n_out, S); break;
+        case 1: launch_reduce_kind<false, true>(grid, stream, kind, V, out, n_out, S); break;
+        case 2: launch_reduce_kind<true, false>(grid, stream, kind, V, out, n_out, S); break;
+        default: launch_reduce_kind<true, true>(grid, stream, kind, V, out, n_out, S); break;
     }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     const unsigned fgrid = (unsigned)((S.nspans + SC_BLOCK - 1) / SC_BLOCK);
 #define DSA_FIN_CASE(K_) hipLaunchKernelGGL((k_reduce_finish<K_>), dim3(fgrid), dim3(SC_BLOCK), 0, stream, S.nspans, static_cast<const double*>(S.a0), \
-                                            static_cast<const double*>(S.a1), static_cast<const int64_t*>(S.a2), part_keys, table_len, out, n_out, S.hdr, pinned, seq)
+                                            static_cast<const double*>(S.a1), static_cast<const int64_t*>(S.a2), V.part_keys, V.table_len, out, n_out, S.hdr, pinned, seq)
     if (kind == RED_ABSMAX) DSA_FIN_CASE(RED_ABSMAX); else DSA_FIN_CASE(RED_SUM);      // every other kind combines with +
 #undef DSA_FIN_CASE
     return hipGetLastError();
 }
 
-hipError_t launch_scale_check(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems,
-                              const int64_t* part_keys, int64_t table_len, int64_t dim_key, int64_t dim_part, void* scratch,
-                              unsigned long long* pinned, unsigned long long seq, hipStream_t stream) {
-    if (capacity <= 0) return hipErrorInvalidValue;
-    const ScScratch S(scratch, capacity);
+hipError_t launch_scale_check(const SlotView& V, int64_t dim_key, int64_t dim_part, void* scratch, unsigned long long* pinned,
+                              unsigned long long seq, hipStream_t stream) {
+    if (V.capacity <= 0) return hipErrorInvalidValue;
+    const ScScratch S(scratch, V.capacity);
     hipError_t e = hipMemsetAsync(S.hdr, 0, sizeof(ScHeader), stream);
     if (e != hipSuccess) return e;
     const unsigned grid = (unsigned)((S.nspans + SC_WAVES - 1) / SC_WAVES);
-    if (keys.wide) hipLaunchKernelGGL((k_scale_check<true>), dim3(grid), dim3(SC_BLOCK), 0, stream, keys, vals, occ, capacity, dim_key, S.hdr, static_cast<int64_t*>(S.a0));
-    else hipLaunchKernelGGL((k_scale_check<false>), dim3(grid), dim3(SC_BLOCK), 0, stream, keys, vals, occ, capacity, dim_key, S.hdr, static_cast<int64_t*>(S.a0));
-    if (table_len > 0)
-        hipLaunchKernelGGL(k_scale_tables, dim3((unsigned)((table_len + SC_BLOCK - 1) / SC_BLOCK)), dim3(SC_BLOCK), 0, stream, sems, part_keys, table_len,
-                           dim_part, S.hdr);
+    int64_t* open_at = static_cast<int64_t*>(S.a0);
+    if (V.keys.wide) hipLaunchKernelGGL((k_scale_check<true>), dim3(grid), dim3(SC_BLOCK), 0, stream, V.keys, V.vals, V.occ, V.capacity, dim_key, S.hdr, open_at);
+    else hipLaunchKernelGGL((k_scale_check<false>), dim3(grid), dim3(SC_BLOCK), 0, stream, V.keys, V.vals, V.occ, V.capacity, dim_key, S.hdr, open_at);
+    if (V.table_len > 0)
+        hipLaunchKernelGGL(k_scale_tables, dim3((unsigned)((V.table_len + SC_BLOCK - 1) / SC_BLOCK)), dim3(SC_BLOCK), 0, stream, V.sems, V.part_keys,
+                           V.table_len, dim_part, S.hdr);
     hipLaunchKernelGGL(k_scale_carry, dim3(1), dim3(SC_CARRY_THREADS), 0, stream, S.nspans, static_cast<const int64_t*>(S.a0), static_cast<int64_t*>(S.a1),
                        S.hdr, pinned, seq);
     return hipGetLastError();

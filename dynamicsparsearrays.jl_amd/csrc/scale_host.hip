@@ -42,7 +42,7 @@ void reduce_dev(dsa_mat* h, int32_t orientation, int32_t kind, double* d_out, in
     ExportArea& A = P.sc;
     A.ensure(P.stream, std::max(reduce_scratch_bytes(P.capacity()), scale_scratch_bytes(P.capacity())), 2);      // pinned {error word, sequence number}
     const unsigned long long seq = A.next();
-    LAUNCH("reduce", launch_reduce(P.K(), P.V(), P.O(), P.capacity(), P.col_keys, P.h_ctl->table_len, kind, d_out, n_out,
+    LAUNCH("reduce", launch_reduce(P.view(), kind, d_out, n_out,
                                    stream_nt(P, n_out * (int64_t)sizeof(double)), A.scratch, A.pin, seq, P.stream));
     wait_handover(P, A.pin + 1, seq, "reduce");
     export_verdict(A.pin, "reduce", rows ? "a stored row lies outside size(m)" : "a stored column lies outside size(m)");
@@ -75,7 +75,7 @@ void scale_prepare(dsa_mat* h, const double* d_r, int64_t nr, const double* d_c,
         A.ensure(P.stream, std::max(reduce_scratch_bytes(P.capacity()), scale_scratch_bytes(P.capacity())), 2);
         seq[o] = A.next();
         // colmajor: keys are rows, partitions columns; rowmajor: the other way round
-        LAUNCH("scale (check)", launch_scale_check(P.K(), P.V(), P.O(), P.capacity(), P.sems, P.col_keys, P.h_ctl->table_len, o == 0 ? h->m : h->n,
+        LAUNCH("scale (check)", launch_scale_check(P.view(), o == 0 ? h->m : h->n,
                                                    o == 0 ? h->n : h->m, A.scratch, A.pin, seq[o], P.stream));
     }
     for (int o = 0; o < 2; ++o) wait_handover(*side[o], side[o]->sc.pin + 1, seq[o], "scale (check)");

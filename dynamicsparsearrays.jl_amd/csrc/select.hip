@@ -122,17 +122,15 @@ __global__ __launch_bounds__(256) void k_sel_emit(KeyArr keys, const double* __r
     emit_epilogue(err, lane, wv, s.err, s.ticket, a.pinned, a.seq);
 }
 
-hipError_t launch_select_count(const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,
-                               int64_t table_len, bool dense, const int64_t* d_sel, int64_t nsel, int64_t dim_out, int32_t index_bits,
-                               int64_t base, void* d_ptr, void* scratch, unsigned long long* pinned4, unsigned long long seq,
-                               hipStream_t stream) {
-    if (capacity < 0 || table_len < 0 || nsel < 0 || nsel > INT32_MAX || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
+hipError_t launch_select_count(const SlotView& V, const int64_t* d_sel, int64_t nsel, int64_t dim_out, int32_t index_bits, int64_t base,
+                               void* d_ptr, void* scratch, unsigned long long* pinned4, unsigned long long seq, hipStream_t stream) {
+    if (V.capacity < 0 || V.table_len < 0 || nsel < 0 || nsel > INT32_MAX || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
     const SelScratch s = sel_carve(scratch, nsel);
     hipError_t e = hipMemsetAsync(s.err, 0, 8, stream);
     if (e != hipSuccess) return e;
     if (nsel > 0)
-        hipLaunchKernelGGL(k_key_spans<true>, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, occ, capacity, sems, col_keys, col_live,
-                           table_len, dense || col_live == nullptr, d_sel, nsel, dim_out, s.lo, s.hi, s.choff, s.off, s.err);
+        hipLaunchKernelGGL(k_key_spans<true>, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, stream, V, d_sel, nsel, dim_out, s.lo, s.hi,
+                           s.choff, s.off, s.err);
     if (index_bits == 32)
         hipLaunchKernelGGL(k_sel_scan<int32_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, nsel, base, static_cast<int32_t*>(d_ptr), pinned4, seq);
     else
@@ -140,14 +138,15 @@ hipError_t launch_select_count(const uint64_t* occ, int64_t capacity, const int6
     return hipGetLastError();
 }
 
-hipError_t launch_select_emit(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t nsel, int64_t items,
-                              int64_t total, int64_t dim_in, int32_t index_bits, int64_t base, void* d_idx, double* d_vals, void* scratch,
-                              unsigned long long* pinned2, unsigned long long seq, hipStream_t stream) {
-    if (capacity < 0 || nsel < 1 || items < 1 || total < 1 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
+hipError_t launch_select_emit(const SlotView& V, int64_t nsel, int64_t items, int64_t total, int64_t dim_in, int32_t index_bits, int64_t base,
+                              void* d_idx, double* d_vals, void* scratch, unsigned long long* pinned2, unsigned long long seq,
+                              hipStream_t stream) {
+    if (V.capacity < 0 || nsel < 1 || items < 1 || total < 1 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
     const SelScratch s = sel_carve(scratch, nsel);
     const SelArgs a{d_idx, d_vals, nsel, items, total, dim_in, base, pinned2, seq};
-    dispatch_wide_it(keys.wide, index_bits, [&](auto wide, auto ix) {
-        hipLaunchKernelGGL((k_sel_emit<decltype(wide)::value, decltype(ix)>), dim3(ex_grid(items, 4)), dim3(256), 0, stream, keys, vals, occ, s, a);
+    dispatch_wide_it(V.keys.wide, index_bits, [&](auto wide, auto ix) {
+        hipLaunchKernelGGL((k_sel_emit<decltype(wide)::value, decltype(ix)>), dim3(ex_grid(items, 4)), dim3(256), 0, stream, V.keys, V.vals,
+                           V.occ, s, a);
     });
     return hipGetLastError();
 }

@@ -3,7 +3,7 @@
 //
 // Y[j, 0:k] = sum over the cells of the live partition whose key is sel[j] of val * X[key - 1, 0:k] (keys 1-based, any order, repeats
 // allowed: every occurrence gets its own row).  One wave per selected key, four independent waves per workgroup, no workgroup barrier:
-//   span     export_dev.h: key_span — wave-parallel table search, tombstoned entries behind the partition skipped 64 at a time: the
+//   span     find_dev.h: key_span — wave-parallel table search, tombstoned entries behind the partition skipped 64 at a time: the
 //            cells are the occupied slots of [lo, hi).  Its error is ignored: a key that is < 1, never written or deleted has no live
 //            partition and its row is +0.0 (nothing can be reported without a host wait, and this call makes none).
 //   load     nine bitmap words at a time (spmm_dev.h: mm_load_compact, SPAN form): occupancy words, keys (physical width) and values,
@@ -30,16 +30,12 @@
 //   waves per CU, which is the limiter), no scratch in any of the 12 instantiations (key width x NT x KB).
 #include "selprod.h"
 #include "spmm_dev.h"
-#include "export_dev.h"
 
 namespace dsa {
 
 // x, y: first column of the block (the host adds the block's offset); kc <= KB columns of it exist
 template <bool WIDE, bool NT, int KB>
-__global__ __launch_bounds__(MM_BLOCK) void k_selprod(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ,
-                                                      int64_t capacity, const int64_t* __restrict__ sems,
-                                                      const int64_t* __restrict__ col_keys, const uint8_t* __restrict__ col_live,
-                                                      int64_t table_len, bool dense, const int64_t* __restrict__ sel, int64_t nsel,
+__global__ __launch_bounds__(MM_BLOCK) void k_selprod(SlotView V, const int64_t* __restrict__ sel, int64_t nsel,
                                                       const double* __restrict__ x, int64_t nx, int64_t ldx, double* __restrict__ y,
                                                       int64_t ldy, int kc) {
     typedef typename std::conditional<WIDE, int64_t, int32_t>::type key_t;
@@ -48,7 +44,9 @@ __global__ __launch_bounds__(MM_BLOCK) void k_selprod(KeyArr keys, const double*
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t j = (int64_t)blockIdx.x * MM_WAVES + wv;
     if (j >= nsel) return;                                   // (whole waves: nothing below waits for another wave)
-    const key_t* __restrict__ kp = static_cast<const key_t*>(keys.p);
+    const key_t* __restrict__ kp = static_cast<const key_t*>(V.keys.p);
+    const double* __restrict__ vals = V.vals;
+    const uint64_t* __restrict__ occ = V.occ;
     MmWave<key_t>& S = sW[wv];
     const int col = lane % KB;
     const bool walker = lane < KB;                           // the lanes that sum: one per column
@@ -56,7 +54,7 @@ __global__ __launch_bounds__(MM_BLOCK) void k_selprod(KeyArr keys, const double*
     const double* __restrict__ xcol = x + (colok ? col : 0);
 
     // any key may own a live partition (also one beyond size(m)): the table decides
-    const KeySpan sp = key_span(capacity, sems, col_keys, col_live, table_len, dense, sel[j], INT64_MAX, lane);
+    const KeySpan sp = key_span(V, sel[j], INT64_MAX, lane);
     const int64_t lo = sp.lo, hi = nx > 0 ? sp.hi : sp.lo;   // nx = 0: nothing can contribute (and X may be NULL)
     double sum = 0.0;
     if (hi > lo) {
@@ -74,31 +72,25 @@ __global__ __launch_bounds__(MM_BLOCK) void k_selprod(KeyArr keys, const double*
 }
 
 template <bool WIDE, bool NT>
-static void launch_selprod_block(unsigned grid, hipStream_t stream, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                                 const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live, int64_t table_len, bool dense,
-                                 const int64_t* d_sel, int64_t nsel, const double* x, int64_t nx, int64_t ldx, double* y, int64_t ldy,
-                                 int kc) {
-#define DSA_SELPROD_CASE(KB_) hipLaunchKernelGGL((k_selprod<WIDE, NT, KB_>), dim3(grid), dim3(MM_BLOCK), 0, stream, keys, vals, occ, \
-                                                 capacity, sems, col_keys, col_live, table_len, dense, d_sel, nsel, x, nx, ldx, y, ldy, kc)
+static void launch_selprod_block(unsigned grid, hipStream_t stream, const SlotView& V, const int64_t* d_sel, int64_t nsel, const double* x,
+                                 int64_t nx, int64_t ldx, double* y, int64_t ldy, int kc) {
+#define DSA_SELPROD_CASE(KB_) hipLaunchKernelGGL((k_selprod<WIDE, NT, KB_>), dim3(grid), dim3(MM_BLOCK), 0, stream, V, d_sel, nsel, x, nx, \
+                                                 ldx, y, ldy, kc)
     if (kc <= 4) DSA_SELPROD_CASE(4);
     else if (kc <= 8) DSA_SELPROD_CASE(8);
     else DSA_SELPROD_CASE(16);
 #undef DSA_SELPROD_CASE
 }
 
-hipError_t launch_selprod(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems,
-                          const int64_t* col_keys, const uint8_t* col_live, int64_t table_len, bool dense, const int64_t* d_sel,
-                          int64_t nsel, const double* x, int64_t nx, int64_t k, int64_t ldx, double* y, int64_t ldy, bool nt,
-                          hipStream_t stream) {
-    if (capacity < 0 || table_len < 0 || nsel < 0 || nsel > INT32_MAX) return hipErrorInvalidValue;
+hipError_t launch_selprod(const SlotView& V, const int64_t* d_sel, int64_t nsel, const double* x, int64_t nx, int64_t k, int64_t ldx,
+                          double* y, int64_t ldy, bool nt, hipStream_t stream) {
+    if (V.capacity < 0 || V.table_len < 0 || nsel < 0 || nsel > INT32_MAX) return hipErrorInvalidValue;
     if (nsel == 0 || k <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((nsel + MM_WAVES - 1) / MM_WAVES);
-    dense = dense || col_live == nullptr;
     for (int64_t jb = 0; jb < k; jb += 16) {
         const int kc = (int)(k - jb < 16 ? k - jb : 16);
-        const int which = (keys.wide ? 2 : 0) | (nt ? 1 : 0);
-#define DSA_SELPROD_BLOCK(W_, N_) launch_selprod_block<W_, N_>(grid, stream, keys, vals, occ, capacity, sems, col_keys, col_live, table_len, \
-                                                               dense, d_sel, nsel, x + jb, nx, ldx, y + jb, ldy, kc)
+        const int which = (V.keys.wide ? 2 : 0) | (nt ? 1 : 0);
+#define DSA_SELPROD_BLOCK(W_, N_) launch_selprod_block<W_, N_>(grid, stream, V, d_sel, nsel, x + jb, nx, ldx, y + jb, ldy, kc)
         switch (which) {
             case 0: DSA_SELPROD_BLOCK(false, false); break;
             case 1: DSA_SELPROD_BLOCK(false, true); break;

@@ -32,9 +32,7 @@ void selprod_dev(dsa_mat* h, int32_t transpose, const int64_t* d_sel, int64_t ns
     Pma& P = transpose ? h->col : h->row;
     // the slot stream goes around the cache when X does not fit an XCD's 4 MB L2 beside it (the rule of spmm_dev)
     const bool nt = nx * k * (int64_t)sizeof(double) > (3 << 20);
-    const Ctl& c = *P.h_ctl;
-    LAUNCH("selected product", launch_selprod(P.K(), P.V(), P.O(), c.capacity, P.sems, P.col_keys, P.col_live, c.table_len,
-                                              c.nb_partitions == c.table_len, d_sel, nsel, d_x, nx, k, ldx, d_y, ldy, nt, s));
+    LAUNCH("selected product", launch_selprod(P.view(), d_sel, nsel, d_x, nx, k, ldx, d_y, ldy, nt, s));
 }
 
 // the same with the keys, X and Y in host memory: packed device staging (leading dimension k), one stream sync at the end

@@ -3,8 +3,8 @@
 //
 // Round 6 form.  Two persistent arrays per matrix with a ZERO INVARIANT (all zero between two products): acc[ny] (Float64 sums) and
 // bm[ny / 64] (one bit per touched row).  A product is three launches, no memset, no copy command in between:
-//   k_spx_accum   one wave per stored x entry: locate the column (direct hit when the column table is the identity up to the entry,
-//                 else the 64-ary search), walk its slot range, acc[row] += x_j * a with fp64 atomics, bm |= bit(row)
+//   k_spx_accum   one wave per stored x entry: locate the column (direct hit when the column table is the identity at the entry,
+//                 else find_dev.h: live_span, the lookup of the exports and products), walk its slot range, acc[row] += x_j * a with fp64 atomics, bm |= bit(row)
 //   k_spx_count   touched rows per 4096-row tile from the bitmap; the workgroup that finishes last (ticket) turns the counts into
 //                 exclusive prefixes and the total
 //   k_spx_emit    (row, acc[row]) pairs in ascending row order into the packed result (HBM; the first cells also straight into a
@@ -17,70 +17,35 @@
 #include <algorithm>
 #include <cstdint>
 #include <mutex>
-#include "wave_dev.h"
+#include "find_dev.h"
 
 namespace dsa {
 
-// ---- locate: the slot range [from, to] (1-based, inclusive) of the live column with key `col`; false: there is none.  Called by a
-// whole wave with a wave-uniform `col`.
-__device__ __forceinline__ bool spx_locate(int64_t col, int lane, int64_t capacity, const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
-                                           const uint8_t* __restrict__ col_live, int64_t table_len, int64_t& from, int64_t& to) {
+// ---- locate: the slot range [from, to] (1-based, inclusive) of the cells of the live column with key `col`; from > to: there is none
+// (no such column: the x entry is skipped, src/operations.jl:76-79).  Called by a whole wave with a wave-uniform `col`.
+__device__ __forceinline__ void spx_locate(const SlotView& V, int64_t col, int lane, int64_t& from, int64_t& to) {
     // Direct hit first: a table without holes in front of `col` has the column at index col (ids are positions, keys ascend: a
     // matrix whose columns are 1..n, the usual case).  Everything the hit needs is requested in ONE round: key, liveness, the
     // column's semaphore and the next one.
-    int64_t pos = 0;
-    from = 0; to = 0;
-    bool have = false;
-    if (col >= 1 && col <= table_len) {
-        const int64_t ck = col_keys[col - 1];
-        const uint8_t lv = col_live[col - 1];
-        const int64_t s0 = sems[col - 1];
-        const int64_t s1 = col < table_len ? sems[col] : 0;
-        if (ck == col && lv && s0 != 0) {
-            pos = col; from = s0 + 1; have = true;
-            if (col == table_len) to = capacity;
-            else if (s1 != 0) to = s1 - 1;
-            else have = false;                      // a tombstone behind it: the general walk below
+    if (col >= 1 && col <= V.table_len) {
+        const int64_t ck = V.part_keys[col - 1];
+        const bool lv = V.dense || V.part_live[col - 1];
+        const int64_t s0 = V.sems[col - 1];
+        const int64_t s1 = col < V.table_len ? V.sems[col] : 0;
+        if (ck == col && lv && s0 != 0 && (col == V.table_len || s1 != 0)) {
+            from = s0 + 1; to = col == V.table_len ? V.capacity : s1 - 1;
+            return;
         }
     }
-    if (!have) {
-        // largest live table index with col_keys <= col  (64-ary narrowing; live keys ascend with the index)
-        int64_t L = 0, H = table_len;
-        while (H - L > 64) {
-            const int64_t width = H - L;
-            const int64_t p = L + (width * (lane + 1)) / 64;
-            int64_t q = p;
-            while (q > L && !col_live[q - 1]) --q;
-            bool pr = true;
-            if (q > L) pr = col_keys[q - 1] <= col;
-            const uint64_t nb = ~__ballot(pr);
-            const int j = nb ? __ffsll((unsigned long long)nb) - 1 : 64;
-            const int64_t pj = L + (width * (j + 1)) / 64;
-            const int64_t pj1 = L + (width * j) / 64;
-            if (j < 64) H = pj - 1;
-            L = pj1;
-        }
-        const int64_t p = L + 1 + lane;
-        bool viol = false;
-        if (p <= H && col_live[p - 1]) viol = col_keys[p - 1] > col;
-        const uint64_t b = __ballot(viol);
-        pos = b ? L + __ffsll((unsigned long long)b) - 1 : H;
-        while (pos > 0 && !col_live[pos - 1]) --pos;
-        if (pos == 0 || col_keys[pos - 1] != col) return false;      // no such column: x entry skipped (src/operations.jl:76-79)
-        from = sems[pos - 1] + 1;
-        int64_t nxt = pos + 1;
-        while (nxt <= table_len && sems[nxt - 1] == 0) ++nxt;
-        to = nxt <= table_len ? sems[nxt - 1] - 1 : capacity;
-    }
-    return true;
+    // the table is not the identity at `col`, or a tombstone follows the column: the shared lookup (find_dev.h); any key may own a
+    // live partition, also one below 1, and a span the tables do not bear out is no span
+    const KeySpan sp = live_span(V, col, lane);
+    from = sp.lo + 1; to = sp.hi;
 }
 
 // ---- accumulate ---------------------------------------------------------------------------------------------------------------
 // x entries come from HBM or straight from pinned host memory (few entries: no copy command in front of the launch).
-__global__ __launch_bounds__(256) void k_spx_accum(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ, int64_t capacity,
-                                                   const int64_t* __restrict__ sems, const int64_t* __restrict__ col_keys,
-                                                   const uint8_t* __restrict__ col_live, int64_t table_len,
-                                                   const int64_t* __restrict__ xi, const double* __restrict__ xv, int64_t nx,
+__global__ __launch_bounds__(256) void k_spx_accum(SlotView V, const int64_t* __restrict__ xi, const double* __restrict__ xv, int64_t nx,
                                                    double* __restrict__ acc, unsigned long long* __restrict__ bm, int64_t ny) {
     const int lane = threadIdx.x & 63;
     const int64_t e = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -88,12 +53,12 @@ __global__ __launch_bounds__(256) void k_spx_accum(KeyArr keys, const double* __
     const int64_t col = xi[e];
     const double xval = xv[e];
     int64_t from, to;
-    if (!spx_locate(col, lane, capacity, sems, col_keys, col_live, table_len, from, to)) return;
+    spx_locate(V, col, lane, from, to);
     for (int64_t s = from + lane; s <= to; s += 64) {
-        if ((occ[(s - 1) >> 6] >> ((s - 1) & 63)) & 1ull) {
-            const int64_t row = keys[s - 1];
+        if (occ_test(V.occ, s)) {
+            const int64_t row = V.keys[s - 1];
             if (row >= 1 && row <= ny) {
-                atomicAdd(&acc[row - 1], xval * vals[s - 1]);
+                atomicAdd(&acc[row - 1], xval * V.vals[s - 1]);
                 atomicOr(&bm[(row - 1) >> 6], 1ull << ((row - 1) & 63));
             }
         }
@@ -117,10 +82,7 @@ __global__ __launch_bounds__(256) void k_spx_pattern_bits(const double* __restri
 // over its own partition of the twin, cells of columns x does not store left out (xf = the 0/1 pattern of x).  One wave per 64 rows,
 // lane <-> row; a finite y had no such cell (its product would be NaN) and is what it was.  Non-finite rows are the rare case: the
 // kernel reads pattern and y once and ends.
-__global__ __launch_bounds__(256) void k_spx_repair(KeyArr keys, const double* __restrict__ vals, const uint64_t* __restrict__ occ, int64_t capacity,
-                                                    const int64_t* __restrict__ sems, const int64_t* __restrict__ part_keys,
-                                                    const uint8_t* __restrict__ part_live, int64_t table_len,
-                                                    const double* __restrict__ xd, const double* __restrict__ xf, int64_t nx,
+__global__ __launch_bounds__(256) void k_spx_repair(SlotView V, const double* __restrict__ xd, const double* __restrict__ xf, int64_t nx,
                                                     const double* __restrict__ pattern, double* __restrict__ y, int64_t ny) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -134,12 +96,11 @@ __global__ __launch_bounds__(256) void k_spx_repair(KeyArr keys, const double* _
         const int64_t row = (w << 6) + l + 1;
         int64_t from, to;
         double sum = 0.0;
-        if (spx_locate(row, lane, capacity, sems, part_keys, part_live, table_len, from, to)) {
-            for (int64_t s = from + lane; s <= to; s += 64) {
-                if ((occ[(s - 1) >> 6] >> ((s - 1) & 63)) & 1ull) {
-                    const int64_t c = keys[s - 1];
-                    if (c >= 1 && c <= nx && xf[c - 1] != 0.0) sum += vals[s - 1] * xd[c - 1];
-                }
+        spx_locate(V, row, lane, from, to);
+        for (int64_t s = from + lane; s <= to; s += 64) {
+            if (occ_test(V.occ, s)) {
+                const int64_t c = V.keys[s - 1];
+                if (c >= 1 && c <= nx && xf[c - 1] != 0.0) sum += V.vals[s - 1] * xd[c - 1];
             }
         }
         sum = wave_reduce_add(sum);
@@ -247,12 +208,11 @@ __global__ __launch_bounds__(64) void k_spx_emit(unsigned long long* __restrict_
     }
 }
 
-hipError_t launch_spx_accum(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys,
-                            const uint8_t* col_live, int64_t table_len, const int64_t* xi, const double* xv, int64_t nx, double* acc,
-                            uint64_t* bm, int64_t ny, hipStream_t stream) {
+hipError_t launch_spx_accum(const SlotView& V, const int64_t* xi, const double* xv, int64_t nx, double* acc, uint64_t* bm, int64_t ny,
+                            hipStream_t stream) {
     if (nx <= 0 || ny <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spx_accum, dim3((unsigned)((nx + 3) / 4)), dim3(256), 0, stream, keys, vals, occ, capacity, sems, col_keys, col_live,
-                       table_len, xi, xv, nx, acc, reinterpret_cast<unsigned long long*>(bm), ny);
+    hipLaunchKernelGGL(k_spx_accum, dim3((unsigned)((nx + 3) / 4)), dim3(256), 0, stream, V, xi, xv, nx, acc,
+                       reinterpret_cast<unsigned long long*>(bm), ny);
     return hipGetLastError();
 }
 hipError_t launch_spx_pattern_bits(const double* pattern, int64_t ny, uint64_t* bm, hipStream_t stream) {
@@ -261,13 +221,11 @@ hipError_t launch_spx_pattern_bits(const double* pattern, int64_t ny, uint64_t* 
     hipLaunchKernelGGL(k_spx_pattern_bits, dim3((unsigned)((nwords + 3) / 4)), dim3(256), 0, stream, pattern, ny, reinterpret_cast<unsigned long long*>(bm), nwords);
     return hipGetLastError();
 }
-hipError_t launch_spx_repair(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* part_keys,
-                             const uint8_t* part_live, int64_t table_len, const double* xd, const double* xf, int64_t nx, const double* pattern,
-                             double* y, int64_t ny, hipStream_t stream) {
+hipError_t launch_spx_repair(const SlotView& V, const double* xd, const double* xf, int64_t nx, const double* pattern, double* y, int64_t ny,
+                             hipStream_t stream) {
     const int64_t nwords = (ny + 63) >> 6;
     if (nwords <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_spx_repair, dim3((unsigned)((nwords + 3) / 4)), dim3(256), 0, stream, keys, vals, occ, capacity, sems, part_keys, part_live,
-                       table_len, xd, xf, nx, pattern, y, ny);
+    hipLaunchKernelGGL(k_spx_repair, dim3((unsigned)((nwords + 3) / 4)), dim3(256), 0, stream, V, xd, xf, nx, pattern, y, ny);
     return hipGetLastError();
 }
 // count + emit (a single-workgroup count + emit for small products was measured: 30 vs 15 us per product — dropped); scratch = the caller's (tile_cnt, tile_off [ntiles + 1], ticket [2 words, zero between launches])

@@ -27,17 +27,16 @@ int64_t spgemm_slab_words(int64_t ny);
 
 // Phase 1 (one memset, k_spg_bound, k_spg_classify): the input contract, the span and the cell count of every stored entry of S,
 // the cells each column will visit, the list of the long columns.  {error bits, long columns} and then `seq` go to pinned3.
-hipError_t launch_spgemm_bound(const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,
-                               int64_t table_len, bool dense, SpgIndex ix, const void* d_xptr, const void* d_xidx, int64_t k, int64_t nnzx,
-                               void* scratch, unsigned long long* pinned3, unsigned long long seq, hipStream_t stream);
+hipError_t launch_spgemm_bound(const SlotView& V, SpgIndex ix, const void* d_xptr, const void* d_xidx, int64_t k, int64_t nnzx, void* scratch,
+                               unsigned long long* pinned3, unsigned long long seq, hipStream_t stream);
 // Phase 2 (k_spg_lds<count>, k_spg_slab<count> when n_large > 0, k_spg_scan) on the scratch phase 1 left: touched rows per column,
 // yptr[k + 1]; {error bits, total} and then `seq` go to pinned3.  slabs: nslabs slabs, all zero, left all zero.
-hipError_t launch_spgemm_count(KeyArr keys, const uint64_t* occ, int64_t k, int64_t nnzx, int64_t ny, int64_t n_large, uint64_t* slabs,
+hipError_t launch_spgemm_count(const SlotView& V, int64_t k, int64_t nnzx, int64_t ny, int64_t n_large, uint64_t* slabs,
                                int64_t nslabs, SpgIndex ix, void* d_yptr, void* scratch, unsigned long long* pinned3, unsigned long long seq,
                                hipStream_t stream);
 // Phase 3 (k_spg_lds<emit>, k_spg_slab<emit> when n_large > 0, k_spg_done): yidx / yval[total]; {error bits} and then `seq` go to
 // pinned2.  total > 0.
-hipError_t launch_spgemm_emit(KeyArr keys, const double* vals, const uint64_t* occ, const double* d_xval, int64_t k, int64_t nnzx, int64_t ny,
+hipError_t launch_spgemm_emit(const SlotView& V, const double* d_xval, int64_t k, int64_t nnzx, int64_t ny,
                               int64_t n_large, uint64_t* slabs, int64_t nslabs, SpgIndex ix, void* d_yidx, double* d_yval, void* scratch,
                               unsigned long long* pinned2, unsigned long long seq, hipStream_t stream);
 

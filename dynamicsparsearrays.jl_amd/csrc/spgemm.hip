@@ -5,7 +5,7 @@
 //
 // A two-phase (count, then emit) row-wise Gustavson product in three groups of launches with a host wait behind each:
 //   k_spg_bound     one wave per stored entry of S: its column (search over xptr), the input contract (xidx strictly ascending within
-//                   a column; xptr checked by one thread per column), the span of the partition its key names (export_dev.h:
+//                   a column; xptr checked by one thread per column), the span of the partition its key names (find_dev.h:
 //                   key_span, the lookup of the selected export), the popcount of the span; (lo, hi, cells) per entry go to scratch so
 //                   that no later pass locates again, ub[c] += cells (integer atomics)
 //   k_spg_classify  one workgroup: the columns with ub > SPG_SMALL_MAX go on the list of the long ones; {error, long columns} handed over
@@ -65,9 +65,7 @@ __device__ __forceinline__ int64_t spg_ld(const void* p, int64_t i, int bits32) 
 
 // ---- phase 1 --------------------------------------------------------------------------------------------------------------------
 // virtual workgroups [0, eblocks): four entries each, one wave per entry; [eblocks, eblocks + cblocks): 256 column boundaries each
-__global__ __launch_bounds__(256) void k_spg_bound(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
-                                                   const int64_t* __restrict__ col_keys, const uint8_t* __restrict__ col_live,
-                                                   int64_t table_len, bool dense, SpgIndex ix, const void* __restrict__ xptr,
+__global__ __launch_bounds__(256) void k_spg_bound(SlotView V, SpgIndex ix, const void* __restrict__ xptr,
                                                    const void* __restrict__ xidx, int64_t k, int64_t nnzx, SpgScratch s, int64_t eblocks,
                                                    int64_t cblocks) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -100,10 +98,10 @@ __global__ __launch_bounds__(256) void k_spg_bound(const uint64_t* __restrict__ 
             const int64_t key = spg_ld(xidx, e, ix.bits32) + 1 - ix.base;
             if (e > 0 && e > spg_ld(xptr, c, ix.bits32) - ix.base && spg_ld(xidx, e - 1, ix.bits32) + 1 - ix.base >= key) err = SPG_ERR_INPUT;
             // a key without a live partition (never written, deleted, beyond the table, below 1) contributes nothing
-            const KeySpan sp = key_span(capacity, sems, col_keys, col_live, table_len, dense, key, INT64_MAX, lane);
+            const KeySpan sp = key_span(V, key, INT64_MAX, lane);
             if (sp.err & 2u) err |= SPG_ERR_STEP;
             lo = sp.lo; hi = sp.hi;
-            cells = hi > lo ? sel_span_popc(occ, lo, hi, lane) : 0;
+            cells = hi > lo ? sel_span_popc(V.occ, lo, hi, lane) : 0;
         }
         if (lane != 0) continue;
         s.lo[e] = lo; s.hi[e] = hi; s.cells[e] = cells;
@@ -325,31 +323,29 @@ __global__ void k_spg_done(SpgScratch s, unsigned long long* pinned, unsigned lo
 // ---- launches ---------------------------------------------------------------------------------------------------------------------
 static bool spg_shape_ok(int64_t k, int64_t nnzx) { return k >= 0 && k <= INT32_MAX && nnzx >= 0 && nnzx <= INT32_MAX; }
 
-hipError_t launch_spgemm_bound(const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,
-                               int64_t table_len, bool dense, SpgIndex ix, const void* d_xptr, const void* d_xidx, int64_t k, int64_t nnzx,
-                               void* scratch, unsigned long long* pinned3, unsigned long long seq, hipStream_t stream) {
-    if (capacity < 0 || table_len < 0 || !spg_shape_ok(k, nnzx)) return hipErrorInvalidValue;
+hipError_t launch_spgemm_bound(const SlotView& V, SpgIndex ix, const void* d_xptr, const void* d_xidx, int64_t k, int64_t nnzx, void* scratch,
+                               unsigned long long* pinned3, unsigned long long seq, hipStream_t stream) {
+    if (V.capacity < 0 || V.table_len < 0 || !spg_shape_ok(k, nnzx)) return hipErrorInvalidValue;
     const SpgScratch s = spg_carve(scratch, k, nnzx);
     hipError_t e = hipMemsetAsync(scratch, 0, 16 + (size_t)k * 8, stream);
     if (e != hipSuccess) return e;
     const int64_t eblocks = (nnzx + 3) / 4, cblocks = (k + 1 + 255) / 256;
     const int64_t grid = eblocks + cblocks < SPG_GRID_MAX ? eblocks + cblocks : SPG_GRID_MAX;
-    hipLaunchKernelGGL(k_spg_bound, dim3((unsigned)grid), dim3(256), 0, stream, occ, capacity, sems, col_keys, col_live, table_len,
-                       dense || col_live == nullptr, ix, d_xptr, d_xidx, k, nnzx, s, eblocks, cblocks);
+    hipLaunchKernelGGL(k_spg_bound, dim3((unsigned)grid), dim3(256), 0, stream, V, ix, d_xptr, d_xidx, k, nnzx, s, eblocks, cblocks);
     hipLaunchKernelGGL(k_spg_classify, dim3(1), dim3(1024), 0, stream, s, k, pinned3, seq);
     return hipGetLastError();
 }
 
-hipError_t launch_spgemm_count(KeyArr keys, const uint64_t* occ, int64_t k, int64_t nnzx, int64_t ny, int64_t n_large, uint64_t* slabs,
+hipError_t launch_spgemm_count(const SlotView& V, int64_t k, int64_t nnzx, int64_t ny, int64_t n_large, uint64_t* slabs,
                                int64_t nslabs, SpgIndex ix, void* d_yptr, void* scratch, unsigned long long* pinned3, unsigned long long seq,
                                hipStream_t stream) {
     if (!spg_shape_ok(k, nnzx) || ny < 0 || n_large < 0 || n_large > k || (n_large > 0 && (nslabs < 1 || !slabs))) return hipErrorInvalidValue;
     const SpgScratch s = spg_carve(scratch, k, nnzx);
     if (k > 0)
-        hipLaunchKernelGGL(k_spg_lds<false>, dim3((unsigned)(k < SPG_GRID_MAX ? k : SPG_GRID_MAX)), dim3(64), 0, stream, keys, nullptr, occ, s,
+        hipLaunchKernelGGL(k_spg_lds<false>, dim3((unsigned)(k < SPG_GRID_MAX ? k : SPG_GRID_MAX)), dim3(64), 0, stream, V.keys, nullptr, V.occ, s,
                            nullptr, k, ny, ix, nullptr, nullptr);
     if (n_large > 0)
-        hipLaunchKernelGGL(k_spg_slab<false>, dim3((unsigned)nslabs), dim3(256), 0, stream, keys, nullptr, occ, s, nullptr, ny,
+        hipLaunchKernelGGL(k_spg_slab<false>, dim3((unsigned)nslabs), dim3(256), 0, stream, V.keys, nullptr, V.occ, s, nullptr, ny,
                            reinterpret_cast<unsigned long long*>(slabs), spgemm_slab_words(ny), ix, nullptr, nullptr);
     if (ix.bits32)
         hipLaunchKernelGGL(k_spg_scan<int32_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, k, ix.base, static_cast<int32_t*>(d_yptr), pinned3, seq);
@@ -358,16 +354,16 @@ hipError_t launch_spgemm_count(KeyArr keys, const uint64_t* occ, int64_t k, int6
     return hipGetLastError();
 }
 
-hipError_t launch_spgemm_emit(KeyArr keys, const double* vals, const uint64_t* occ, const double* d_xval, int64_t k, int64_t nnzx, int64_t ny,
+hipError_t launch_spgemm_emit(const SlotView& V, const double* d_xval, int64_t k, int64_t nnzx, int64_t ny,
                               int64_t n_large, uint64_t* slabs, int64_t nslabs, SpgIndex ix, void* d_yidx, double* d_yval, void* scratch,
                               unsigned long long* pinned2, unsigned long long seq, hipStream_t stream) {
     if (!spg_shape_ok(k, nnzx) || k < 1 || ny < 1 || n_large < 0 || n_large > k || (n_large > 0 && (nslabs < 1 || !slabs)) || !d_yidx || !d_yval)
         return hipErrorInvalidValue;
     const SpgScratch s = spg_carve(scratch, k, nnzx);
-    hipLaunchKernelGGL(k_spg_lds<true>, dim3((unsigned)(k < SPG_GRID_MAX ? k : SPG_GRID_MAX)), dim3(64), 0, stream, keys, vals, occ, s, d_xval, k,
+    hipLaunchKernelGGL(k_spg_lds<true>, dim3((unsigned)(k < SPG_GRID_MAX ? k : SPG_GRID_MAX)), dim3(64), 0, stream, V.keys, V.vals, V.occ, s, d_xval, k,
                        ny, ix, d_yidx, d_yval);
     if (n_large > 0)
-        hipLaunchKernelGGL(k_spg_slab<true>, dim3((unsigned)nslabs), dim3(256), 0, stream, keys, vals, occ, s, d_xval, ny,
+        hipLaunchKernelGGL(k_spg_slab<true>, dim3((unsigned)nslabs), dim3(256), 0, stream, V.keys, V.vals, V.occ, s, d_xval, ny,
                            reinterpret_cast<unsigned long long*>(slabs), spgemm_slab_words(ny), ix, d_yidx, d_yval);
     hipLaunchKernelGGL(k_spg_done, dim3(1), dim3(1), 0, stream, s, pinned2, seq);
     return hipGetLastError();

@@ -49,10 +49,7 @@ SpgTotals spgemm_count(const SpgSide& e, int32_t index_bits, int32_t index_base,
     // {error word, sequence number} of the emit
     A.ensure(P.stream, spgemm_scratch_bytes(k, nnzx), 8);
     unsigned long long seq = A.next();
-    const Ctl& c = *P.h_ctl;
-    LAUNCH("sparse product (bound)", launch_spgemm_bound(P.O(), c.capacity, P.sems, P.col_keys, P.col_live, c.table_len,
-                                                         c.nb_partitions == c.table_len, ix, d_xptr, d_xidx, k, nnzx, A.scratch, A.pin, seq,
-                                                         P.stream));
+    LAUNCH("sparse product (bound)", launch_spgemm_bound(P.view(), ix, d_xptr, d_xidx, k, nnzx, A.scratch, A.pin, seq, P.stream));
     wait_handover(P, A.pin + 2, seq, "sparse product (bound)");
     spgemm_verdict(A.pin);
     SpgTotals t;
@@ -71,7 +68,7 @@ SpgTotals spgemm_count(const SpgSide& e, int32_t index_bits, int32_t index_base,
         }
     }
     seq = A.next();
-    LAUNCH("sparse product (count)", launch_spgemm_count(P.K(), P.O(), k, nnzx, e.ny, t.n_large, static_cast<uint64_t*>(P.spgs.scratch), t.nslabs,
+    LAUNCH("sparse product (count)", launch_spgemm_count(P.view(), k, nnzx, e.ny, t.n_large, static_cast<uint64_t*>(P.spgs.scratch), t.nslabs,
                                                          ix, d_yptr, A.scratch, A.pin + 3, seq, P.stream));
     wait_handover(P, A.pin + 5, seq, "sparse product (count)");
     spgemm_verdict(A.pin + 3);
@@ -89,7 +86,7 @@ void spgemm_emit(const SpgSide& e, const SpgTotals& t, int32_t index_bits, int32
     ExportArea& A = P.spg;
     const SpgIndex ix{index_bits == 32 ? 1 : 0, 0, index_base};
     const unsigned long long seq = A.next();
-    LAUNCH("sparse product (emit)", launch_spgemm_emit(P.K(), P.V(), P.O(), d_xval, k, nnzx, e.ny, t.n_large, static_cast<uint64_t*>(P.spgs.scratch),
+    LAUNCH("sparse product (emit)", launch_spgemm_emit(P.view(), d_xval, k, nnzx, e.ny, t.n_large, static_cast<uint64_t*>(P.spgs.scratch),
                                                        t.nslabs, ix, d_yidx, d_yval, A.scratch, A.pin + 6, seq, P.stream));
     wait_handover(P, A.pin + 7, seq, "sparse product (emit)");
     spgemm_verdict(A.pin + 6);

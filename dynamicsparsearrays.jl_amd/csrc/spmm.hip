@@ -99,11 +99,10 @@ __global__ __launch_bounds__(MM_BLOCK) void k_spmm(KeyArr keys, const double* __
 }
 
 template <bool WIDE, bool NT>
-static void launch_spmm_block(unsigned grid, hipStream_t stream, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                              const int64_t* part_keys, int64_t table_len, const double* x, int64_t nx, int64_t ldx, double* y, int64_t ny,
-                              int64_t ldy, int kc) {
-#define DSA_SPMM_CASE(KB_) hipLaunchKernelGGL((k_spmm<WIDE, NT, KB_>), dim3(grid), dim3(MM_BLOCK), 0, stream, keys, vals, occ, capacity, \
-                                              part_keys, table_len, x, nx, ldx, y, ny, ldy, kc)
+static void launch_spmm_block(unsigned grid, hipStream_t stream, const SlotView& V, const double* x, int64_t nx, int64_t ldx, double* y,
+                              int64_t ny, int64_t ldy, int kc) {
+#define DSA_SPMM_CASE(KB_) hipLaunchKernelGGL((k_spmm<WIDE, NT, KB_>), dim3(grid), dim3(MM_BLOCK), 0, stream, V.keys, V.vals, V.occ, V.capacity, \
+                                              V.part_keys, V.table_len, x, nx, ldx, y, ny, ldy, kc)
     if (kc <= 4) DSA_SPMM_CASE(4);
     else if (kc <= 8) DSA_SPMM_CASE(8);
     else DSA_SPMM_CASE(16);
@@ -111,15 +110,15 @@ static void launch_spmm_block(unsigned grid, hipStream_t stream, KeyArr keys, co
 }
 
 // Y[:, 0:k] = P X[:, 0:k]; Y is NOT zeroed here (rows without a partition keep what they hold).  nt: non-temporal slot loads.
-hipError_t launch_spmm(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* part_keys, int64_t table_len,
-                       const double* x, int64_t nx, int64_t k, int64_t ldx, double* y, int64_t ny, int64_t ldy, bool nt, hipStream_t stream) {
-    if (capacity <= 0 || k <= 0) return hipSuccess;
-    const int64_t ntiles = (capacity + MM_TILE - 1) / MM_TILE;
+hipError_t launch_spmm(const SlotView& V, const double* x, int64_t nx, int64_t k, int64_t ldx, double* y, int64_t ny, int64_t ldy, bool nt,
+                       hipStream_t stream) {
+    if (V.capacity <= 0 || k <= 0) return hipSuccess;
+    const int64_t ntiles = (V.capacity + MM_TILE - 1) / MM_TILE;
     const unsigned grid = (unsigned)(ntiles >= 64 ? 8 * ((ntiles + 7) / 8) : ntiles);
     for (int64_t jb = 0; jb < k; jb += 16) {
         const int kc = (int)(k - jb < 16 ? k - jb : 16);
-        const int sel = (keys.wide ? 2 : 0) | (nt ? 1 : 0);
-#define DSA_SPMM_BLOCK(W_, N_) launch_spmm_block<W_, N_>(grid, stream, keys, vals, occ, capacity, part_keys, table_len, x + jb, nx, ldx, y + jb, ny, ldy, kc)
+        const int sel = (V.keys.wide ? 2 : 0) | (nt ? 1 : 0);
+#define DSA_SPMM_BLOCK(W_, N_) launch_spmm_block<W_, N_>(grid, stream, V, x + jb, nx, ldx, y + jb, ny, ldy, kc)
         switch (sel) {
             case 0: DSA_SPMM_BLOCK(false, false); break;
             case 1: DSA_SPMM_BLOCK(false, true); break;

@@ -23,7 +23,7 @@ void spmm_dev(dsa_mat* h, int32_t transpose, const double* d_x, int64_t nx, int6
     Pma& P = transpose ? h->col : h->row;
     // the slot stream goes around the cache when X does not fit an XCD's 4 MB L2 beside it (the rule of SPMV_PLAIN_STREAM)
     const bool nt = nx * k * (int64_t)sizeof(double) > (3 << 20);
-    LAUNCH("spmm", launch_spmm(P.K(), P.V(), P.O(), P.capacity(), P.col_keys, P.h_ctl->table_len, d_x, nx, k, ldx, d_y, ny, ldy, nt, s));
+    LAUNCH("spmm", launch_spmm(P.view(), d_x, nx, k, ldx, d_y, ny, ldy, nt, s));
 }
 
 // the same with X and Y in host memory: packed device staging (leading dimension k), one stream sync at the end

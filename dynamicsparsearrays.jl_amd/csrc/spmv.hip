@@ -589,57 +589,56 @@ __global__ __launch_bounds__(256) void k_spmv_meta(const int64_t* __restrict__ s
         __hip_atomic_store(ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
-hipError_t launch_spmv_meta(const int64_t* sems, const int64_t* part_keys, int64_t table_len, int64_t capacity,
-                            unsigned long long* scratch, unsigned long long* out6_pinned, unsigned long long seq, hipStream_t stream) {
+hipError_t launch_spmv_meta(const SlotView& V, unsigned long long* scratch, unsigned long long* out6_pinned, unsigned long long seq,
+                            hipStream_t stream) {
+    const int64_t table_len = V.table_len;
     if (table_len <= 0) return hipErrorInvalidValue;
     // four entries per thread and step; beyond 256 workgroups the count grows with the table only slowly (1 M entries: 256 workgroups
     // x 4 steps 12-15 us, 977 x 1 step 18-20 us, 64 x 16 steps 26-33 us: every workgroup costs a partial + a ticket at device scope)
     int64_t blocks = (table_len + 1023) / 1024;
     if (blocks > 256) blocks = std::max<int64_t>(256, std::min<int64_t>(SPMV_META_BLOCKS, table_len >> 12));
-    hipLaunchKernelGGL(k_spmv_meta, dim3((unsigned)blocks), dim3(256), 0, stream, sems, part_keys, table_len, capacity, scratch, out6_pinned, seq);
+    hipLaunchKernelGGL(k_spmv_meta, dim3((unsigned)blocks), dim3(256), 0, stream, V.sems, V.part_keys, table_len, V.capacity, scratch, out6_pinned, seq);
     return hipGetLastError();
 }
 
 template <bool WIDE, bool NT, bool ZFILL>
-static void launch_gather_t(int64_t grid, hipStream_t stream, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                            const int64_t* sems, const int64_t* part_keys, int64_t table_len, const double* x, int64_t nx, double* y,
-                            int64_t ny, int pattern) {
+static void launch_gather_t(int64_t grid, hipStream_t stream, const SlotView& V, const double* x, int64_t nx, double* y, int64_t ny,
+                            int pattern) {
     // SHARE needs every wave of every workgroup at its barrier: whole tiles only (DSA_SPMV_SHARE=0: the form without the barrier)
     static const bool share_ok = [] { const char* e = dev_env("DSA_SPMV_SHARE"); return !(e && e[0] == '0'); }();
     // SHARE pays where the gathers miss (config 3: 118.1 vs 121.2 us without it); where x is L2-resident the barrier costs more than the
     // ninth word saves (banded shape: 90.9 vs 86.9 us), so the plain-stream instantiations run without it
-    const bool share = NT && share_ok && capacity >= SP_TILE && capacity % SP_TILE == 0;
+    const bool share = NT && share_ok && V.capacity >= SP_TILE && V.capacity % SP_TILE == 0;
     if (share)
-        hipLaunchKernelGGL((k_spmv_gather<WIDE, NT, ZFILL, true>), dim3((unsigned)grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, sems,
-                           part_keys, table_len, x, nx, y, ny, pattern);
+        hipLaunchKernelGGL((k_spmv_gather<WIDE, NT, ZFILL, true>), dim3((unsigned)grid), dim3(SP_BLOCK), 0, stream, V.keys, V.vals, V.occ,
+                           V.capacity, V.sems, V.part_keys, V.table_len, x, nx, y, ny, pattern);
     else
-        hipLaunchKernelGGL((k_spmv_gather<WIDE, NT, ZFILL, false>), dim3((unsigned)grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, sems,
-                           part_keys, table_len, x, nx, y, ny, pattern);
+        hipLaunchKernelGGL((k_spmv_gather<WIDE, NT, ZFILL, false>), dim3((unsigned)grid), dim3(SP_BLOCK), 0, stream, V.keys, V.vals, V.occ,
+                           V.capacity, V.sems, V.part_keys, V.table_len, x, nx, y, ny, pattern);
 }
 
 // mode bit 0 (SPMV_ZFILL): skip the memset of y, the kernel zeroes the rows without a partition itself (see k_spmv_gather);
 // mode bit 1 (SPMV_PLAIN_STREAM): plain instead of non-temporal slot loads.  Scatter form: mode ignored.
-static hipError_t launch_spmv(bool scatter, int pattern, int mode, KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                              const int64_t* sems, const int64_t* part_keys, int64_t table_len, const double* x, int64_t nx,
-                              double* y, int64_t ny, hipStream_t stream) {
+static hipError_t launch_spmv(bool scatter, int pattern, int mode, const SlotView& V, const double* x, int64_t nx, double* y, int64_t ny,
+                              hipStream_t stream) {
     {   // dev knob: DSA_SPMV_STREAM=nt|plain forces the stream policy
         static const char* st = dev_env("DSA_SPMV_STREAM"); if (st) mode = (mode & ~2) | (st[0] == 'p' ? 2 : 0);
     }
     if (scatter) mode = 0;
-    const bool zfill = (mode & 1) && table_len > 0;
+    const bool zfill = (mode & 1) && V.table_len > 0;
     if (!zfill) {
         hipError_t e = hipMemsetAsync(y, 0, (size_t)ny * sizeof(double), stream);
         if (e != hipSuccess) return e;
     }
-    const int64_t ntiles = (capacity + SP_TILE - 1) / SP_TILE;
+    const int64_t ntiles = (V.capacity + SP_TILE - 1) / SP_TILE;
     const int64_t grid = ntiles >= 64 ? 8 * ((ntiles + 7) / 8) : ntiles;     // see the XCD-aware mapping in k_spmv
     if (scatter) {
-        hipLaunchKernelGGL(k_spmv_scatter, dim3((unsigned)grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, sems,
-                           part_keys, table_len, x, nx, y, ny, 0);
+        hipLaunchKernelGGL(k_spmv_scatter, dim3((unsigned)grid), dim3(SP_BLOCK), 0, stream, V.keys, V.vals, V.occ, V.capacity, V.sems,
+                           V.part_keys, V.table_len, x, nx, y, ny, 0);
         return hipGetLastError();
     }
-    const int sel = (keys.wide ? 4 : 0) | ((mode & 2) ? 0 : 2) | (zfill ? 1 : 0);
-#define DSA_GATHER_CASE(W_, N_, Z_) launch_gather_t<W_, N_, Z_>(grid, stream, keys, vals, occ, capacity, sems, part_keys, table_len, x, nx, y, ny, pattern)
+    const int sel = (V.keys.wide ? 4 : 0) | ((mode & 2) ? 0 : 2) | (zfill ? 1 : 0);
+#define DSA_GATHER_CASE(W_, N_, Z_) launch_gather_t<W_, N_, Z_>(grid, stream, V, x, nx, y, ny, pattern)
     switch (sel) {
         case 0: DSA_GATHER_CASE(false, false, false); break;
         case 1: DSA_GATHER_CASE(false, false, true); break;
@@ -815,16 +814,17 @@ __global__ __launch_bounds__(PLAN_SCAN_THREADS) void k_plan_scan(PlanDev pl, int
     }
 }
 
-hipError_t launch_spmv_plan_build(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, const int64_t* part_keys,
-                                  int64_t table_len, int64_t nx, int64_t ny, const PlanDev& pl, unsigned long long* out3_pinned,
+hipError_t launch_spmv_plan_build(const SlotView& V, int64_t nx, int64_t ny, const PlanDev& pl, unsigned long long* out3_pinned,
                                   unsigned long long seq, hipStream_t stream) {
     if (pl.groups <= 0 || pl.groups > PLAN_MAX_GROUPS || pl.slices <= 0 || pl.slices > PLAN_MAX_SLICES || pl.width <= 0 || pl.width > 65536 ||
         ny < 0 || ny + 1 >= ((int64_t)1 << 32))
         return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((pl.groups + SP_WAVES - 1) / SP_WAVES);
-    hipLaunchKernelGGL(k_plan_pass<false>, dim3(grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, nx, pl, part_keys, table_len, ny);
-    hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(PLAN_SCAN_THREADS), 0, stream, pl, table_len, out3_pinned, seq);
-    hipLaunchKernelGGL(k_plan_pass<true>, dim3(grid), dim3(SP_BLOCK), 0, stream, keys, vals, occ, capacity, nx, pl, part_keys, table_len, ny);
+    hipLaunchKernelGGL(k_plan_pass<false>, dim3(grid), dim3(SP_BLOCK), 0, stream, V.keys, V.vals, V.occ, V.capacity, nx, pl, V.part_keys,
+                       V.table_len, ny);
+    hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(PLAN_SCAN_THREADS), 0, stream, pl, V.table_len, out3_pinned, seq);
+    hipLaunchKernelGGL(k_plan_pass<true>, dim3(grid), dim3(SP_BLOCK), 0, stream, V.keys, V.vals, V.occ, V.capacity, nx, pl, V.part_keys,
+                       V.table_len, ny);
     return hipGetLastError();
 }
 
@@ -954,15 +954,11 @@ hipError_t launch_spmv_plan(const PlanDev& pl, int64_t table_len, const double* 
     return hipGetLastError();
 }
 
-hipError_t launch_spmv_gather(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                              const int64_t* sems, const int64_t* part_keys, const uint8_t*, int64_t table_len,
-                              const double* x, int64_t nx, double* y, int64_t ny, int pattern, int mode, hipStream_t stream) {
-    return launch_spmv(false, pattern, mode, keys, vals, occ, capacity, sems, part_keys, table_len, x, nx, y, ny, stream);
+hipError_t launch_spmv_gather(const SlotView& V, const double* x, int64_t nx, double* y, int64_t ny, int pattern, int mode, hipStream_t stream) {
+    return launch_spmv(false, pattern, mode, V, x, nx, y, ny, stream);
 }
-hipError_t launch_spmv_scatter(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity,
-                               const int64_t* sems, const int64_t* part_keys, const uint8_t*, int64_t table_len,
-                               const double* x, int64_t nx, double* y, int64_t ny, hipStream_t stream) {
-    return launch_spmv(true, 0, 0, keys, vals, occ, capacity, sems, part_keys, table_len, x, nx, y, ny, stream);
+hipError_t launch_spmv_scatter(const SlotView& V, const double* x, int64_t nx, double* y, int64_t ny, hipStream_t stream) {
+    return launch_spmv(true, 0, 0, V, x, nx, y, ny, stream);
 }
 
 }  // namespace dsa

@@ -14,7 +14,7 @@ namespace host {
 // Tables with tombstones or unmerged entries take the memset path whatever the layout: nothing to compute.
 static bool spmv_meta_applicable(const Pma& P) {
     const Ctl& c = *P.h_ctl;
-    return P.has_cols && c.table_len > 0 && c.nb_partitions == c.table_len && c.n_pending == 0;
+    return P.has_cols && c.table_len > 0 && P.view().dense && c.n_pending == 0;
 }
 // Enqueues k_spmv_meta + the copy of its 5 result words behind whatever is on the stream (one launch, no host wait).  Called at the
 // end of every write batch / build, so that the product that follows finds the words already in pinned memory: the product after a
@@ -30,7 +30,7 @@ void prefetch_spmv_meta(Pma& P) {
         P.meta_seq = 0;
     }
     // the kernel writes its five words and then the sequence number straight into pinned host memory
-    LAUNCH("spmv meta", launch_spmv_meta(P.sems, P.col_keys, P.h_ctl->table_len, P.h_ctl->capacity, P.d_meta,
+    LAUNCH("spmv meta", launch_spmv_meta(P.view(), P.d_meta,
                                          reinterpret_cast<unsigned long long*>(P.h_meta), ++P.meta_seq, P.stream));
     P.meta_inflight_epoch = P.layout_epoch;
 }
@@ -109,7 +109,7 @@ void spmv_plan_build(Pma& P, int64_t nx, int64_t ny, hipStream_t s) {
     d.nsem = d.pfirst + G + 1;
     d.yrow = d.nsem + G;
     unsigned long long* out = reinterpret_cast<unsigned long long*>(P.h_meta + 6);
-    launch_check(launch_spmv_plan_build(P.K(), P.V(), P.O(), P.capacity(), P.col_keys, P.h_ctl->table_len, nx, ny, d, out, ++L.seq, s), "spmv plan build: ");
+    launch_check(launch_spmv_plan_build(P.view(), nx, ny, d, out, ++L.seq, s), "spmv plan build: ");
     L.state = Pma::SpmvPlan::PENDING;
     ++P.stat_spmv_plan_builds;
 }

@@ -271,32 +271,31 @@ __global__ __launch_bounds__(256) void k_sub_emit(KeyArr keys, const double* __r
     emit_epilogue(err, lane, wv, s.err, s.ticket, a.pinned, a.seq);
 }
 
-hipError_t launch_submatrix_keys(const uint64_t* occ, int64_t capacity, const int64_t* sems, const int64_t* col_keys, const uint8_t* col_live,
-                                 int64_t table_len, bool dense, const int64_t* d_outer, int64_t nouter, int64_t dim_out,
-                                 const int64_t* d_inner, int64_t ninner, int64_t dim_in, void* key_scratch, unsigned long long* pinned3,
-                                 unsigned long long seq, hipStream_t stream) {
-    if (capacity < 0 || table_len < 0 || nouter < 0 || nouter > INT32_MAX || ninner < 0 || ninner > INT32_MAX) return hipErrorInvalidValue;
+hipError_t launch_submatrix_keys(const SlotView& V, const int64_t* d_outer, int64_t nouter, int64_t dim_out, const int64_t* d_inner,
+                                 int64_t ninner, int64_t dim_in, void* key_scratch, unsigned long long* pinned3, unsigned long long seq,
+                                 hipStream_t stream) {
+    if (V.capacity < 0 || V.table_len < 0 || nouter < 0 || nouter > INT32_MAX || ninner < 0 || ninner > INT32_MAX) return hipErrorInvalidValue;
     const SubKeys s = sub_carve(key_scratch, nouter, ninner);
     hipError_t e = hipMemsetAsync(key_scratch, 0, 16 + (size_t)(s.tmask + 1) * 8, stream);      // error word, ticket, every key word
     if (e != hipSuccess) return e;
     if (ninner > 0) hipLaunchKernelGGL(k_sub_hash, dim3(ex_grid(ninner, 256)), dim3(256), 0, stream, d_inner, ninner, dim_in, s);
     if (nouter > 0)
-        hipLaunchKernelGGL(k_key_spans<false>, dim3((unsigned)((nouter + 3) / 4)), dim3(256), 0, stream, occ, capacity, sems, col_keys, col_live,
-                           table_len, dense || col_live == nullptr, d_outer, nouter, dim_out, s.lo, s.hi, s.choff, (int64_t*)nullptr, s.err);
+        hipLaunchKernelGGL(k_key_spans<false>, dim3((unsigned)((nouter + 3) / 4)), dim3(256), 0, stream, V, d_outer, nouter, dim_out, s.lo, s.hi,
+                           s.choff, (int64_t*)nullptr, s.err);
     hipLaunchKernelGGL(k_sub_scan_items, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, nouter, pinned3, seq);
     return hipGetLastError();
 }
 
-hipError_t launch_submatrix_count(KeyArr keys, const uint64_t* occ, int64_t capacity, int64_t nouter, int64_t ninner, int64_t items,
-                                  int64_t dim_in, int32_t index_bits, int64_t base, void* d_ptr, void* key_scratch, void* item_scratch,
-                                  unsigned long long* pinned3, unsigned long long seq, hipStream_t stream) {
-    if (capacity < 0 || nouter < 0 || ninner < 0 || items < 0 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
+hipError_t launch_submatrix_count(const SlotView& V, int64_t nouter, int64_t ninner, int64_t items, int64_t dim_in, int32_t index_bits,
+                                  int64_t base, void* d_ptr, void* key_scratch, void* item_scratch, unsigned long long* pinned3,
+                                  unsigned long long seq, hipStream_t stream) {
+    if (V.capacity < 0 || nouter < 0 || ninner < 0 || items < 0 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
     const SubKeys s = sub_carve(key_scratch, nouter, ninner);
     const SubItems it = sub_carve_items(item_scratch, items);
     if (items > 0) {
         const unsigned grid = ex_grid(items, 4);
-        if (keys.wide) hipLaunchKernelGGL(k_sub_count<true>, dim3(grid), dim3(256), 0, stream, keys, occ, s, it, nouter, items, dim_in);
-        else hipLaunchKernelGGL(k_sub_count<false>, dim3(grid), dim3(256), 0, stream, keys, occ, s, it, nouter, items, dim_in);
+        if (V.keys.wide) hipLaunchKernelGGL(k_sub_count<true>, dim3(grid), dim3(256), 0, stream, V.keys, V.occ, s, it, nouter, items, dim_in);
+        else hipLaunchKernelGGL(k_sub_count<false>, dim3(grid), dim3(256), 0, stream, V.keys, V.occ, s, it, nouter, items, dim_in);
     }
     if (index_bits == 32)
         hipLaunchKernelGGL(k_sub_scan_cells<int32_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, it, nouter, items, base,
@@ -307,16 +306,16 @@ hipError_t launch_submatrix_count(KeyArr keys, const uint64_t* occ, int64_t capa
     return hipGetLastError();
 }
 
-hipError_t launch_submatrix_emit(KeyArr keys, const double* vals, const uint64_t* occ, int64_t capacity, int64_t nouter, int64_t ninner,
-                                 int64_t items, int64_t total, int32_t index_bits, int64_t base, void* d_idx, double* d_vals,
-                                 void* key_scratch, void* item_scratch, unsigned long long* pinned2, unsigned long long seq,
-                                 hipStream_t stream) {
-    if (capacity < 0 || nouter < 1 || ninner < 1 || items < 1 || total < 1 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
+hipError_t launch_submatrix_emit(const SlotView& V, int64_t nouter, int64_t ninner, int64_t items, int64_t total, int32_t index_bits,
+                                 int64_t base, void* d_idx, double* d_vals, void* key_scratch, void* item_scratch,
+                                 unsigned long long* pinned2, unsigned long long seq, hipStream_t stream) {
+    if (V.capacity < 0 || nouter < 1 || ninner < 1 || items < 1 || total < 1 || (index_bits != 32 && index_bits != 64)) return hipErrorInvalidValue;
     const SubKeys s = sub_carve(key_scratch, nouter, ninner);
     const SubItems it = sub_carve_items(item_scratch, items);
     const SubArgs a{d_idx, d_vals, nouter, items, total, base, pinned2, seq};
-    dispatch_wide_it(keys.wide, index_bits, [&](auto wide, auto ix) {
-        hipLaunchKernelGGL((k_sub_emit<decltype(wide)::value, decltype(ix)>), dim3(ex_grid(items, 4)), dim3(256), 0, stream, keys, vals, occ, s, it, a);
+    dispatch_wide_it(V.keys.wide, index_bits, [&](auto wide, auto ix) {
+        hipLaunchKernelGGL((k_sub_emit<decltype(wide)::value, decltype(ix)>), dim3(ex_grid(items, 4)), dim3(256), 0, stream, V.keys, V.vals,
+                           V.occ, s, it, a);
     });
     return hipGetLastError();
 }

@@ -327,7 +327,7 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
     // front of the fresh ops.  Only where no op can fail (a failing op must find exactly the ops in front of it applied): no tombstones,
     // not the cut batches of the tombstone path.  DSA_RUN_AHEAD=0: the prefix rule of rounds 2-5 (A/B).
     static const bool run_ahead_on = [] { const char* e = dev_env("DSA_RUN_AHEAD"); return !(e && e[0] == '0'); }();
-    const bool run_ahead = run_ahead_on && !can_fail && (!P.has_cols || P.h_ctl->nb_partitions == P.h_ctl->table_len);
+    const bool run_ahead = run_ahead_on && !can_fail && P.view().dense;
     int np = 0, cur = 0;                    // pending ops of the rounds and which half of d_pend holds them
     bool drain = false;                     // the next bursts work on the pending list alone ...
     int after_drain = 0;                    // ... and then: 1 switch to the local rounds, 2 the sequencer takes the chunk at the cursor

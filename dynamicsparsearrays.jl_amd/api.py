@@ -1029,6 +1029,43 @@ class DynamicSparseMatrix(_Handle):
         self.b.call("mat_scale_dev", self.h, float(alpha), C.c_void_p(int(d_r)) if d_r else None, int(nr),
                     C.c_void_p(int(d_c)) if d_c else None, int(nc))
 
+    # ---- batched delete (include/dsa.h: dsa_mat_delete_batch[_dev]; HIP library only) --------------------------------------------
+    def _delete_batch(self, orientation, keys):
+        self._require("mat_delete_batch", "the batched delete needs the HIP product library")
+        if type(keys).__module__.split(".")[0] == "torch":
+            import torch
+            if keys.dtype != torch.int64 or keys.dim() != 1:
+                raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 tensor")
+            if keys.is_cuda:
+                k = keys.contiguous()
+                # the library reads the keys on its own streams: torch's pending work on them must be over first
+                torch.cuda.current_stream(k.device).synchronize()
+                return self.delete_batch_dev(orientation, k.data_ptr(), k.numel())
+            keys = keys.numpy()
+        k, kp = _i64(np.asarray(keys, dtype=np.int64).reshape(-1))
+        got = C.c_int64()
+        self.b.call("mat_delete_batch", self.h, int(orientation), kp, len(k), C.byref(got))
+        return got.value
+
+    def delete_columns(self, cols):
+        """deletecolumn! for every key of cols in one device pass (any order, distinct keys, each a live column).  cols: a sequence, a
+        numpy array or an int64 tensor (one on the GPU is used where it is).  Content and tables are those of the single deletes one
+        after the other; the survivors of both orientations are spread evenly as by rebalance_root.  Every error leaves the matrix
+        untouched.  Returns the number of entries removed.  For one or two keys deletecolumn is the cheaper call."""
+        return self._delete_batch(COLMAJOR, cols)
+
+    def delete_rows(self, rows):
+        """deleterow! for every key of rows in one device pass (see delete_columns)"""
+        return self._delete_batch(ROWMAJOR, rows)
+
+    def delete_batch_dev(self, orientation, d_keys, n):
+        """the batched delete with the key list in HBM (device address of n int64 keys, complete at the call): COLMAJOR deletes
+        columns, ROWMAJOR rows; returns the number of entries removed"""
+        self._require("mat_delete_batch", "the batched delete needs the HIP product library")
+        got = C.c_int64()
+        self.b.call("mat_delete_batch_dev", self.h, int(orientation), C.c_void_p(int(d_keys)) if d_keys else None, int(n), C.byref(got))
+        return got.value
+
 
 def dynamicsparse(I=None, J=None, V=None, m=None, n=None, fill_mode=True,
                   binding: Binding | None = None) -> DynamicSparseMatrix:
@@ -1129,6 +1166,14 @@ def deletecolumn(mat, col):
 def deleterow(mat, row):
     mat.deleterow(row)
     return True
+
+
+def deletecolumns(mat, cols):
+    return mat.delete_columns(cols)
+
+
+def deleterows(mat, rows):
+    return mat.delete_rows(rows)
 
 
 def addrow(mat, row, colids, vals):

@@ -1550,6 +1550,41 @@ int32_t dsa_mat_scale(dsa_mat_t* h, double alpha, const double* r, int64_t nr, c
     API_CATCH
 }
 
+// ---- batched delete (delbatch.hip): every column (row) of a key list leaves both orientations in one device pass.  The validate
+// pass is in front of the epoch bump: an error leaves layouts and cached plans as they were
+int32_t dsa_mat_delete_batch_dev(dsa_mat_t* h, int32_t orientation, const int64_t* d_keys, int64_t n, int64_t* removed_out) {
+    API_TRY
+    if (removed_out) *removed_out = 0;
+    const int64_t cells = delete_batch_prepare(h, orientation, d_keys, n);
+    if (cells >= 0) {
+        mat_content_changed(h);
+        delete_batch_apply(h, orientation, n, cells);
+        mat_prefetch_spmv_meta(h);
+        if (removed_out) *removed_out = cells;
+    }
+    API_CATCH
+}
+int32_t dsa_mat_delete_batch(dsa_mat_t* h, int32_t orientation, const int64_t* keys, int64_t n, int64_t* removed_out) {
+    API_TRY
+    if (removed_out) *removed_out = 0;
+    mat_flush(h);
+    if (h->fillmode || !h->has_major) fail(DSA_EMODE, "Cannot delete columns or rows in fill mode");
+    Pma& P = orient(h, orientation);
+    if (n < 0) fail(DSA_EARG, "delete batch: n is negative");
+    if (n > 0 && !keys) fail(DSA_EARG, "delete batch: the key list is NULL");
+    if (n > 0) {
+        DevStaging b(P.stream);                           // drains the own stream before the keys go back to the pool
+        HIPCHK(pool_alloc(&b.p[0], (size_t)n * sizeof(int64_t)));
+        HIPCHK(hipMemcpyAsync(b.p[0], keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, P.stream));
+        const int64_t cells = delete_batch_prepare(h, orientation, static_cast<const int64_t*>(b.p[0]), n);
+        mat_content_changed(h);
+        delete_batch_apply(h, orientation, n, cells);     // (returns with both streams drained: the twin is done with the table)
+        mat_prefetch_spmv_meta(h);
+        if (removed_out) *removed_out = cells;
+    }
+    API_CATCH
+}
+
 int32_t dsa_mat_check(dsa_mat_t* h, int32_t o, int64_t* report) { API_TRY mat_flush(h); pma_check(orient(h, o), report); API_CATCH }
 int32_t dsa_mat_set_stream(dsa_mat_t* h, void* s) {
     API_TRY

@@ -140,6 +140,76 @@ __device__ __forceinline__ uint64_t chunk_word(const uint64_t* __restrict__ occ,
     return myword;
 }
 
+// ---- the key block of a key-list operation (submatrix.hip: the inner list; delbatch.hip: the keys to delete): an open-addressing
+// hash table of a list of distinct keys >= 1 in pooled scratch — capacity the power of two >= 2 * ninner (load <= 1/2, linear
+// probing, Fibonacci hashing), entry = int64 key + int32 position in the list, empty = key 0 — and three arrays of one entry per
+// outer key.  Layout: {error word, ticket, 8 bytes of padding}, the table's key words (one memset clears header and key words;
+// nothing else is initialised), its positions, then lo / hi / choff.
+constexpr uint64_t SUB_NONE = ~0ull;
+struct SubKeys {
+    uint32_t* err; uint32_t* ticket;
+    int64_t* tkey; int32_t* tpos; uint64_t tmask; int tshift;      // entry p of the table; p = (key * phi) >> tshift
+    int64_t* lo; int64_t* hi;                            // span of outer key j: slots [lo, hi), 0-based
+    int64_t* choff;                                      // work items of j (k_key_spans), then their exclusive prefix
+};
+static inline uint64_t sub_table_cap(int64_t ninner) {
+    uint64_t c = 2;
+    while (c < 2 * (uint64_t)(ninner > 0 ? ninner : 0)) c <<= 1;
+    return c;
+}
+static inline SubKeys sub_carve(void* base, int64_t nouter, int64_t ninner) {
+    const uint64_t cap = sub_table_cap(ninner);
+    SubKeys s;
+    s.err = static_cast<uint32_t*>(base);
+    s.ticket = s.err + 1;
+    s.tkey = reinterpret_cast<int64_t*>(static_cast<char*>(base) + 16);
+    s.tpos = reinterpret_cast<int32_t*>(s.tkey + cap);
+    s.tmask = cap - 1;
+    s.tshift = 64 - __builtin_ctzll(cap);
+    s.lo = reinterpret_cast<int64_t*>(s.tpos + cap);     // cap is even: 8-byte aligned
+    s.hi = s.lo + nouter;
+    s.choff = s.hi + nouter;
+    return s;
+}
+static inline size_t sub_key_block_bytes(int64_t nouter, int64_t ninner) {
+    return 16 + (size_t)sub_table_cap(ninner) * 12 + (size_t)(nouter > 0 ? nouter : 0) * 24;
+}
+static inline size_t sub_key_block_clear_bytes(const SubKeys& s) { return 16 + (size_t)(s.tmask + 1) * 8; }      // error word, ticket, every key word
+
+__device__ __forceinline__ uint64_t sub_slot(const SubKeys& s, int64_t key) {
+    return ((uint64_t)key * 0x9E3779B97F4A7C15ull) >> s.tshift;
+}
+// the entry that holds `key` (>= 1), given the key word t already loaded from its first entry p; SUB_NONE if the key is not listed
+__device__ __forceinline__ uint64_t sub_resolve(const SubKeys& s, int64_t key, uint64_t p, int64_t t) {
+    for (uint64_t n = 0; n <= s.tmask; ++n) {
+        if (t == key) return p;
+        if (t == 0) return SUB_NONE;
+        p = (p + 1) & s.tmask;
+        t = s.tkey[p];
+    }
+    return SUB_NONE;
+}
+
+// grid-wide over the list: range check (error bit 4), 64-bit atomicCAS on the key word of the probed entry; a CAS that meets its
+// own key again is the repeated-key error (bit 8).  (A template like k_key_spans, so that only the units that launch it hold a copy.)
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void k_sub_hash(const int64_t* __restrict__ inner, int64_t ninner, int64_t dim_in, SubKeys s) {
+    uint32_t err = 0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ninner; i += stride) {
+        const int64_t key = inner[i];
+        if (key < 1 || key > dim_in) { err |= 4u; continue; }
+        uint64_t p = sub_slot(s, key);
+        for (uint64_t n = 0; n <= s.tmask; ++n) {                // load <= 1/2: an empty entry always turns up
+            const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(s.tkey + p), 0ull, (unsigned long long)key);
+            if (old == 0ull) { s.tpos[p] = (int32_t)i; break; }
+            if (old == (unsigned long long)key) { err |= 8u; break; }
+            p = (p + 1) & s.tmask;
+        }
+    }
+    if (err) atomicOr(s.err, err);
+}
+
 // The hand-over at the end of a scan or emit kernel (one thread).  The pinned words by n, the number of totals the host expects:
 //   n = 0  {error word, seq}     n = 1  {error word, t0, seq}     n = 2  {error word, t0, t1, seq}
 // n must be the literal the host side's wait_handover(pin + n + 1) goes with: seq lands behind the totals.

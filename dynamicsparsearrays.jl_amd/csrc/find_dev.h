@@ -241,12 +241,14 @@ static __device__ PartSpan part_span(const SlotView& V, int64_t id) {
 // [lo, hi), 0-based, strictly between its semaphore and the next live semaphore (tombstoned table entries behind the partition are
 // skipped 64 at a time; the end of the slot array behind the last one).  lo = hi = 0 for a key without a live partition.
 // err: 1 the key lies outside 1..dim_out, 2 tables out of step with the slots.
-struct KeySpan { int64_t lo, hi; uint32_t err; };
+// pos = the 1-based table entry of the partition (0: none), for the callers that write the tables (delbatch.hip).
+struct KeySpan { int64_t lo, hi; uint32_t err; int64_t pos; };
 // ... of any key the table holds, also one below 1 (the sparse-x product: a matrix may own such a column); err is 0 or 2
 __device__ __forceinline__ KeySpan live_span(const SlotView& V, int64_t key, int lane) {
-    KeySpan r{0, 0, 0u};
+    KeySpan r{0, 0, 0u, 0};
     const DFoundKey f = d_find_table_fast(V.part_keys, V.part_live, V.table_len, key, V.dense);
     if (f.has && f.key == key) {
+        r.pos = f.pos;
         const int64_t sp = V.sems[f.pos - 1];                    // 1-based slot of the semaphore = 0-based slot of the first cell
         int64_t nx = 0;                                          // the next live semaphore (tombstones have none)
         for (int64_t e0 = f.pos; e0 < V.table_len; e0 += 64) {
@@ -262,7 +264,7 @@ __device__ __forceinline__ KeySpan live_span(const SlotView& V, int64_t key, int
     return r;
 }
 __device__ __forceinline__ KeySpan key_span(const SlotView& V, int64_t key, int64_t dim_out, int lane) {
-    if (key < 1 || key > dim_out) return KeySpan{0, 0, 1u};
+    if (key < 1 || key > dim_out) return KeySpan{0, 0, 1u, 0};
     return live_span(V, key, lane);
 }
 

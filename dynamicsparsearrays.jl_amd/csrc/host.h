@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, pma_host.hip, writes_host.hip, build_host.hip,
-// spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
+// spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -153,6 +153,8 @@ struct Pma {
     // batched sparse-x product (spgemm.hip): per-entry spans and per-column counts, and the slabs of the long columns (all zero
     // between two calls)
     ExportArea spg, spgs;
+    // batched delete (delbatch.hip): counters, the hash table of the key list and its spans; the pinned words of its two hand-overs
+    ExportArea del;
     // thresholds  src/pma.jl:58,70,87
     double t_h = 0.7, t_0 = 0.92, p_h = 0.3, p_0 = 0.08, t_d = 0.0, p_d = 0.0;
 
@@ -335,6 +337,12 @@ struct ScaleStaging {
     ScaleStaging(dsa_mat* h, const double* r, int64_t nr, const double* c, int64_t nc);
     ~ScaleStaging();
 };
+
+// ---- delbatch_host.hip: the batched delete of columns (DSA_COLMAJOR) or rows (DSA_ROWMAJOR), d_keys a device array.  Two steps so
+// that the entry point can bump the content epoch between them: delete_batch_prepare (flush, checks, the validate pass: DSA_EMODE /
+// DSA_EARG with nothing modified; returns the matrix entries the delete removes, -1 for an empty list) and delete_batch_apply.
+int64_t delete_batch_prepare(dsa_mat* h, int32_t orientation, const int64_t* d_keys, int64_t n);
+void delete_batch_apply(dsa_mat* h, int32_t orientation, int64_t n, int64_t cells);
 
 // Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks
 // and uploaded asynchronously as a chunk fills (the copy of chunk k overlaps the caller's appends into chunk k+1), so that

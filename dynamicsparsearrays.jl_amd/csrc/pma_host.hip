@@ -69,6 +69,7 @@ void pma_destroy(Pma& P) {
     P.sub.release();
     P.subi.release();
     P.sc.release();
+    P.del.release();
     P.spg.release();
     P.spgs.release();
     if (P.tmerge.sems2) hipFree(P.tmerge.sems2);

@@ -40,83 +40,23 @@
 
 namespace dsa {
 
-constexpr uint64_t SUB_NONE = ~0ull;
+// SubKeys, the key block (hash table of the inner list, spans of the outer list), its carving and k_sub_hash are in export_dev.h:
+// the batched delete (delbatch.hip) puts its key list into the same table
 
-// key block: {error word, ticket of the emit, 8 bytes of padding}, the table's key words (the memset ends behind them), its
-// positions, then three arrays of nouter entries
-struct SubKeys {
-    uint32_t* err; uint32_t* ticket;
-    int64_t* tkey; int32_t* tpos; uint64_t tmask; int tshift;      // entry p of the table; p = (key * phi) >> tshift
-    int64_t* lo; int64_t* hi;                            // span of outer key j: slots [lo, hi), 0-based
-    int64_t* choff;                                      // work items of j (k_key_spans), then their exclusive prefix
-};
 // item block
 struct SubItems {
     int64_t* off;                                        // kept cells of item w (k_sub_count), then their exclusive prefix
     int32_t* owner;                                      // the outer index j the item belongs to
 };
 
-static uint64_t sub_table_cap(int64_t ninner) {
-    uint64_t c = 2;
-    while (c < 2 * (uint64_t)(ninner > 0 ? ninner : 0)) c <<= 1;
-    return c;
-}
-static SubKeys sub_carve(void* base, int64_t nouter, int64_t ninner) {
-    const uint64_t cap = sub_table_cap(ninner);
-    SubKeys s;
-    s.err = static_cast<uint32_t*>(base);
-    s.ticket = s.err + 1;
-    s.tkey = reinterpret_cast<int64_t*>(static_cast<char*>(base) + 16);
-    s.tpos = reinterpret_cast<int32_t*>(s.tkey + cap);
-    s.tmask = cap - 1;
-    s.tshift = 64 - __builtin_ctzll(cap);
-    s.lo = reinterpret_cast<int64_t*>(s.tpos + cap);     // cap is even: 8-byte aligned
-    s.hi = s.lo + nouter;
-    s.choff = s.hi + nouter;
-    return s;
-}
 static SubItems sub_carve_items(void* base, int64_t items) {
     SubItems it;
     it.off = static_cast<int64_t*>(base);
     it.owner = reinterpret_cast<int32_t*>(it.off + items);
     return it;
 }
-size_t submatrix_key_scratch_bytes(int64_t nouter, int64_t ninner) {
-    return 16 + (size_t)sub_table_cap(ninner) * 12 + (size_t)(nouter > 0 ? nouter : 0) * 24;
-}
+size_t submatrix_key_scratch_bytes(int64_t nouter, int64_t ninner) { return sub_key_block_bytes(nouter, ninner); }
 size_t submatrix_item_scratch_bytes(int64_t items) { return (size_t)(items > 0 ? items : 0) * 12 + 16; }
-
-__device__ __forceinline__ uint64_t sub_slot(const SubKeys& s, int64_t key) {
-    return ((uint64_t)key * 0x9E3779B97F4A7C15ull) >> s.tshift;
-}
-// the entry that holds `key` (>= 1), given the key word t already loaded from its first entry p; SUB_NONE if the key is not listed
-__device__ __forceinline__ uint64_t sub_resolve(const SubKeys& s, int64_t key, uint64_t p, int64_t t) {
-    for (uint64_t n = 0; n <= s.tmask; ++n) {
-        if (t == key) return p;
-        if (t == 0) return SUB_NONE;
-        p = (p + 1) & s.tmask;
-        t = s.tkey[p];
-    }
-    return SUB_NONE;
-}
-
-// grid-wide over the inner list
-__global__ __launch_bounds__(256) void k_sub_hash(const int64_t* __restrict__ inner, int64_t ninner, int64_t dim_in, SubKeys s) {
-    uint32_t err = 0;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ninner; i += stride) {
-        const int64_t key = inner[i];
-        if (key < 1 || key > dim_in) { err |= 4u; continue; }
-        uint64_t p = sub_slot(s, key);
-        for (uint64_t n = 0; n <= s.tmask; ++n) {                // load <= 1/2: an empty entry always turns up
-            const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(s.tkey + p), 0ull, (unsigned long long)key);
-            if (old == 0ull) { s.tpos[p] = (int32_t)i; break; }
-            if (old == (unsigned long long)key) { err |= 8u; break; }
-            p = (p + 1) & s.tmask;
-        }
-    }
-    if (err) atomicOr(s.err, err);
-}
 
 // one workgroup: choff becomes its exclusive prefix in place
 __global__ __launch_bounds__(EX_SCAN_THREADS) void k_sub_scan_items(SubKeys s, int64_t nouter, unsigned long long* pinned,
@@ -276,9 +216,9 @@ hipError_t launch_submatrix_keys(const SlotView& V, const int64_t* d_outer, int6
                                  hipStream_t stream) {
     if (V.capacity < 0 || V.table_len < 0 || nouter < 0 || nouter > INT32_MAX || ninner < 0 || ninner > INT32_MAX) return hipErrorInvalidValue;
     const SubKeys s = sub_carve(key_scratch, nouter, ninner);
-    hipError_t e = hipMemsetAsync(key_scratch, 0, 16 + (size_t)(s.tmask + 1) * 8, stream);      // error word, ticket, every key word
+    hipError_t e = hipMemsetAsync(key_scratch, 0, sub_key_block_clear_bytes(s), stream);
     if (e != hipSuccess) return e;
-    if (ninner > 0) hipLaunchKernelGGL(k_sub_hash, dim3(ex_grid(ninner, 256)), dim3(256), 0, stream, d_inner, ninner, dim_in, s);
+    if (ninner > 0) hipLaunchKernelGGL(k_sub_hash<>, dim3(ex_grid(ninner, 256)), dim3(256), 0, stream, d_inner, ninner, dim_in, s);
     if (nouter > 0)
         hipLaunchKernelGGL(k_key_spans<false>, dim3((unsigned)((nouter + 3) / 4)), dim3(256), 0, stream, V, d_outer, nouter, dim_out, s.lo, s.hi,
                            s.choff, (int64_t*)nullptr, s.err);

@@ -29,5 +29,7 @@ const keyfrom = DynamicSparseArraysAMD.keyfrom
 const set_device! = DynamicSparseArraysAMD.set_device!
 const getindex_batch = DynamicSparseArraysAMD.getindex_batch
 const setindex_batch! = DynamicSparseArraysAMD.setindex_batch!
+const deletecolumns! = DynamicSparseArraysAMD.deletecolumns!      # a list of columns / rows in one device pass (dsa_mat_delete_batch)
+const deleterows! = DynamicSparseArraysAMD.deleterows!
 
 end # module

@@ -22,7 +22,7 @@ using SparseArrays
 using LinearAlgebra: Transpose
 
 export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC, dynamicsparsevec, dynamicsparse, nbpartitions,
-       deletecolumn!, deleterow!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
+       deletecolumn!, deleterow!, deletecolumns!, deleterows!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
        keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev,
        scale!, reduce_rows, reduce_cols, mul_rows, mul_cols, mul_sparse
@@ -300,6 +300,18 @@ end
 closefillmode!(a::DynamicSparseMatrix) = (_check(ccall((:dsa_mat_closefillmode, libdsa), Int32, (Ptr{Cvoid},), a.h)); true)
 deletecolumn!(a::DynamicSparseMatrix, col) = (_check(ccall((:dsa_mat_deletecolumn, libdsa), Int32, (Ptr{Cvoid}, Int64), a.h, _in(a.cols, col))); true)
 deleterow!(a::DynamicSparseMatrix, row) = (_check(ccall((:dsa_mat_deleterow, libdsa), Int32, (Ptr{Cvoid}, Int64), a.h, _in(a.rows, row))); true)
+# deletecolumn! / deleterow! for a list of keys in one device pass (dsa_mat_delete_batch; no reference counterpart: the content and
+# the tables are those of the single calls one after the other, the survivors are spread as by a root rebalance).  The keys in any
+# order, distinct, each a live column / row whose mapped key is >= 1; an error leaves the matrix untouched.  Returns the number of
+# entries removed.  For one or two keys the single calls are cheaper.
+function _delete_batch!(a::DynamicSparseMatrix, orientation::Int32, ki::Vector{Int64})
+    out = Ref{Int64}(0)
+    GC.@preserve ki _check(ccall((:dsa_mat_delete_batch, libdsa), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Int64, Ref{Int64}), a.h, orientation, ki, length(ki), out))
+    return out[]
+end
+deletecolumns!(a::DynamicSparseMatrix, cols::AbstractVector) = _delete_batch!(a, Int32(0), _in(a.cols, cols))          # DSA_COLMAJOR
+deleterows!(a::DynamicSparseMatrix, rows::AbstractVector) = _delete_batch!(a, Int32(1), _in(a.rows, rows))              # DSA_ROWMAJOR
 function SparseArrays.nnz(a::DynamicSparseMatrix)
     out = Ref{Int64}(0); _check(ccall((:dsa_mat_nnz, libdsa), Int32, (Ptr{Cvoid}, Ref{Int64}), a.h, out)); out[]
 end

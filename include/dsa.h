@@ -431,6 +431,23 @@ int32_t dsa_mat_reduce(dsa_mat_t* h, int32_t orientation, int32_t kind, double* 
  * pass only.  The host form stages r and c through pooled device memory and waits for both streams. */
 int32_t dsa_mat_scale_dev(dsa_mat_t* h, double alpha, const double* d_r, int64_t nr, const double* d_c, int64_t nc);
 int32_t dsa_mat_scale(dsa_mat_t* h, double alpha, const double* r, int64_t nr, const double* c, int64_t nc);
+/* Batched delete: every column (orientation = DSA_COLMAJOR) or row (DSA_ROWMAJOR) of a key list leaves the matrix in one device pass.
+ * CONTENT, partition tables and size() afterwards are those of deletecolumn! / deleterow! (src/matrix.jl:95-111; deletepartition!,
+ * src/pcsr.jl:188-212) called for the same keys one after the other: in the orientation whose partitions the keys name every listed
+ * partition goes away with its semaphore and its table entry becomes a tombstone (table_len unchanged); in the other orientation every
+ * entry whose inner key is listed goes away and every semaphore stays; size(m) is unchanged.  The LAYOUT is not that of n sequential
+ * deletes: capacity, height, segment capacity and thresholds stay, and the surviving cells of each orientation, in slot order, are
+ * spread over [1, capacity] by the reference's spread! rule — what dsa_mat_rebalance_root gives (a single-leaf array is not moved).
+ * The batch never shrinks; the next write that reaches the root does, as after the reference's own deletes.
+ * The list may be in any order and must hold distinct keys, each a live partition of its orientation.  Every error is found before
+ * the first write — both orientations and the cached SpMV plans stay as they were: DSA_EMODE in fill mode; DSA_EARG for n < 0, a
+ * repeated key, a key that is absent, already deleted or <= 0 (dsa_last_error names the first offending key; of a key listed more than
+ * twice the occurrence that counts is the second or a later one).  n = 0 does nothing.  Queued single writes are applied first.
+ * removed_out (host pointer, may be NULL) receives the number of matrix entries removed.  The call returns with both streams drained.
+ * _dev: d_keys is a device array that holds its final contents when the call is made.  The host form stages the keys through pooled
+ * device memory.  For one or two keys dsa_mat_deletecolumn / dsa_mat_deleterow remain the cheaper calls. */
+int32_t dsa_mat_delete_batch_dev(dsa_mat_t* h, int32_t orientation, const int64_t* d_keys, int64_t n, int64_t* removed_out);
+int32_t dsa_mat_delete_batch(dsa_mat_t* h, int32_t orientation, const int64_t* keys, int64_t n, int64_t* removed_out);
 /* ---- column-range shards. No reference counterpart: the reference is single-process.  One PROCESS per GPU:
  * each process selects its device (dsa_set_device), builds ITS shard and runs the local SpMV; the single data-path collective —
  * the all-reduce (sum) of the partial y — is dsa_shard_allreduce_dev below (RCCL behind this ABI), or whatever the host layer has

@@ -11,7 +11,7 @@ of the reference's public surface; ``julia/`` the `ccall` wrapper a Julia host u
 from . import binding  # noqa: F401
 from .api import (  # noqa: F401
     COLMAJOR, ROWMAJOR, DynamicSparseMatrix, DynamicSparseVector, PackedCSC, Transposed,
-    addrow, closefillmode, deletecolumn, deletecolumns, deletepartition, deleterow, deleterows, dynamicsparse,
+    addrow, closefillmode, deletecolumn, deletecolumns, deletepartition, deleterow, deleterows, droptol, dropzeros, dynamicsparse,
     dynamicsparse_compressed_dev, dynamicsparse_dev, from_torch,
     dynamicsparsevec, import_packedcsc_layout, import_vector_layout, nbpartitions, nnz, packedcsc, packedcsc_empty, pool_idle_bytes,
     pool_trim, shrink_size, dev_switches,

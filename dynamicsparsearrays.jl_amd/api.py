@@ -1066,6 +1066,67 @@ class DynamicSparseMatrix(_Handle):
         self.b.call("mat_delete_batch_dev", self.h, int(orientation), C.c_void_p(int(d_keys)) if d_keys else None, int(n), C.byref(got))
         return got.value
 
+    # ---- dropzeros! / droptol! (include/dsa.h: dsa_mat_droptol[_dev]; HIP library only) -------------------------------------------
+    def _droptol(self, tol, rows, cols, count_only):
+        self._require("mat_droptol", "dropzeros and droptol need the HIP product library")
+        ops = [x for x in (rows, cols) if x is not None]
+        is_t = [type(x).__module__.split(".")[0] == "torch" for x in ops]
+        if any(is_t):
+            import torch
+            if not all(is_t):
+                raise B.DsaArgumentError(B.EARG, "rows and cols must both be numpy arrays or both be tensors on the GPU")
+            for x in ops:
+                if x.dtype != torch.float64 or not x.is_cuda or x.dim() != 1:
+                    raise B.DsaArgumentError(B.EARG, "rows and cols must be 1-D float64 tensors on the GPU")
+            r = None if rows is None else rows.contiguous()
+            c = None if cols is None else cols.contiguous()
+            # the library reads the thresholds on its own two streams: torch's pending work on them must be over first, and they
+            # must stay as they are until the call has finished
+            torch.cuda.current_stream(ops[0].device).synchronize()
+            got = self.droptol_dev(tol, 0 if r is None else r.data_ptr(), 0 if r is None else r.numel(),
+                                   0 if c is None else c.data_ptr(), 0 if c is None else c.numel(), count_only=count_only)
+            self.sync()
+            return got
+        rr, rp = (None, None) if rows is None else _f64(np.asarray(rows, dtype=np.float64))
+        cc, cp = (None, None) if cols is None else _f64(np.asarray(cols, dtype=np.float64))
+        # a vector of length 0 is still "given": a non-NULL pointer that is never read
+        dummy = np.zeros(1, dtype=np.float64)
+        if rr is not None and len(rr) == 0:
+            rp = dummy.ctypes.data_as(P_F64)
+        if cc is not None and len(cc) == 0:
+            cp = dummy.ctypes.data_as(P_F64)
+        got = C.c_int64()
+        self.b.call("mat_droptol", self.h, float(tol), rp, 0 if rr is None else len(rr), cp, 0 if cc is None else len(cc),
+                    1 if count_only else 0, C.byref(got))
+        return got.value
+
+    def droptol(self, tol, rows=None, cols=None):
+        """SparseArrays' droptol! in place on the device: the stored cell (i, j) with value v is dropped iff |v| <= tol, or
+        |v| <= rows[i - 1], or |v| <= cols[j - 1] (IEEE: a NaN value is never dropped, a NaN or negative threshold matches nothing;
+        a negative tol gives purely relative dropping, e.g. A.droptol(-1, rows=eps * A.row_norms(np.inf))).  Content and tables are
+        those of A[i, j] = 0 for every dropped cell; an emptied column or row stays as an empty partition; the survivors of both
+        orientations are spread evenly as by rebalance_root.  When nothing is dropped nothing changes (cached SpMV plans survive), and
+        every error leaves the matrix untouched.  rows / cols: numpy arrays (or sequences), or float64 tensors on the GPU — both of
+        the same kind; None = vector absent.  Returns the number of entries dropped."""
+        return self._droptol(tol, rows, cols, False)
+
+    def dropzeros(self):
+        """SparseArrays' dropzeros!: every stored 0.0 / -0.0 leaves the matrix (droptol(0.0)).  Returns the number dropped."""
+        return self._droptol(0.0, None, None, False)
+
+    def count_droptol(self, tol, rows=None, cols=None):
+        """the number of entries droptol(tol, rows, cols) would drop; modifies nothing"""
+        return self._droptol(tol, rows, cols, True)
+
+    def droptol_dev(self, tol, d_r, nr, d_c, nc, count_only=False):
+        """droptol with the threshold vectors in HBM (device addresses, 0 = vector absent): they are read on both orientations'
+        streams and must be complete at the call; returns the number of entries dropped (count_only: that would be dropped)"""
+        self._require("mat_droptol", "dropzeros and droptol need the HIP product library")
+        got = C.c_int64()
+        self.b.call("mat_droptol_dev", self.h, float(tol), C.c_void_p(int(d_r)) if d_r else None, int(nr),
+                    C.c_void_p(int(d_c)) if d_c else None, int(nc), 1 if count_only else 0, C.byref(got))
+        return got.value
+
 
 def dynamicsparse(I=None, J=None, V=None, m=None, n=None, fill_mode=True,
                   binding: Binding | None = None) -> DynamicSparseMatrix:
@@ -1174,6 +1235,17 @@ def deletecolumns(mat, cols):
 
 def deleterows(mat, rows):
     return mat.delete_rows(rows)
+
+
+def droptol(mat, tol, rows=None, cols=None):
+    """droptol!(A, tol; rows, cols): returns the matrix, like SparseArrays"""
+    mat.droptol(tol, rows=rows, cols=cols)
+    return mat
+
+
+def dropzeros(mat):
+    mat.dropzeros()
+    return mat
 
 
 def addrow(mat, row, colids, vals):

@@ -12,8 +12,6 @@
 namespace dsa {
 namespace host {
 
-namespace {
-
 // What is left of an orientation after its mark pass, in slot order, spread over [1, capacity] by the root rebalance: the layout
 // dsa_mat_rebalance_root gives.  A single leaf is left as it is (root _even_rebalance! is a no-op there, src/pma.jl:96-99), and with
 // no cell left there is nothing to move and nothing to clear: the mark pass has cleared every bit (the branch of window_rebalance
@@ -24,8 +22,6 @@ void respread(Pma& X) {
     c.stat_rebalances += 1; c.stat_window_slots += c.capacity;
     root_rebalance(X, c.capacity, c.capacity, c.nb_elements, false);
 }
-
-}  // namespace
 
 // Everything of a batched delete in front of its first write.  Returns the number of matrix entries the delete removes, or -1 for an
 // empty list (nothing to do).  Throws DSA_EMODE / DSA_EARG with both orientations untouched.

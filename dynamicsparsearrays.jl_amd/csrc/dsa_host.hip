@@ -1585,6 +1585,36 @@ int32_t dsa_mat_delete_batch(dsa_mat_t* h, int32_t orientation, const int64_t* k
     API_CATCH
 }
 
+// ---- dropzeros! / droptol! (droptol.hip): every small cell leaves both orientations in place.  The decide pass is in front of the
+// epoch bump: an error, a call that drops nothing and the count-only call leave layouts and cached plans as they were
+namespace {
+void mat_droptol(dsa_mat_t* h, double tol, const double* d_rtol, int64_t nr, const double* d_ctol, int64_t nc, int32_t count_only,
+                 int64_t* dropped_out) {
+    const int64_t count = droptol_prepare(h, tol, d_rtol, nr, d_ctol, nc);
+    if (count > 0 && !count_only) {
+        mat_content_changed(h);
+        droptol_apply(h, count);
+        mat_prefetch_spmv_meta(h);
+    }
+    if (dropped_out) *dropped_out = count;
+}
+}  // namespace
+int32_t dsa_mat_droptol_dev(dsa_mat_t* h, double tol, const double* d_rtol, int64_t nr, const double* d_ctol, int64_t nc, int32_t count_only,
+                            int64_t* dropped_out) {
+    API_TRY
+    if (dropped_out) *dropped_out = 0;
+    mat_droptol(h, tol, d_rtol, nr, d_ctol, nc, count_only, dropped_out);
+    API_CATCH
+}
+int32_t dsa_mat_droptol(dsa_mat_t* h, double tol, const double* rtol, int64_t nr, const double* ctol, int64_t nc, int32_t count_only,
+                        int64_t* dropped_out) {
+    API_TRY
+    if (dropped_out) *dropped_out = 0;
+    ScaleStaging st(h, rtol, nr, ctol, nc);               // flush, DSA_EMODE / DSA_EARG, the vectors in HBM until both streams have drained
+    mat_droptol(h, tol, st.d_r, nr, st.d_c, nc, count_only, dropped_out);
+    API_CATCH
+}
+
 int32_t dsa_mat_check(dsa_mat_t* h, int32_t o, int64_t* report) { API_TRY mat_flush(h); pma_check(orient(h, o), report); API_CATCH }
 int32_t dsa_mat_set_stream(dsa_mat_t* h, void* s) {
     API_TRY

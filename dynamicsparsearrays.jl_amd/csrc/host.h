@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, pma_host.hip, writes_host.hip, build_host.hip,
-// spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
+// spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -155,6 +155,8 @@ struct Pma {
     ExportArea spg, spgs;
     // batched delete (delbatch.hip): counters, the hash table of the key list and its spans; the pinned words of its two hand-overs
     ExportArea del;
+    // dropzeros! / droptol! (droptol.hip): the scale scratch, the counter and the drop masks; the pinned {error word, count, sequence number}
+    ExportArea drp;
     // thresholds  src/pma.jl:58,70,87
     double t_h = 0.7, t_0 = 0.92, p_h = 0.3, p_0 = 0.08, t_d = 0.0, p_d = 0.0;
 
@@ -330,6 +332,7 @@ void submatrix_compressed_host(dsa_mat* h, int32_t orientation, int32_t index_ba
 // from host memory in HBM until both streams have drained.
 void reduce_dev(dsa_mat* h, int32_t orientation, int32_t kind, double* d_out, int64_t n_out);
 void reduce_host(dsa_mat* h, int32_t orientation, int32_t kind, double* out, int64_t n_out);
+bool stream_nt(const Pma& P, int64_t vector_bytes);      // the slot stream of P goes around the cache: it does not fit an XCD's L2 beside the vectors
 void scale_prepare(dsa_mat* h, const double* d_r, int64_t nr, const double* d_c, int64_t nc);
 void scale_apply(dsa_mat* h, double alpha, const double* d_r, const double* d_c);
 struct ScaleStaging {
@@ -343,6 +346,17 @@ struct ScaleStaging {
 // DSA_EARG with nothing modified; returns the matrix entries the delete removes, -1 for an empty list) and delete_batch_apply.
 int64_t delete_batch_prepare(dsa_mat* h, int32_t orientation, const int64_t* d_keys, int64_t n);
 void delete_batch_apply(dsa_mat* h, int32_t orientation, int64_t n, int64_t cells);
+// the finish of a pass that only cleared occupancy bits (h_ctl->nb_elements already lowered): the survivors, in slot order, spread over
+// [1, capacity] by the root rebalance; a single leaf or an empty array is not moved.  Bumps the layout epoch.
+void respread(Pma& X);
+
+// ---- droptol_host.hip: dropzeros! / droptol!, every cell with |v| <= tol, <= d_rtol[row - 1] or <= d_ctol[col - 1] leaves both
+// orientations (d_* are device arrays, nullptr = absent).  Two steps so that the entry point can bump the content epoch between them:
+// droptol_prepare (flush, checks, the decide pass over both orientations: DSA_EMODE / DSA_EARG / DSA_EBOUNDS / DSA_EASSERT with
+// nothing modified; returns the number of cells the predicate drops) and droptol_apply (the marks and root rebalances; returns with
+// both control blocks uploaded and both streams drained).
+int64_t droptol_prepare(dsa_mat* h, double tol, const double* d_rtol, int64_t nr, const double* d_ctol, int64_t nc);
+void droptol_apply(dsa_mat* h, int64_t count);
 
 // Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks
 // and uploaded asynchronously as a chunk fills (the copy of chunk k overlaps the caller's appends into chunk k+1), so that

@@ -70,6 +70,7 @@ void pma_destroy(Pma& P) {
     P.subi.release();
     P.sc.release();
     P.del.release();
+    P.drp.release();
     P.spg.release();
     P.spgs.release();
     if (P.tmerge.sems2) hipFree(P.tmerge.sems2);

@@ -11,12 +11,12 @@
 namespace dsa {
 namespace host {
 
-namespace {
-
 // the slot stream goes around the cache when it does not fit an XCD's 4 MB L2 beside the vectors (the rule of spmm_dev)
 bool stream_nt(const Pma& P, int64_t vector_bytes) {
     return P.capacity() * (int64_t)(P.kb() + sizeof(double)) + vector_bytes > (3 << 20);
 }
+
+namespace {
 
 void check_factors(dsa_mat* h, const double* r, int64_t nr, const double* c, int64_t nc) {
     if (h->fillmode || !h->has_major) fail(DSA_EMODE, "matrix is in fill mode");

@@ -31,5 +31,8 @@ const getindex_batch = DynamicSparseArraysAMD.getindex_batch
 const setindex_batch! = DynamicSparseArraysAMD.setindex_batch!
 const deletecolumns! = DynamicSparseArraysAMD.deletecolumns!      # a list of columns / rows in one device pass (dsa_mat_delete_batch)
 const deleterows! = DynamicSparseArraysAMD.deleterows!
+const dropzeros! = DynamicSparseArraysAMD.dropzeros!              # SparseArrays' dropzeros! / droptol! in place on the device (dsa_mat_droptol):
+const droptol! = DynamicSparseArraysAMD.droptol!                  # droptol!(A, tol; rows = nothing, cols = nothing)
+const count_droptol = DynamicSparseArraysAMD.count_droptol
 
 end # module

@@ -25,7 +25,7 @@ export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC
        deletecolumn!, deleterow!, deletecolumns!, deleterows!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
        keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev,
-       scale!, reduce_rows, reduce_cols, mul_rows, mul_cols, mul_sparse
+       scale!, reduce_rows, reduce_cols, mul_rows, mul_cols, mul_sparse, dropzeros!, droptol!, count_droptol
 
 const libdsa = get(ENV, "DSA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libdsa_hip.so"))
 
@@ -707,5 +707,31 @@ function scale!(a::DynamicSparseMatrix; alpha::Real = 1.0, rows::Union{Nothing,A
         cols === nothing ? Ptr{Float64}(C_NULL) : pointer(isempty(c) ? one : c), length(c)))
     return a
 end
+
+# SparseArrays' dropzeros! / droptol! in place on the device (include/dsa.h: dsa_mat_droptol; what the reference does with one
+# setindex! of a zero per cell, src/matrix.jl:43-62): a cell with |v| <= tol, <= rows[i] or <= cols[j] leaves both orientations (IEEE
+# comparisons: NaN is never dropped), an emptied column or row stays as an empty partition, the survivors are spread as by a root
+# rebalance; when nothing is dropped nothing changes.  rows / cols are indexed by the mapped integer key; nothing: the vector is
+# absent.  A negative tol matches nothing (purely relative dropping).  Returns a; count_droptol returns the number of entries the same
+# call would drop and modifies nothing.
+function _droptol(a::DynamicSparseMatrix, tol::Real, rows, cols, count_only::Bool)
+    r = rows === nothing ? Float64[] : Vector{Float64}(rows)
+    c = cols === nothing ? Float64[] : Vector{Float64}(cols)
+    one = Float64[1.0]                                    # a given vector of length 0 is still a non-NULL pointer
+    out = Ref{Int64}(0)
+    GC.@preserve r c one _check(ccall((:dsa_mat_droptol, libdsa), Int32,
+        (Ptr{Cvoid}, Float64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int32, Ref{Int64}), a.h, Float64(tol),
+        rows === nothing ? Ptr{Float64}(C_NULL) : pointer(isempty(r) ? one : r), length(r),
+        cols === nothing ? Ptr{Float64}(C_NULL) : pointer(isempty(c) ? one : c), length(c), Int32(count_only), out))
+    return out[]
+end
+function SparseArrays.droptol!(a::DynamicSparseMatrix, tol::Real; rows::Union{Nothing,AbstractVector{<:Real}} = nothing,
+                               cols::Union{Nothing,AbstractVector{<:Real}} = nothing)
+    _droptol(a, tol, rows, cols, false)
+    return a
+end
+SparseArrays.dropzeros!(a::DynamicSparseMatrix) = SparseArrays.droptol!(a, 0.0)
+count_droptol(a::DynamicSparseMatrix, tol::Real; rows::Union{Nothing,AbstractVector{<:Real}} = nothing,
+              cols::Union{Nothing,AbstractVector{<:Real}} = nothing) = _droptol(a, tol, rows, cols, true)
 
 end # module

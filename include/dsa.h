@@ -448,6 +448,35 @@ int32_t dsa_mat_scale(dsa_mat_t* h, double alpha, const double* r, int64_t nr, c
  * device memory.  For one or two keys dsa_mat_deletecolumn / dsa_mat_deleterow remain the cheaper calls. */
 int32_t dsa_mat_delete_batch_dev(dsa_mat_t* h, int32_t orientation, const int64_t* d_keys, int64_t n, int64_t* removed_out);
 int32_t dsa_mat_delete_batch(dsa_mat_t* h, int32_t orientation, const int64_t* keys, int64_t n, int64_t* removed_out);
+/* dropzeros! / droptol! (csrc/droptol.hip): every small stored entry leaves the matrix in place, in one device pass.  No reference
+ * counterpart as a bulk call — SparseArrays' dropzeros! / droptol! for a SparseMatrixCSC; it replaces one setindex! with a zero per
+ * cell (src/matrix.jl:43-62).  A cell (i, j) with stored value v is DROPPED iff |v| <= tol, or rtol is given and |v| <= rtol[i - 1],
+ * or ctol is given and |v| <= ctol[j - 1].  The comparisons are IEEE: a NaN value is never dropped, a NaN or negative threshold
+ * matches nothing, +-Inf goes only against a threshold of +Inf, -0.0 counts as zero.  dropzeros! is tol = 0 without vectors; a negative
+ * tol is valid and matches nothing (purely relative dropping through the vectors).  rtol or ctol NULL (its length argument is then
+ * ignored) means that the vector is absent; when given, nr must equal m and nc must equal n (dsa_mat_size after the queued single
+ * writes have been applied).
+ * CONTENT, partition tables, size() and the number of partitions afterwards are those of A[i, j] = 0 for every dropped cell in turn:
+ * the cell leaves BOTH orientations; a column or row that loses its last cell stays as an empty live partition — no semaphore is
+ * ever cleared, with tol = +Inf every cell goes and every partition stays.  The LAYOUT follows the rule of the batched delete:
+ * capacity, segment capacity, height and table_len stay, and the survivors of each orientation, in slot order, are spread over
+ * [1, capacity] — what dsa_mat_rebalance_root gives (a single-leaf array is not moved).  The call never shrinks; the next write that
+ * reaches the root does.
+ * When NOTHING is dropped nothing at all changes: no rebalance, no epoch moves (cached SpMV plans survive), the slot arrays keep
+ * their bytes.  count_only != 0 evaluates the predicate and modifies nothing.  dropped_out (host pointer, may be NULL) receives the
+ * number of matrix entries the predicate drops.  A call that drops something returns with both streams drained.  The same input
+ * gives the same bits on every call (no floating-point atomics).
+ * Every error is found before the first write — both orientations and the cached SpMV plans stay as they were: DSA_EMODE in fill
+ * mode; DSA_EARG: tol is NaN, nr != m or nc != n for a vector that is given; DSA_EBOUNDS: a vector is given and a stored entry lies
+ * outside size(m) (the check of dsa_mat_scale; the scalar-only form needs no bounds and works on such a matrix).  Queued single
+ * writes are applied first.
+ * _dev: d_rtol / d_ctol are device arrays, read on BOTH orientations' streams: they must hold their final contents when the call is
+ * made and stay valid and unchanged until it returns (the host waits for the decide pass).  The host form stages rtol and ctol
+ * through pooled device memory.  For a handful of cells dsa_mat_set_batch with zeros remains the cheaper call. */
+int32_t dsa_mat_droptol_dev(dsa_mat_t* h, double tol, const double* d_rtol, int64_t nr, const double* d_ctol, int64_t nc,
+                            int32_t count_only, int64_t* dropped_out);
+int32_t dsa_mat_droptol(dsa_mat_t* h, double tol, const double* rtol, int64_t nr, const double* ctol, int64_t nc,
+                        int32_t count_only, int64_t* dropped_out);
 /* ---- column-range shards. No reference counterpart: the reference is single-process.  One PROCESS per GPU:
  * each process selects its device (dsa_set_device), builds ITS shard and runs the local SpMV; the single data-path collective —
  * the all-reduce (sum) of the partial y — is dsa_shard_allreduce_dev below (RCCL behind this ABI), or whatever the host layer has

@@ -4,7 +4,6 @@
 #include "host.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <functional>
 #include <mutex>
@@ -23,8 +22,8 @@ struct KeyScan {
         lo = l; hi = h; zero = z;
     }
     bool empty() const { return hi < lo; }
-    bool fit32() const { return !g_force_wide && (empty() || (key_fits32(lo) && key_fits32(hi))); }
     KeyRange range() const { KeyRange r; if (!empty()) { r.lo = lo; r.hi = hi; } return r; }
+    bool fit32() const { return !needs_wide(range()); }
 };
 }  // namespace
 
@@ -55,8 +54,7 @@ void pma_build_dev(Pma& P, const int64_t* d_part, const int64_t* d_key, const do
     }
     BuildScratch sc;
     int64_t counts[2] = {0, 0};
-    static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-    const auto tp0 = std::chrono::steady_clock::now();
+    const auto tp0 = Clock::now();
     // While the sort kernels run (build_prepare calls this between enqueueing them and waiting for the counts): tables and slot buffers
     // for the UPPER bounds — every triple a cell of its own, every partition of the key range present.  The exact sizes are known only
     // from the counts, but capacity_for is monotone and the allocations (13 of them, a dozen memsets) used to sit between the sort and
@@ -98,7 +96,7 @@ void pma_build_dev(Pma& P, const int64_t* d_part, const int64_t* d_key, const do
     hipError_t e;
     try { e = build_prepare(d_part, d_key, d_val, nnz, part_range, key_range, sc, counts, P.stream, &prealloc); }
     catch (...) { build_abort(sc); throw; }          // (an allocation of `prealloc` failed: the scratch of the sort is released here)
-    const auto tp1 = std::chrono::steady_clock::now();
+    const auto tp1 = Clock::now();
     launch_check(e, "K-build prepare: ");
     const int64_t np = mode == 0 ? counts[1] : (mode == 2 ? nparts_explicit : 0);
     const int64_t n = counts[0] + np;
@@ -113,7 +111,7 @@ void pma_build_dev(Pma& P, const int64_t* d_part, const int64_t* d_key, const do
         ensure_capacity_alloc(P, 2 * capacity);
         if (P.has_cols && np > 0) HIPCHK(hipMemsetAsync(P.col_live, 1, (size_t)np, P.stream));
     } catch (...) { build_abort(sc); throw; }
-    const auto tp2 = std::chrono::steady_clock::now();
+    const auto tp2 = Clock::now();
     ++P.layout_epoch;
     // (the emit kernels are only enqueued: the spread goes in right behind them, the scratch of the sort is released after the one
     //  stream wait of upload_ctl instead of after a wait of its own)
@@ -132,7 +130,7 @@ void pma_build_dev(Pma& P, const int64_t* d_part, const int64_t* d_key, const do
     }
     e = build_emit(d_val, combine, sc, P.K(), P.V(), P.has_cols ? P.col_keys : nullptr, mode, nparts_explicit, P.stream, false);
     if (e != hipSuccess) { emit_order.unlock(); build_abort(sc); fail(DSA_EHIP, std::string("K-build emit: ") + hipGetErrorString(e)); }
-    const auto tp3 = std::chrono::steady_clock::now();
+    const auto tp3 = Clock::now();
     P.h_ctl->stat_rebalances = 0; P.h_ctl->stat_window_slots = 0;
     if (P.capacity() != P.h_ctl->segment_capacity) { P.h_ctl->stat_rebalances = 1; P.h_ctl->stat_window_slots = P.capacity(); }
     try {
@@ -142,11 +140,9 @@ void pma_build_dev(Pma& P, const int64_t* d_part, const int64_t* d_key, const do
         upload_ctl(P);
     } catch (...) { if (emit_order.owns_lock()) emit_order.unlock(); build_abort(sc); throw; }
     build_abort(sc);          // (stream already waited for: releases the scratch)
-    if (dbg_time) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    if (dbg_time())
         fprintf(stderr, "  [pma_build_dev] prepare (alloc + sorts + scans) %.1f ms  tables/slot alloc %.1f ms  emit (+ free) %.1f ms  spread + ctl %.1f ms\n",
-                ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3), ms(tp3, std::chrono::steady_clock::now()));
-    }
+                elapsed_ms(tp0, tp1), elapsed_ms(tp1, tp2), elapsed_ms(tp2, tp3), elapsed_ms(tp3));
 }
 
 // Both orientations of a matrix from ONE sort of the caller's triples (round 6).  A = the orientation whose partitions are d_part

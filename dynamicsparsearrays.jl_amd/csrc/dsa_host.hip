@@ -1,12 +1,15 @@
-// csrc/dsa_host.hip — the handle layer of libdsa_hip.so: the last-error text, the table of development switches, the fill-mode
-// staging buffer, what is written in terms of dsa_vec / dsa_pcsc / dsa_mat (flush and apply of queued writes, the builds of both
-// orientations, slices, the dense product) and the C ABI of include/dsa.h.
+// csrc/dsa_host.hip — the handle layer of libdsa_hip.so: the last-error text, the roctx loader, the table of development switches,
+// what is written in terms of dsa_vec / dsa_pcsc (flush and apply of queued vector writes, packs, slices), the dense product of a
+// matrix, and the C ABI of include/dsa.h.
 //
-// Everything that works on ONE packed-memory array (the Pma of host.h) is in the engine units pma_host.hip (lifecycle, geometry,
-// rebalances, reads), writes_host.hip (yield loop around the sequencer, batch-parallel rounds), build_host.hip (K-build) and
-// spmv_host.hip (SpMV meta and plan); the exports, the multi-vector product and the device import sit behind three-line entry points
-// in export_host.hip, spmm_host.hip, selprod_host.hip and ingest_host.hip; the sparse-x product and the parity hooks have entry points of their own in
-// sparsex_host.hip and raw_host.hip.
+// The matrix entry points are short wrappers: the argument checks that belong to the ABI plus one or two calls.  What they call is in
+// units of its own: the fill-mode buffer in fill_host.hip, every write to a matrix (the builds of both orientations, the set batch
+// and its strategies, the flush of queued writes, the delete of one column or row) in matwrite_host.hip; the exports, the products,
+// the device import, scale, the batched delete and droptol in export_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip,
+// ingest_host.hip, scale_host.hip, delbatch_host.hip and droptol_host.hip; the sparse-x product and the parity hooks have entry points
+// of their own in sparsex_host.hip and raw_host.hip.  Everything that works on ONE packed-memory array (the Pma of host.h) is in the
+// engine units pma_host.hip (lifecycle, geometry, rebalances, reads), writes_host.hip (yield loop around the sequencer, batch-parallel
+// rounds), build_host.hip (K-build) and spmv_host.hip (SpMV meta and plan).
 //
 // Everything that touches slots runs on the GPU (rebalance.hip, sequencer.hip, spmv.hip).  The host
 // keeps only: the control scalars of each PMA (mirrored from the device control block), the integer
@@ -22,10 +25,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 using namespace dsa;
@@ -114,459 +114,11 @@ namespace {
 // Single setindex! calls are write-combined on the host (the "buffered batched writes" of the path): they are queued and
 // applied, in order, by ONE sequencer launch at the latest before the next call that observes the structure.
 constexpr size_t PENDING_FLUSH = 1u << 16;
-inline bool fill_row_test_and_set(FillBuffer& b, int64_t row) {
-    if (row >= 1 && row < ((int64_t)1 << 28)) {
-        const size_t w = (size_t)(row >> 6);
-        if (w >= b.row_bits.size()) b.row_bits.resize(std::max<size_t>(2 * b.row_bits.size(), w + 1024), 0ull);
-        const uint64_t bit = 1ull << (row & 63);
-        const bool was = (b.row_bits[w] & bit) != 0;
-        b.row_bits[w] |= bit;
-        return was;
-    }
-    return !b.rows_far.insert(row).second;
-}
-// pinned staging chunks are expensive to allocate and free (milliseconds each): one set is kept for the next fill-mode matrix
-struct FillStagingCache { std::mutex mu; int64_t* hI[2] = {nullptr, nullptr}; int64_t* hJ[2] = {nullptr, nullptr}; double* hV[2] = {nullptr, nullptr}; int device = -1; };
-static FillStagingCache g_fill_cache;
-void fill_release(FillBuffer& b) {
-    if (b.stream) hipStreamSynchronize(b.stream);
-    {
-        std::lock_guard<std::mutex> lk(g_fill_cache.mu);
-        if (b.hI[0] && g_fill_cache.hI[0] == nullptr) {
-            for (int k = 0; k < 2; ++k) { g_fill_cache.hI[k] = b.hI[k]; g_fill_cache.hJ[k] = b.hJ[k]; g_fill_cache.hV[k] = b.hV[k]; b.hI[k] = nullptr; b.hJ[k] = nullptr; b.hV[k] = nullptr; }
-            g_fill_cache.device = b.device;
-        }
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (b.hI[k]) hipHostFree(b.hI[k]);
-        if (b.hJ[k]) hipHostFree(b.hJ[k]);
-        if (b.hV[k]) hipHostFree(b.hV[k]);
-        if (b.uploaded[k]) hipEventDestroy(b.uploaded[k]);
-    }
-    pool_free(b.dI); pool_free(b.dJ); pool_free(b.dV);
-    pool_free(b.d_acc); pinned_free(b.h_acc);
-    if (b.stream) stream_put(b.stream, b.device);
-    b = FillBuffer();
-}
 
-// ---- device-resident fill buffer --------------------------------------------------------------------------------------
-void fill_init(FillBuffer& b) {
-    if (b.stream) return;
-    HIPCHK(hipSetDevice(g_device));
-    b.device = g_device;
-    HIPCHK(stream_get(&b.stream));
-    {
-        std::lock_guard<std::mutex> lk(g_fill_cache.mu);
-        if (g_fill_cache.hI[0] != nullptr && g_fill_cache.device == b.device)
-            for (int k = 0; k < 2; ++k) { b.hI[k] = g_fill_cache.hI[k]; b.hJ[k] = g_fill_cache.hJ[k]; b.hV[k] = g_fill_cache.hV[k]; g_fill_cache.hI[k] = nullptr; g_fill_cache.hJ[k] = nullptr; g_fill_cache.hV[k] = nullptr; }
-    }
-    {
-        void* p = nullptr;
-        HIPCHK(pool_alloc(&p, 64)); b.d_acc = static_cast<long long*>(p);
-        HIPCHK(pinned_alloc(&p, 64)); b.h_acc = static_cast<long long*>(p);
-        b.h_acc[0] = INT64_MAX; b.h_acc[1] = INT64_MIN; b.h_acc[2] = INT64_MAX; b.h_acc[3] = INT64_MIN; b.h_acc[4] = 0;
-        HIPCHK(hipMemcpyAsync(b.d_acc, b.h_acc, 5 * sizeof(long long), hipMemcpyHostToDevice, b.stream));
-        HIPCHK(hipStreamSynchronize(b.stream));             // (h_acc is reused as the read-back target)
-    }
-    for (int k = 0; k < 2; ++k) {
-        HIPCHK(hipEventCreateWithFlags(&b.uploaded[k], hipEventDisableTiming));
-        if (b.hI[k]) continue;
-        HIPCHK(hipHostMalloc(&b.hI[k], (size_t)FillBuffer::CHUNK * sizeof(int64_t), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(&b.hJ[k], (size_t)FillBuffer::CHUNK * sizeof(int64_t), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(&b.hV[k], (size_t)FillBuffer::CHUNK * sizeof(double), hipHostMallocDefault));
-    }
-}
-// ships what is staged in the current pinned chunk and not yet sent (triples [b.sent, b.fill)) to HBM, asynchronously; a chunk that
-// is full (or `finish`: the end of a batch) is closed — its event recorded — and the other chunk becomes current.  Pieces go up
-// while the caller's memcpy fills the rest of the chunk, so that closefillmode! waits for one piece (6 MB), not for a chunk (24 MB).
-void fill_upload_chunk(FillBuffer& b, bool finish = true) {
-    if (b.fill == 0) return;
-    HIPCHK(hipSetDevice(b.device));
-    const int64_t npiece = b.fill - b.sent;
-    if (npiece > 0) {
-        if (b.dlen + npiece > b.dcap) {          // grow geometrically: new arrays, device-to-device copy of what is resident
-            const int64_t ncap = std::max<int64_t>(2 * b.dcap, std::max<int64_t>(b.dlen + npiece, 4 * FillBuffer::CHUNK));
-            int64_t *nI = nullptr, *nJ = nullptr; double* nV = nullptr;
-            HIPCHK(pool_alloc(reinterpret_cast<void**>(&nI), (size_t)ncap * sizeof(int64_t)));
-            HIPCHK(pool_alloc(reinterpret_cast<void**>(&nJ), (size_t)ncap * sizeof(int64_t)));
-            HIPCHK(pool_alloc(reinterpret_cast<void**>(&nV), (size_t)ncap * sizeof(double)));
-            if (b.dlen > 0) {
-                HIPCHK(hipMemcpyAsync(nI, b.dI, (size_t)b.dlen * sizeof(int64_t), hipMemcpyDeviceToDevice, b.stream));
-                HIPCHK(hipMemcpyAsync(nJ, b.dJ, (size_t)b.dlen * sizeof(int64_t), hipMemcpyDeviceToDevice, b.stream));
-                HIPCHK(hipMemcpyAsync(nV, b.dV, (size_t)b.dlen * sizeof(double), hipMemcpyDeviceToDevice, b.stream));
-            }
-            HIPCHK(hipStreamSynchronize(b.stream));       // earlier uploads into the old arrays have landed
-            pool_free(b.dI); pool_free(b.dJ); pool_free(b.dV);
-            b.dI = nI; b.dJ = nJ; b.dV = nV; b.dcap = ncap;
-        }
-        const int c = b.cur;
-        HIPCHK(hipMemcpyAsync(b.dI + b.dlen, b.hI[c] + b.sent, (size_t)npiece * sizeof(int64_t), hipMemcpyHostToDevice, b.stream));
-        HIPCHK(hipMemcpyAsync(b.dJ + b.dlen, b.hJ[c] + b.sent, (size_t)npiece * sizeof(int64_t), hipMemcpyHostToDevice, b.stream));
-        HIPCHK(hipMemcpyAsync(b.dV + b.dlen, b.hV[c] + b.sent, (size_t)npiece * sizeof(double), hipMemcpyHostToDevice, b.stream));
-        {   // the value ranges of the piece, folded into the running ones behind its upload
-            LAUNCH("key range", launch_key_scan_acc(b.dI + b.dlen, b.dJ + b.dlen, npiece, b.d_acc, b.stream));
-        }
-        b.dlen += npiece;
-        b.sent = b.fill;
-    }
-    if (!finish && b.fill < FillBuffer::CHUNK) return;
-    const int c = b.cur;
-    HIPCHK(hipEventRecord(b.uploaded[c], b.stream));
-    b.in_flight[c] = true;
-    b.fill = 0; b.sent = 0;
-    b.cur = 1 - c;
-    if (b.in_flight[b.cur]) { HIPCHK(hipEventSynchronize(b.uploaded[b.cur])); b.in_flight[b.cur] = false; }   // its pinned memory is free again
-}
-// addelem!  src/buffer.jl:20-31 for n entries (n = 1: one setindex! in fill mode)
-void fill_append(FillBuffer& b, const int64_t* I, const int64_t* J, const double* V, int64_t n) {
-    fill_init(b);
-    int64_t k = 0;
-    while (k < n) {
-        const int64_t room = std::min(FillBuffer::CHUNK - b.fill, FillBuffer::PIECE - (b.fill - b.sent));      // up to the end of the chunk / of the piece
-        const int64_t take = std::min(room, n - k);
-        std::memcpy(b.hI[b.cur] + b.fill, I + k, (size_t)take * sizeof(int64_t));
-        std::memcpy(b.hJ[b.cur] + b.fill, J + k, (size_t)take * sizeof(int64_t));
-        std::memcpy(b.hV[b.cur] + b.fill, V + k, (size_t)take * sizeof(double));
-        b.fill += take; k += take;
-        if (b.fill == FillBuffer::CHUNK || b.fill - b.sent >= FillBuffer::PIECE) fill_upload_chunk(b, false);
-    }
-    // a batch of appends has ended: what is staged goes up now (asynchronously), so that closefillmode! finds almost nothing left
-    // in pinned memory — single-element appends (setindex! in fill mode) only ship whole quarter chunks
-    if (b.fill - b.sent >= (n > 1 ? FillBuffer::EAGER : FillBuffer::CHUNK / 4)) fill_upload_chunk(b, false);
-    b.length += n;
-}
-
-void bind_device(const Pma& P) { HIPCHK(hipSetDevice(P.device)); }
-void check_key(int64_t k) { if (k == 0) fail(DSA_EKEY, "0 is the reserved semaphore key (src/pcsr.jl:23)"); }
-Op make_op(int32_t kind, int64_t a, int64_t b, double v) { Op o; o.a = a; o.b = b; o.v = v; o.kind = kind; o.pad = 0; return o; }
 Pma& orient(dsa_mat* h, int32_t o) {
     if (!h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
     if (o != DSA_COLMAJOR && o != DSA_ROWMAJOR) fail(DSA_EARG, "orientation must be 0 or 1");
     return o == DSA_COLMAJOR ? h->col : h->row;
-}
-
-// both orientations from (row, col, value) triples that are ALREADY in HBM (they stay the caller's): dynamicsparse(I, J, V) after its
-// upload, closefillmode! straight from the device-resident fill buffer.  On failure nothing of the two structures is left behind.
-void mat_build_major_dev(dsa_mat* h, const int64_t* dI, const int64_t* dJ, const double* dV, int64_t nnz, bool wide_rows, bool wide_cols,
-                         KeyRange rows = KeyRange(), KeyRange cols = KeyRange()) {
-    try {
-        static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-        const auto ti0 = std::chrono::steady_clock::now();
-        pma_init_common(h->col, true, true);
-        pma_init_common(h->row, true, true);
-        const auto tb0 = std::chrono::steady_clock::now();
-        if (dbg_time) fprintf(stderr, "[mat_build_major] handles (streams, control blocks) %.2f ms\n", std::chrono::duration<double, std::milli>(tb0 - ti0).count());
-        // the two orientations are independent structures on their own streams and both only read the triples: built side by side
-        // (the rowmajor one on a helper thread; each build waits once for its cell / partition counts)
-        // large builds: ONE sort of the triples, the rowmajor orientation from the cells colmajor's emit leaves behind (mat_build_both_dev);
-        // smaller ones, a shared stream or an injected failure: two independent builds side by side
-        if (nnz >= (1 << 16) && h->col.stream != h->row.stream && dev_env("DSA_FAIL_BUILD") == nullptr) {
-            const bool both = mat_build_both_dev(h->col, h->row, dJ, dI, dV, nnz, wide_rows, wide_cols, cols, rows);
-            if (!both) pma_build_dev(h->row, dI, dJ, dV, nnz, DSA_COMBINE_ADD, 0, 0, wide_cols, rows, cols);
-            if (dbg_time) fprintf(stderr, "[mat_build_major] nnz=%lld both orientations (%s) %.1f ms\n", (long long)nnz, both ? "twin derived" : "general path",
-                                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count());
-            h->has_major = true;
-            return;
-        }
-        std::exception_ptr row_exc;
-        std::thread row_thread;
-        const bool side_by_side = h->col.stream != h->row.stream && nnz > 0;
-        if (side_by_side)
-            row_thread = std::thread([&] {
-                try { bind_device(h->row); pma_build_dev(h->row, dI, dJ, dV, nnz, DSA_COMBINE_ADD, 0, 0, wide_cols, rows, cols); }
-                catch (...) { row_exc = std::current_exception(); }
-            });
-        try { pma_build_dev(h->col, dJ, dI, dV, nnz, DSA_COMBINE_ADD, 0, 0, wide_rows, cols, rows); }      // dynamicsparsecolmajor(I, J, V): partitions = columns, keys = rows
-        catch (...) { if (row_thread.joinable()) row_thread.join(); throw; }
-        const auto tb1 = std::chrono::steady_clock::now();
-        if (side_by_side) { row_thread.join(); if (row_exc) std::rethrow_exception(row_exc); }
-        else pma_build_dev(h->row, dI, dJ, dV, nnz, DSA_COMBINE_ADD, 0, 0, wide_cols, rows, cols);      // dynamicsparsecolmajor(J, I, V): partitions = rows, keys = columns
-        if (dbg_time)
-            fprintf(stderr, "[mat_build_major] nnz=%lld colmajor %.1f ms  rowmajor %.1f ms\n", (long long)nnz,
-                    std::chrono::duration<double, std::milli>(tb1 - tb0).count(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb1).count());
-    } catch (...) {
-        // streams, control blocks and whatever slot buffers / tables exist by now (dsa_mat_destroy only looks at them once has_major is set)
-        pma_destroy(h->col);
-        pma_destroy(h->row);
-        throw;
-    }
-    h->has_major = true;
-}
-
-// dynamicsparse(I, J, V): upload + both builds; *rows_out / *cols_out receive the value ranges of the keys
-void mat_build_major(dsa_mat* h, const int64_t* I, const int64_t* J, const double* V, int64_t nnz, KeyRange* rows_out = nullptr, KeyRange* cols_out = nullptr) {
-    int64_t *dI = nullptr, *dJ = nullptr; double* dV = nullptr;
-    const auto tup0 = std::chrono::steady_clock::now();
-    HIPCHK(hipSetDevice(g_device));
-    try {
-        KeyRange rows, cols;
-        bool zr = false, zc = false;
-        if (nnz > 0) {
-            HIPCHK(pool_alloc(reinterpret_cast<void**>(&dI), (size_t)nnz * sizeof(int64_t)));
-            HIPCHK(pool_alloc(reinterpret_cast<void**>(&dJ), (size_t)nnz * sizeof(int64_t)));
-            HIPCHK(pool_alloc(reinterpret_cast<void**>(&dV), (size_t)nnz * sizeof(double)));
-            HIPCHK(hipMemcpy(dI, I, (size_t)nnz * sizeof(int64_t), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(dJ, J, (size_t)nnz * sizeof(int64_t), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(dV, V, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-            // value ranges (K-build's composite, the storage width of the keys, the size guesses) and the reserved key 0: one pass on
-            // the device over the arrays just uploaded — the host never loops over the caller's 10^7 keys
-            launch_check(device_key_scan(dI, dJ, nnz, &rows, &cols, &zr, &zc, nullptr), "key scan: ");
-        }
-        static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-        if (dbg_time) fprintf(stderr, "[mat_build_major] upload of %lld triples from caller memory + key scan %.1f ms\n", (long long)nnz,
-                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tup0).count());
-        if (rows_out) *rows_out = rows;
-        if (cols_out) *cols_out = cols;
-        if (zr || zc) check_key(0);
-        auto fit32 = [](const KeyRange& r) { return !g_force_wide && (!r.known() || (key_fits32(r.lo) && key_fits32(r.hi))); };
-        mat_build_major_dev(h, dI, dJ, dV, nnz, !fit32(rows), !fit32(cols), rows, cols);
-    } catch (...) { pool_free(dI); pool_free(dJ); pool_free(dV); throw; }      // (a failed build has synchronised and destroyed its streams)
-    pool_free(dI); pool_free(dJ); pool_free(dV);
-}
-
-// Host replay of ONE partition table (MappedPackedCSC.col_keys + which ids are tombstones) through a batch of writes: which write is
-// the first one the reference refuses?  Control logic like the integer density bounds — no slot is read or written here; the device
-// executes (and judges) every write.  Follows find(col_keys, col) + addcolumn! + the table half of addpartition!(pcsc, prev)
-// (src/pcsr.jl:341-351, 148-169, 114-146): a key that is present changes nothing; a key behind the last entry is pushed; a key whose
-// table slot prev+1 is a tombstone reuses it, unless no live id follows (semaphores[0]: BoundsError, :121-125); a key in front of an
-// occupied slot shifts the tail of the tables, which asserts on the first tombstone it meets (:129-133).
-struct TableReplay {
-    std::vector<int64_t> ck; std::vector<uint8_t> live;
-    int64_t last_tomb = 0, last_live = 0;          // 1-based index of the last tombstone / the last live entry (0: none)
-    void load(Pma& P) {
-        const int64_t len = P.h_ctl->table_len;
-        ck.resize((size_t)len); live.resize((size_t)len);
-        if (len > 0) {
-            HIPCHK(hipMemcpyAsync(ck.data(), P.col_keys, (size_t)len * sizeof(int64_t), hipMemcpyDeviceToHost, P.stream));
-            HIPCHK(hipMemcpyAsync(live.data(), P.col_live, (size_t)len, hipMemcpyDeviceToHost, P.stream));
-            HIPCHK(hipStreamSynchronize(P.stream));
-        }
-        rescan();
-    }
-    void rescan() {
-        last_tomb = 0; last_live = 0;
-        for (int64_t i = (int64_t)live.size(); i >= 1 && (last_tomb == 0 || last_live == 0); --i) {
-            if (live[(size_t)i - 1]) { if (last_live == 0) last_live = i; } else if (last_tomb == 0) last_tomb = i;
-        }
-    }
-    // find(col_keys, key) with tombstones (the host twin of d_find_table, csrc/find_dev.h): position of the key or of its predecessor
-    int64_t find(int64_t key, bool* exact) const {
-        int64_t from = 1, to = (int64_t)ck.size();
-        *exact = false;
-        while (from <= to) {
-            const int64_t mid = (from + to) >> 1;
-            int64_t i = mid;
-            while (i >= from && !live[(size_t)i - 1]) --i;
-            if (i < from) from = mid + 1;
-            else {
-                const int64_t c = ck[(size_t)i - 1];
-                if (c > key) to = i - 1;
-                else if (c < key) from = mid + 1;
-                else { *exact = true; return i; }
-            }
-        }
-        int64_t i = to;
-        while (i > 0 && !live[(size_t)i - 1]) --i;
-        return i;
-    }
-    // a write into partition `key`: 0 when the table accepts it (and the table as it is afterwards), else the reference's error
-    int32_t touch(int64_t key) {
-        bool exact = false;
-        const int64_t prev = find(key, &exact);
-        if (exact) return 0;
-        const int64_t len = (int64_t)ck.size();
-        if (prev == len) { ck.push_back(key); live.push_back(1); last_live = len + 1; return 0; }
-        if (!live[(size_t)prev]) {                                  // entry prev + 1 is a tombstone: reuse it
-            if (last_live <= prev + 1) return DSA_EBOUNDS;
-            ck[(size_t)prev] = key; live[(size_t)prev] = 1;
-            if (last_tomb == prev + 1) rescan();
-            return 0;
-        }
-        if (last_tomb >= prev + 1) return DSA_EASSERT;               // the shift of the tail meets a tombstone
-        ck.insert(ck.begin() + prev, key); live.insert(live.begin() + prev, (uint8_t)1);
-        last_live = len + 1;
-        return 0;
-    }
-};
-
-// setindex! on both orientations for ops [0, n)  src/matrix.jl:53-59
-void mat_apply_sets(dsa_mat* h, const int64_t* I, const int64_t* J, const double* V, int64_t n) {
-    // colmajor[row, col] = val / rowmajor[col, row] = val: the batch-parallel path takes the caller's columns as they are, the other
-    // branches below build the op arrays they need
-    const OpBatch bc(OP_MPCSC_SET, I, J, V, n), br(OP_MPCSC_SET, J, I, V, n);
-    std::vector<Op> oc, orw;
-    auto build_ops = [&] {
-        if (!oc.empty() || n == 0) return;
-        oc.resize((size_t)n); orw.resize((size_t)n);
-        for (int64_t k = 0; k < n; ++k) {
-            oc[(size_t)k] = make_op(OP_MPCSC_SET, I[k], J[k], V[k]);
-            orw[(size_t)k] = make_op(OP_MPCSC_SET, J[k], I[k], V[k]);
-        }
-    };
-    // size(m) after writes [from, to): a write of a nonzero raises it (src/matrix.jl:44-47)
-    auto grow_size = [&](int64_t from, int64_t to) {
-        for (int64_t k = from; k < to; ++k) if (V[k] != 0.0) { h->m = std::max(h->m, I[k]); h->n = std::max(h->n, J[k]); }
-    };
-    // Without tombstones an OP_MPCSC_SET cannot fail (the reference's assert / bounds paths of addpartition! need a
-    // deleted partition, App. A.6 (3)), so the two orientations can be updated concurrently; otherwise the colmajor
-    // batch runs first and the rowmajor batch is cut at the failing op, like the reference's statement order.
-    const bool no_tombstones = h->col.view().dense && h->row.view().dense;
-    static const bool par = [] { const char* e = dev_env("DSA_PARBATCH"); return !(e && e[0] == '0'); }();
-    // With tombstones a write can only fail while it CREATES a partition in the middle of the table (addpartition!(pcsc, prev),
-    // src/pcsr.jl:114-146: the two asserts, and the lookup behind a tombstoned tail).  A batch whose partition keys never decrease and start
-    // at or behind the last table entry — which must be live — only ever writes to that entry or appends behind it (find() returns the
-    // last position, addcolumn! takes its push! branch, src/pcsr.jl:148-154): it cannot fail either, and the two orientations may run side
-    // by side.  That is column generation with deletions: new columns get new, larger ids while old ones are deleted (config 5 + deletecolumn!:
-    // 445 -> 330 ms).  Anything else with tombstones keeps the reference's statement order below.
-    auto cannot_fail = [&](Pma& P, const int64_t* part_keys_of_ops) -> bool {
-        const Ctl& c = *P.h_ctl;
-        if (P.view().dense) return true;
-        if (c.table_len <= 0 || c.n_pending != 0) return false;
-        uint8_t live = 0; int64_t last_key = 0;
-        HIPCHK(hipMemcpyAsync(&live, P.col_live + (c.table_len - 1), 1, hipMemcpyDeviceToHost, P.stream));
-        HIPCHK(hipMemcpyAsync(&last_key, P.col_keys + (c.table_len - 1), sizeof(int64_t), hipMemcpyDeviceToHost, P.stream));
-        HIPCHK(hipStreamSynchronize(P.stream));
-        if (!live) return false;
-        int64_t running = last_key;
-        for (int64_t k = 0; k < n; ++k) { if (part_keys_of_ops[k] < running) return false; running = part_keys_of_ops[k]; }
-        return true;
-    };
-    const bool side_by_side_ok = no_tombstones || (n >= 128 && cannot_fail(h->col, J) && cannot_fail(h->row, I));
-    if (par && side_by_side_ok && n >= 128) {
-        // batch-parallel rounds per orientation (writes to existing columns with disjoint footprints run concurrently; new
-        // columns and anything else fall back to the sequential sequencer inside run_ops_parallel)
-        int32_t ec = 0, er = 0;
-        static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-        // the two orientations are independent structures on their own streams: their round / sequencer loops (host-driven)
-        // run side by side, the rowmajor one on a helper thread
-        const auto t0 = std::chrono::steady_clock::now();
-        int64_t dc = 0, dr = 0;
-        std::exception_ptr row_exc;
-        auto t_row_done = t0;
-        const bool side_by_side = h->col.stream != h->row.stream;
-        std::thread row_thread;
-        if (side_by_side)
-            row_thread = std::thread([&] {
-                try { bind_device(h->row); dr = run_ops_parallel(h->row, br, &er); t_row_done = std::chrono::steady_clock::now(); }
-                catch (...) { row_exc = std::current_exception(); }
-            });
-        const int64_t rounds0 = h->row.stat_par_rounds;
-        try { dc = run_ops_parallel(h->col, bc, &ec); }
-        catch (...) { if (row_thread.joinable()) row_thread.join(); throw; }
-        const auto t1 = std::chrono::steady_clock::now();
-        if (side_by_side) { row_thread.join(); if (row_exc) std::rethrow_exception(row_exc); }
-        else dr = run_ops_parallel(h->row, br, &er);
-        if (dbg_time)
-            fprintf(stderr, "[mat_apply_sets] n=%lld both orientations %.2f ms (colmajor done after %.2f ms, rowmajor after %.2f ms)  colmajor (par %lld seq %lld ext %lld)  "
-                    "rowmajor (par %lld seq %lld ext %lld rounds +%lld)\n", (long long)n,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
-                    std::chrono::duration<double, std::milli>(t1 - t0).count(), std::chrono::duration<double, std::milli>(t_row_done - t0).count(), (long long)h->col.stat_par_ops,
-                    (long long)h->col.stat_seq_ops, (long long)h->col.h_ctl->stat_extends, (long long)h->row.stat_par_ops, (long long)h->row.stat_seq_ops,
-                    (long long)h->row.h_ctl->stat_extends, (long long)(h->row.stat_par_rounds - rounds0));
-        if (dbg_time)
-            fprintf(stderr, "    rowmajor: sequencer launches %lld  stops by reason [0 unplannable %lld, 1 newcol %lld, 2 limits %lld, 3 shifts %lld, 4 semleaf %lld, "
-                    "5 window %lld, 6 scan %lld, 7 conflict %lld]\n", (long long)h->row.stat_seq_launches, (long long)h->row.stat_why[0], (long long)h->row.stat_why[1],
-                    (long long)h->row.stat_why[2], (long long)h->row.stat_why[3], (long long)h->row.stat_why[4], (long long)h->row.stat_why[5],
-                    (long long)h->row.stat_why[6], (long long)h->row.stat_why[7]);
-        if (dbg_time && h->row.h_ctl->prof[7] != 0) {      // -DDSA_PROFILE builds only: shader-clock split of the rowmajor sequencer (cumulative)
-            const int64_t* q = h->row.h_ctl->prof;
-            const double us = 1.0 / 100.0;                   // s_memtime ticks at 100 MHz
-            fprintf(stderr, "    rowmajor sequencer profile (cumulative): kernel %.0f us | %lld matrix writes: table lookup %.0f us, %lld new partitions %.0f us, write in partition %.0f us "
-                    "[partition end %.0f, find %.0f, insert/shift %.0f, scan+rebalance %.0f (%lld in-block rebalances %.0f us, %lld slots)] | %lld table merges %.0f us\n",
-                    q[7] * us, (long long)q[4], q[0] * us, (long long)q[5], q[1] * us, q[2] * us, q[11] * us, q[8] * us, q[9] * us, q[10] * us, (long long)q[13], q[12] * us,
-                    (long long)q[14], (long long)q[6], q[3] * us);
-        }
-        const int64_t done = std::min(dc, dr);
-        grow_size(0, std::min(done + 1, n));
-        if (ec && er && dr < dc) fail(er, err_text(er));      // both halves failed: the rowmajor half of the EARLIER write comes first
-        if (ec) fail(ec, err_text(ec));
-        if (er) fail(er, err_text(er));
-        return;
-    }
-    build_ops();
-    if (no_tombstones && h->col.stream != h->row.stream) {
-        // A small batch (a column or a few that arrive together, a row): the orientation in which its writes fall into MANY
-        // partitions takes the local rounds (one wave per op: k_local_rounds), the one in which they share a few partitions — writes
-        // into one column are ordered by nature — its sequencer, side by side.  16 writes of a new column: 218 -> ~120 us.
-        if (par && n >= 8) {
-            std::vector<int64_t> di(I, I + n), dj(J, J + n);
-            std::sort(di.begin(), di.end()); std::sort(dj.begin(), dj.end());
-            const int64_t ni = std::unique(di.begin(), di.end()) - di.begin(), nj = std::unique(dj.begin(), dj.end()) - dj.begin();
-            Pma* rounds = nullptr; Pma* seq = nullptr; const std::vector<Op>* ro = nullptr; const std::vector<Op>* so = nullptr;
-            if (ni >= 2 * nj && ni >= 8) { rounds = &h->row; ro = &orw; seq = &h->col; so = &oc; }          // many rows, few columns
-            else if (nj >= 2 * ni && nj >= 8) { rounds = &h->col; ro = &oc; seq = &h->row; so = &orw; }     // many columns, few rows
-            if (rounds != nullptr) {
-                SeqRun rs;
-                seq_start(rs, *seq, *so);
-                int32_t er = 0;
-                int64_t dr = 0;
-                try { dr = run_ops_parallel(*rounds, *ro, &er); } catch (...) { while (seq_step(rs)) {} throw; }
-                while (seq_step(rs)) {}
-                const int64_t done = std::min(dr, rs.applied);
-                grow_size(0, std::min(done + 1, n));
-                if (rs.err) fail(rs.err, err_text(rs.err));
-                if (er) fail(er, err_text(er));
-                return;
-            }
-        }
-        SeqRun rc, rr;
-        run_ops_pair(h->col, oc, h->row, orw, rc, rr);
-        const int64_t done = std::min(rc.applied, rr.applied);
-        grow_size(0, std::min(done + 1, n));
-        if (rc.err) fail(rc.err, err_text(rc.err));
-        if (rr.err) fail(rr.err, err_text(rr.err));
-        return;
-    }
-    // tombstones present: a write that creates a column can fail (src/pcsr.jl:124,132), so the colmajor batch runs first and the
-    // rowmajor batch is cut at the failing op, like the reference's statement order — still through the batch-parallel
-    // rounds for everything that is plannable (writes to existing columns); new columns take the sequencer's literal path.
-    //
-    // The state after a FAILED batch is the reference's too (round 6; until then colmajor could hold writes behind the failing one):
-    // the reference stops at write k with colmajor holding writes [0, k] when its rowmajor statement threw, [0, k) when the colmajor one
-    // did, rowmajor [0, k) either way (src/matrix.jl:43-62).  Colmajor running ahead of rowmajor is only wrong when ROWMAJOR fails, and
-    // whether a write fails depends on nothing but the partition table (which ids are tombstones: src/pcsr.jl:114-162).  So when the
-    // rowmajor table holds tombstones the first write it will refuse is found up front by replaying the table — not the slots — on the
-    // host (TableReplay), and colmajor is not run beyond it.  The device stays the judge: the error code comes from the device, and
-    // when the device accepts what the replay predicted to fail the loop simply goes on behind it.
-    const bool par_seq = par && n >= 128;
-    int64_t pos = 0;
-    while (pos < n) {
-        const int64_t rem = n - pos;
-        int64_t f = n;                                                  // first write the rowmajor table refuses (n: none)
-        const Ctl& rc = *h->row.h_ctl;
-        if (rem > 1 && rc.nb_partitions != rc.table_len) {
-            TableReplay tr;
-            tr.load(h->row);
-            for (int64_t k = pos; k < n; ++k) if (tr.touch(I[k]) != 0) { f = k; break; }
-        }
-        const int64_t end = std::min(n, f + 1);
-        std::vector<Op> pc(oc.begin() + pos, oc.begin() + end), pr(orw.begin() + pos, orw.begin() + end);
-        int32_t err = 0;
-        const int64_t done = (par_seq ? run_ops_parallel(h->col, pc, &err, true) : run_ops(h->col, pc, &err)) + pos;
-        if (err) {
-            // colmajor refused write `done` (<= f): rowmajor gets the writes in front of it — none of which its table refuses
-            pr.resize((size_t)(done - pos));
-            int32_t e2 = 0;
-            const int64_t d2 = (par_seq ? run_ops_parallel(h->row, pr, &e2, true) : run_ops(h->row, pr, &e2)) + pos;
-            // Which write fails FIRST in the reference's order (colmajor then rowmajor of write 0, of write 1, ...): the rowmajor half of an
-            // earlier write d2 < done comes before the colmajor half of write `done`.  (Rounds 1-4 reported the colmajor error regardless:
-            // tools/fuzz.py run_tombstones seed 503707, EBOUNDS where the reference throws the AssertionError of src/pcsr.jl:132 three writes earlier.)
-            const int64_t fail_at = e2 ? d2 : done;
-            // the failing write had already updated size(m) in the reference (src/matrix.jl:44-47)
-            grow_size(0, std::min(fail_at + 1, n));
-            if (e2) fail(e2, err_text(e2));
-            fail(err, err_text(err));
-        }
-        int32_t e2 = 0;
-        const int64_t d2 = (par_seq ? run_ops_parallel(h->row, pr, &e2, true) : run_ops(h->row, pr, &e2)) + pos;
-        if (e2) {
-            grow_size(0, std::min(d2 + 1, n));
-            fail(e2, err_text(e2));
-        }
-        grow_size(pos, end);
-        pos = end;
-    }
 }
 
 void vec_apply(dsa_vec_t* h, const int64_t* keys, const double* vals, int64_t n) {
@@ -651,31 +203,11 @@ dsa_vec* vec_from_packed_dev(Pma& S, int64_t n, int64_t len) {
     return v;
 }
 
-void mat_prefetch_spmv_meta(dsa_mat* h) {
-    if (!h->has_major) return;
-    prefetch_spmv_meta(h->row);
-    prefetch_spmv_meta(h->col);
-}
-
-// every C-ABI entry that can change a value or a slot of the matrix: the SpMV plans of both orientations are stale from here on
-void mat_content_changed(dsa_mat_t* h) {
-    for (Pma* P : {&h->col, &h->row}) { ++P->content_epoch; spmv_plan_drop(*P); }
-}
-
 }  // namespace
 
 // what sparsex_host.hip calls as well (declared in host.h)
 namespace dsa {
 namespace host {
-
-void mat_flush(dsa_mat_t* h) {
-    if (h->has_major) bind_device(h->col);
-    if (h->pi.empty()) return;
-    std::vector<int64_t> i, j; std::vector<double> v;
-    i.swap(h->pi); j.swap(h->pj); v.swap(h->pv);       // the queue is empty even if the apply fails
-    mat_apply_sets(h, i.data(), j.data(), v.data(), (int64_t)i.size());
-    mat_prefetch_spmv_meta(h);
-}
 
 void ensure_xy(dsa_mat* h, int64_t nx, int64_t ny) {
     if (nx > h->x_cap) { if (h->d_x) hipFree(h->d_x); h->x_cap = std::max<int64_t>(nx, 1024); HIPCHK(hipMalloc(&h->d_x, (size_t)h->x_cap * sizeof(double))); }
@@ -713,14 +245,6 @@ void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, in
     launch_check(e, "spmv launch: ");
 }
 
-// both builds of a fresh handle from triples in HBM with known key ranges (ingest_host.hip), then the SpMV meta prefetch every
-// constructor ends with
-void mat_build_from_dev(dsa_mat* h, const int64_t* dI, const int64_t* dJ, const double* dV, int64_t nnz, KeyRange rows, KeyRange cols) {
-    auto fit32 = [](const KeyRange& r) { return !g_force_wide && (!r.known() || (key_fits32(r.lo) && key_fits32(r.hi))); };
-    mat_build_major_dev(h, dI, dJ, dV, nnz, !fit32(rows), !fit32(cols), rows, cols);
-    try { mat_prefetch_spmv_meta(h); } catch (...) { pma_destroy(h->col); pma_destroy(h->row); h->has_major = false; throw; }
-}
-
 }  // namespace host
 }  // namespace dsa
 
@@ -747,14 +271,12 @@ int32_t slice_impl(dsa_mat_t* h, int32_t o, int64_t key, dsa_vec_t** out) {
     mat_flush(h);
     if (h->fillmode) fail(DSA_EMODE, "slices are not available in fill mode");
     Pma& S = orient(h, o);
-    static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-    const auto ts0 = std::chrono::steady_clock::now();
+    const auto ts0 = Clock::now();
     const DevView dv = view_dev(S, key);
-    const auto ts1 = std::chrono::steady_clock::now();
+    const auto ts1 = Clock::now();
     if (dv.cnt <= 0) { _check_status(dsa_vec_create(nullptr, nullptr, 0, DSA_COMBINE_ADD, 0, out)); return DSA_OK; }      // PackedMemoryArray(L, T)  src/pcsr.jl:288
     *out = vec_from_packed_dev(S, dv.cnt, std::max<int64_t>(dv.last_key, 0));          // _guess_length(pma)  src/vector.jl:7-8
-    if (dbg_time) fprintf(stderr, "[slice] %lld cells: view %.1f us, new vector %.1f us\n", (long long)dv.cnt,
-                          std::chrono::duration<double, std::micro>(ts1 - ts0).count(), std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ts1).count());
+    if (dbg_time()) fprintf(stderr, "[slice] %lld cells: view %.1f us, new vector %.1f us\n", (long long)dv.cnt, elapsed_us(ts0, ts1), elapsed_us(ts1));
     API_CATCH
 }
 // @view m[:, col] / @view m[row, :] with the cells delivered into HBM: d_keys / d_vals are DEVICE arrays of `cap` entries; the copy is
@@ -1091,7 +613,7 @@ int32_t dsa_mat_create_from_coo(const int64_t* I, const int64_t* J, const double
     if (nnz > 0xffffffffll) fail(DSA_EARG, "more than 2^32-1 triples in one call");
     auto* h = new dsa_mat();
     KeyRange rows, cols;
-    try { mat_build_major(h, I, J, V, nnz, &rows, &cols); mat_prefetch_spmv_meta(h); } catch (...) { pma_destroy(h->col); pma_destroy(h->row); delete h; throw; }
+    try { mat_build_major(h, I, J, V, nnz, &rows, &cols); mat_prefetch_spmv_meta(h); } catch (...) { mat_discard(h); throw; }
     if (m < 0) m = rows.known() ? std::max<int64_t>(0, rows.hi) : 0;        // _guess_length  src/vector.jl:6
     if (n < 0) n = cols.known() ? std::max<int64_t>(0, cols.hi) : 0;
     h->m = m; h->n = n;
@@ -1155,7 +677,7 @@ int32_t dsa_mat_create_empty(int32_t fill_mode, dsa_mat_t** out) {
         HIPCHK(hipSetDevice(g_device));     // fail loudly without a device even though nothing is allocated yet
         h->fillmode = true;
     } else {
-        try { mat_build_major(h, nullptr, nullptr, nullptr, 0); } catch (...) { pma_destroy(h->col); pma_destroy(h->row); delete h; throw; }
+        try { mat_build_major(h, nullptr, nullptr, nullptr, 0); } catch (...) { mat_discard(h); throw; }
     }
     *out = h;
     API_CATCH
@@ -1249,40 +771,20 @@ int32_t dsa_mat_closefillmode(dsa_mat_t* h) {     // closefillmode!  src/matrix.
     mat_flush(h);
     if (!h->fillmode) fail(DSA_EMODE, "Cannot close fill mode because matrix is not in fill mode.");
     mat_content_changed(h);
-    // get_rowids_colids_vals (src/buffer.jl:33-50) is a no-op here: the triples already sit in HBM; only the last partial
-    // chunk is still in pinned memory
-    FillBuffer& b = h->buf;
-    int64_t nnz = 0;
-    bool wr = false, wc = false;
-    static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-    const auto tc0 = std::chrono::steady_clock::now();
-    // value ranges of everything appended (K-build's composite, the storage width of the keys): every uploaded piece was folded into
-    // five running words on the device (k_minmax_acc) — they come back with the wait for the last piece; the appends themselves never
-    // look at a key twice
-    KeyRange rows, cols;
-    if (b.stream) {
-        fill_upload_chunk(b);
-        HIPCHK(hipMemcpyAsync(b.h_acc, b.d_acc, 5 * sizeof(long long), hipMemcpyDeviceToHost, b.stream));
-        HIPCHK(hipStreamSynchronize(b.stream));
-        nnz = b.dlen;
-        if (nnz > 0) {
-            rows.lo = b.h_acc[0]; rows.hi = b.h_acc[1]; cols.lo = b.h_acc[2]; cols.hi = b.h_acc[3];
-            wr = g_force_wide || !(key_fits32(rows.lo) && key_fits32(rows.hi));
-            wc = g_force_wide || !(key_fits32(cols.lo) && key_fits32(cols.hi));
-        }
-    }
+    const auto tc0 = Clock::now();
+    const FillDrain d = fill_drain(h->buf);
+    // (the nnz > 0 guard stays here: needs_wide says wide for an UNKNOWN range under DSA_KEYS_WIDE=1, an empty buffer always closed narrow)
+    const bool wr = d.nnz > 0 && needs_wide(d.rows), wc = d.nnz > 0 && needs_wide(d.cols);
     // a failed build (out of memory, a HIP error) leaves the matrix what it was: in fill mode, with all of its triples — the
     // builder only reads them — so the caller may free memory and close again, or keep appending
-    const auto tc1 = std::chrono::steady_clock::now();
-    mat_build_major_dev(h, b.dI, b.dJ, b.dV, nnz, wr, wc, rows, cols);
-    const auto tc2 = std::chrono::steady_clock::now();
+    const auto tc1 = Clock::now();
+    mat_build_major_dev(h, h->buf.dI, h->buf.dJ, h->buf.dV, d.nnz, wr, wc, d.rows, d.cols);
+    const auto tc2 = Clock::now();
     h->fillmode = false;
     fill_release(h->buf);
     mat_prefetch_spmv_meta(h);
-    if (dbg_time) {
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b2) { return std::chrono::duration<double, std::milli>(b2 - a).count(); };
-        fprintf(stderr, "[closefillmode] last chunk %.2f ms  build %.2f ms  release + prefetch %.2f ms\n", ms(tc0, tc1), ms(tc1, tc2), ms(tc2, std::chrono::steady_clock::now()));
-    }
+    if (dbg_time())
+        fprintf(stderr, "[closefillmode] last chunk %.2f ms  build %.2f ms  release + prefetch %.2f ms\n", elapsed_ms(tc0, tc1), elapsed_ms(tc1, tc2), elapsed_ms(tc2));
     API_CATCH
 }
 
@@ -1291,39 +793,7 @@ int32_t dsa_mat_deletecolumn(dsa_mat_t* h, int64_t col) {      // src/matrix.jl:
     mat_flush(h);
     if (h->fillmode) fail(DSA_EMODE, "Cannot delete a column in fill mode");
     mat_content_changed(h);
-    static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-    const auto td0 = std::chrono::steady_clock::now();
-    std::vector<int64_t> rows; std::vector<double> vals;
-    col_view_of(h->col, col, rows, vals);
-    const auto td1 = std::chrono::steady_clock::now();
-    std::vector<Op> ops;
-    for (int64_t r : rows) ops.push_back(make_op(OP_MPCSC_SET, col, r, 0.0));     // rowmajor[col, row] = 0
-    std::vector<Op> del{make_op(OP_MPCSC_DELETECOLUMN, 0, col, 0.0)};
-    struct Report { bool on; std::chrono::steady_clock::time_point a, b; size_t n; ~Report() { if (on) fprintf(stderr, "[deletecolumn] view %.1f us, %zu twin deletes + deletepartition %.1f us\n",
-        std::chrono::duration<double, std::micro>(b - a).count(), n, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - b).count()); } } report{dbg_time, td0, td1, rows.size()};
-    // the element deletes of the twin cannot fail and touch the other structure: the deletepartition! of the own orientation is launched
-    // on its sequencer, the twin's deletes — different partitions, mostly disjoint footprints — go through the local rounds meanwhile
-    // (one wave per op instead of one op after the other: 105 -> 60 us for a column of 16)
-    if (h->col.stream != h->row.stream && !ops.empty()) {
-        SeqRun rc;
-        seq_start(rc, h->col, del);
-        int32_t er = 0;
-        try { run_ops_parallel(h->row, ops, &er); } catch (...) { while (seq_step(rc)) {} throw; }
-        while (seq_step(rc)) {}
-        if (er) fail(er, err_text(er));
-        if (rc.err) fail(rc.err, err_text(rc.err));
-    } else if (h->col.stream != h->row.stream) {
-        SeqRun rr, rc;
-        run_ops_pair(h->row, ops, h->col, del, rr, rc);
-        if (rr.err) fail(rr.err, err_text(rr.err));
-        if (rc.err) fail(rc.err, err_text(rc.err));
-    } else {
-        int32_t err = 0;
-        run_ops(h->row, ops, &err);
-        if (err) fail(err, err_text(err));
-        run_ops(h->col, del, &err);
-        if (err) fail(err, err_text(err));
-    }
+    mat_delete_partition(h, DSA_COLMAJOR, col);
     API_CATCH
 }
 int32_t dsa_mat_deleterow(dsa_mat_t* h, int64_t row) {         // src/matrix.jl:104-111
@@ -1331,31 +801,7 @@ int32_t dsa_mat_deleterow(dsa_mat_t* h, int64_t row) {         // src/matrix.jl:
     mat_flush(h);
     if (h->fillmode) fail(DSA_EMODE, "Cannot delete a row in fill mode");
     mat_content_changed(h);
-    std::vector<int64_t> cols; std::vector<double> vals;
-    col_view_of(h->row, row, cols, vals);
-    std::vector<Op> ops;
-    for (int64_t c : cols) ops.push_back(make_op(OP_MPCSC_SET, row, c, 0.0));     // colmajor[row, col] = 0
-    std::vector<Op> del{make_op(OP_MPCSC_DELETECOLUMN, 0, row, 0.0)};
-    if (h->col.stream != h->row.stream && !ops.empty()) {       // (as in deletecolumn!)
-        SeqRun rr;
-        seq_start(rr, h->row, del);
-        int32_t ec = 0;
-        try { run_ops_parallel(h->col, ops, &ec); } catch (...) { while (seq_step(rr)) {} throw; }
-        while (seq_step(rr)) {}
-        if (ec) fail(ec, err_text(ec));
-        if (rr.err) fail(rr.err, err_text(rr.err));
-    } else if (h->col.stream != h->row.stream) {
-        SeqRun rc, rr;
-        run_ops_pair(h->col, ops, h->row, del, rc, rr);
-        if (rc.err) fail(rc.err, err_text(rc.err));
-        if (rr.err) fail(rr.err, err_text(rr.err));
-    } else {
-        int32_t err = 0;
-        run_ops(h->col, ops, &err);
-        if (err) fail(err, err_text(err));
-        run_ops(h->row, del, &err);
-        if (err) fail(err, err_text(err));
-    }
+    mat_delete_partition(h, DSA_ROWMAJOR, row);
     API_CATCH
 }
 

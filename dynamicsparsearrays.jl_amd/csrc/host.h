@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
-// unit boundary, and the handle structs.  The host units are dsa_host.hip, pma_host.hip, writes_host.hip, build_host.hip,
-// spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
+// unit boundary, and the handle structs.  The host units are dsa_host.hip, fill_host.hip, matwrite_host.hip, pma_host.hip,
+// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -9,6 +9,7 @@
 #include "../../include/dsa.h"
 #include "dsa_dev.h"
 
+#include <chrono>
 #include <cstdint>
 #include <exception>
 #include <string>
@@ -57,6 +58,13 @@ struct ApiRange {
 extern int g_device;                      // the device new handles are created on (dsa_set_device)
 extern const int g_wait_policy_default;   // default of Pma::wait_policy (DSA_WAIT_POLICY=1: yield-friendly waits for every new handle)
 extern const bool g_force_wide;           // dev knob: DSA_KEYS_WIDE=1 keeps every structure in 64-bit keys
+
+// the timing lines on stderr (development switch DSA_DBG_TIME) and the clock they are taken with: elapsed time from a to b (default:
+// to now) in milliseconds / microseconds
+inline bool dbg_time() { static const bool on = dev_env("DSA_DBG_TIME") != nullptr; return on; }
+using Clock = std::chrono::steady_clock;
+inline double elapsed_ms(Clock::time_point a, Clock::time_point b = Clock::now()) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+inline double elapsed_us(Clock::time_point a, Clock::time_point b = Clock::now()) { return std::chrono::duration<double, std::micro>(b - a).count(); }
 
 // What an export keeps on its orientation (export_host.hip): a pooled device scratch, grown on demand, and the pinned words its
 // kernels hand their results to, allocated at the first export.  Sequence numbers start at 1.
@@ -175,6 +183,10 @@ struct Pma {
     }
 };
 
+inline void bind_device(const Pma& P) { HIPCHK(hipSetDevice(P.device)); }
+inline void check_key(int64_t k) { if (k == 0) fail(DSA_EKEY, "0 is the reserved semaphore key (src/pcsr.jl:23)"); }
+inline Op make_op(int32_t kind, int64_t a, int64_t b, double v) { Op o; o.a = a; o.b = b; o.v = v; o.kind = kind; o.pad = 0; return o; }
+
 // A batch of ops as the host hands it to a structure: a ready-made Op array (small batches, mixed kinds), or the caller's COLUMNS —
 // op k = (a[k], b ? b[k] : 0, v[k]) of one kind — which go up as they are (16 / 24 bytes per op instead of 32, no Op vector built on
 // the host) and are expanded into the op array by a kernel behind the upload (sequencer.hip: k_make_ops).
@@ -226,6 +238,8 @@ void pma_destroy(Pma& P);
 void pma_init_common(Pma& P, bool sems, bool cols);
 void upload_keys(Pma& P, void* dst, const int64_t* src, int64_t n);
 bool keys_fit32(const int64_t* k, int64_t n);
+// the storage width a structure needs for keys of this range: 64 bits when an end does not fit 32 (an unknown range fits) or under DSA_KEYS_WIDE=1
+inline bool needs_wide(const KeyRange& r) { return g_force_wide || (r.known() && !(key_fits32(r.lo) && key_fits32(r.hi))); }
 void widen_keys(Pma& P);
 void ensure_tables(Pma& P, int64_t need);
 void compute_bounds(Pma& P);
@@ -274,12 +288,25 @@ void spmv_plan_build(Pma& P, int64_t nx, int64_t ny, hipStream_t s);
 bool spmv_plan_product(Pma& P, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s);
 
 // ---- dsa_host.hip: what sparsex_host.hip needs of the handle layer
-void mat_flush(dsa_mat* h);
 void ensure_xy(dsa_mat* h, int64_t nx, int64_t ny);
 void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s,
               int pattern = 0);
-// both orientations of a fresh handle from 1-based int64 triples in HBM whose key ranges are known; on failure nothing is left of them
+
+// ---- matwrite_host.hip: the writes in terms of dsa_mat.  The builds of both orientations of a fresh handle from 1-based int64 triples
+// (a constructor hands a handle whose build, or the SpMV meta prefetch behind it, threw to mat_discard: structures and handle go)
+void mat_build_major_dev(dsa_mat* h, const int64_t* dI, const int64_t* dJ, const double* dV, int64_t nnz, bool wide_rows, bool wide_cols,
+                         KeyRange rows = KeyRange(), KeyRange cols = KeyRange());
+void mat_build_major(dsa_mat* h, const int64_t* I, const int64_t* J, const double* V, int64_t nnz, KeyRange* rows_out = nullptr,
+                     KeyRange* cols_out = nullptr);
 void mat_build_from_dev(dsa_mat* h, const int64_t* dI, const int64_t* dJ, const double* dV, int64_t nnz, KeyRange rows, KeyRange cols);
+void mat_discard(dsa_mat* h);
+// a batch of setindex! calls, the flush of the queued single writes, what every entry point that changes the matrix does in front of
+// its writes and behind them, and deletecolumn! (DSA_COLMAJOR) / deleterow!
+void mat_apply_sets(dsa_mat* h, const int64_t* I, const int64_t* J, const double* V, int64_t n);
+void mat_flush(dsa_mat* h);
+void mat_content_changed(dsa_mat* h);
+void mat_prefetch_spmv_meta(dsa_mat* h);
+void mat_delete_partition(dsa_mat* h, int32_t orientation, int64_t key);
 
 // ---- ingest_host.hip: a matrix from COO / CSR / CSC arrays in HBM (new handle; the entry points are in dsa_host.hip)
 dsa_mat* mat_from_coo_dev(const void* d_I, const void* d_J, const double* d_V, int64_t nnz, int32_t index_bits, int32_t index_base,
@@ -384,6 +411,14 @@ struct FillBuffer {
     int64_t length = 0;
     int device = 0;
 };
+
+// ---- fill_host.hip: the fill-mode buffer.  fill_row_test_and_set: was the row written before; fill_append: addelem! for n entries;
+// fill_drain: the last piece goes up and the accumulated words come back (the key ranges only with nnz > 0); fill_release: everything back
+bool fill_row_test_and_set(FillBuffer& b, int64_t row);
+void fill_append(FillBuffer& b, const int64_t* I, const int64_t* J, const double* V, int64_t n);
+struct FillDrain { int64_t nnz = 0; KeyRange rows, cols; };
+FillDrain fill_drain(FillBuffer& b);
+void fill_release(FillBuffer& b);
 
 }  // namespace host
 }  // namespace dsa

@@ -5,7 +5,6 @@
 #include "host.h"
 #include "ingest.h"
 
-#include <chrono>
 #include <climits>
 #include <cstring>
 
@@ -64,11 +63,9 @@ void check_index_args(int32_t index_bits, int32_t index_base, int64_t nnz) {
 dsa_mat* build_handle(const int64_t* dI, const int64_t* dJ, const double* dV, int64_t nnz, KeyRange rows, KeyRange cols) {
     auto* h = new dsa_mat();
     try { mat_build_from_dev(h, dI, dJ, dV, nnz, rows, cols); }
-    catch (...) { delete h; throw; }           // (mat_build_from_dev has synchronised and destroyed both structures)
+    catch (...) { mat_discard(h); throw; }
     return h;
 }
-
-double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 
 }  // namespace
 
@@ -77,8 +74,7 @@ dsa_mat* mat_from_coo_dev(const void* d_I, const void* d_J, const double* d_V, i
     check_index_args(index_bits, index_base, nnz);
     if (index_bits == 32 && (m > INT32_MAX || n > INT32_MAX)) fail(DSA_EARG, "a dimension does not fit 32-bit indices");
     if (nnz > 0 && (d_I == nullptr || d_J == nullptr || d_V == nullptr)) fail(DSA_EARG, "NULL array of a non-empty matrix");
-    static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     KeyRange rows, cols;
     const int64_t *dI = nullptr, *dJ = nullptr;
     Ingest in;
@@ -97,11 +93,11 @@ dsa_mat* mat_from_coo_dev(const void* d_I, const void* d_J, const double* d_V, i
     } else {
         HIPCHK(hipSetDevice(g_device));
     }
-    const double t_keys = ms_since(t0);
-    const auto t1 = std::chrono::steady_clock::now();
+    const double t_keys = elapsed_ms(t0);
+    const auto t1 = Clock::now();
     dsa_mat* h = build_handle(dI, dJ, d_V, nnz, rows, cols);
-    if (dbg_time) fprintf(stderr, "[ingest] coo nnz=%lld bits=%d base=%d: expand 0.00 ms  keys %.2f ms  build %.2f ms\n", (long long)nnz, index_bits, index_base,
-                          t_keys, ms_since(t1));
+    if (dbg_time()) fprintf(stderr, "[ingest] coo nnz=%lld bits=%d base=%d: expand 0.00 ms  keys %.2f ms  build %.2f ms\n", (long long)nnz, index_bits, index_base,
+                            t_keys, elapsed_ms(t1));
     h->m = m >= 0 ? m : (rows.known() ? std::max<int64_t>(0, rows.hi) : 0);        // _guess_length  src/vector.jl:6
     h->n = n >= 0 ? n : (cols.known() ? std::max<int64_t>(0, cols.hi) : 0);
     return h;
@@ -115,8 +111,7 @@ dsa_mat* mat_from_compressed_dev(int32_t orientation, int32_t index_bits, int32_
     if (index_bits == 32 && (outer > INT32_MAX || inner > INT32_MAX)) fail(DSA_EARG, "a dimension does not fit 32-bit indices");
     if (d_ptr == nullptr) fail(DSA_EARG, "a compressed form needs its ptr array");
     if (nnz > 0 && (d_idx == nullptr || d_vals == nullptr)) fail(DSA_EARG, "NULL array of a non-empty matrix");
-    static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = Clock::now();
     KeyRange ko, ki;
     Ingest in;
     in.open(2 * nnz);
@@ -124,19 +119,19 @@ dsa_mat* mat_from_compressed_dev(int32_t orientation, int32_t index_bits, int32_
     int64_t* k_inner = nnz > 0 ? in.d_keys + nnz : nullptr;
     LAUNCH("ingest expand", launch_in_expand(d_ptr, index_bits, index_base, outer, nnz, k_outer, in.d_acc, in.stream));
     double t_expand = 0.0;
-    if (dbg_time) { HIPCHK(hipStreamSynchronize(in.stream)); t_expand = ms_since(t0); }      // (the split of the timing line only)
+    if (dbg_time()) { HIPCHK(hipStreamSynchronize(in.stream)); t_expand = elapsed_ms(t0); }      // (the split of the timing line only)
     LAUNCH("ingest keys", launch_in_keys(nullptr, d_idx, index_bits, index_base, nnz, nullptr, k_inner, in.d_acc, in.stream));
     unsigned long long flags = 0;
     in.verdict(ko, ki, flags);
     if (flags & IN_BAD_PTR) fail(DSA_EARG, "malformed ptr: it must start at base, end at base + nnz and never decrease");
     if (nnz > 0 && (!ki.known() || ki.lo < 1 || ki.hi > inner)) fail(DSA_EBOUNDS, "an inner index lies outside base .. base + inner - 1");
     if (nnz == 0) { ko = KeyRange(); ki = KeyRange(); }
-    const double t_keys = ms_since(t0) - t_expand;
-    const auto t1 = std::chrono::steady_clock::now();
+    const double t_keys = elapsed_ms(t0) - t_expand;
+    const auto t1 = Clock::now();
     const bool csr = orientation == DSA_ROWMAJOR;
     dsa_mat* h = csr ? build_handle(k_outer, k_inner, d_vals, nnz, ko, ki) : build_handle(k_inner, k_outer, d_vals, nnz, ki, ko);
-    if (dbg_time) fprintf(stderr, "[ingest] %s nnz=%lld bits=%d base=%d: expand %.2f ms  keys %.2f ms  build %.2f ms\n", csr ? "csr" : "csc", (long long)nnz,
-                          index_bits, index_base, t_expand, t_keys, ms_since(t1));
+    if (dbg_time()) fprintf(stderr, "[ingest] %s nnz=%lld bits=%d base=%d: expand %.2f ms  keys %.2f ms  build %.2f ms\n", csr ? "csr" : "csc", (long long)nnz,
+                            index_bits, index_base, t_expand, t_keys, elapsed_ms(t1));
     h->m = csr ? outer : inner;
     h->n = csr ? inner : outer;
     return h;

@@ -18,7 +18,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <thread>
@@ -160,9 +159,8 @@ int32_t dsa_mat_spmv_sparse_begin(dsa_mat_t* h, int32_t transpose, const int64_t
     if (nx < 0) fail(DSA_EARG, "negative length");
     dsa_mat::Spx& x = h->spx;
     x.res_count = -1; x.dl_started = false;
-    static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-    const auto tq0 = std::chrono::steady_clock::now();
-    auto tq = [&](const char* what) { if (dbg_time) fprintf(stderr, "  [spmv_sparse_begin] %s at %.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tq0).count()); };
+    const auto tq0 = Clock::now();
+    auto tq = [&](const char* what) { if (dbg_time()) fprintf(stderr, "  [spmv_sparse_begin] %s at %.1f us\n", what, elapsed_us(tq0)); };
     const int64_t ny = transpose ? h->n : h->m;
     const int64_t ncols = transpose ? h->m : h->n;
     bool in_range = nx > 0 && xi[0] >= 1;
@@ -261,8 +259,7 @@ int32_t dsa_mat_spmv_sparse_fetch(dsa_mat_t* h, int64_t* yi, double* yv, int64_t
         const size_t off = x.dl_off[q];
         pc[q] = Piece{static_cast<char*>(x.stage) + off, (off < tot ? (char*)yi + off : (char*)yv + (off - tot)), x.dl_bytes[q]};
     }
-    static const bool dbg_time = dev_env("DSA_DBG_TIME") != nullptr;
-    const auto tf0 = std::chrono::steady_clock::now();
+    const auto tf0 = Clock::now();
     // every piece is copied by all workers (a quarter each) as soon as its event has fired; the workers are started ONCE per fetch
     // (a thread per piece and quarter cost more than the copies)
     const int nt = tot >= ((size_t)2 << 20) ? 4 : 1;
@@ -282,8 +279,7 @@ int32_t dsa_mat_spmv_sparse_fetch(dsa_mat_t* h, int64_t* yi, double* yv, int64_t
     work(0);
     for (int t = 1; t < nt; ++t) th[t - 1].join();
     if (herr.load()) { (void)hipGetLastError(); fail(DSA_EHIP, "download of the sparse-x result failed"); }
-    if (dbg_time) fprintf(stderr, "  [spmv_sparse_fetch] %lld pairs in %d pieces, %d threads: %.1f us\n", (long long)cnt, np, nt,
-                          std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tf0).count());
+    if (dbg_time()) fprintf(stderr, "  [spmv_sparse_fetch] %lld pairs in %d pieces, %d threads: %.1f us\n", (long long)cnt, np, nt, elapsed_us(tf0));
     API_CATCH
 }
 

@@ -5,7 +5,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 
@@ -117,8 +116,7 @@ static void wait_published(Pma& P) { wait_handover(P, P.h_pub, P.pub_seq, "devic
 static thread_local double g_seq_launch_ms = 0;
 static void seq_launch(SeqRun& r, bool upload = true) {
     Pma& P = *r.P;
-    struct T { std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-               ~T() { g_seq_launch_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } timer;
+    struct T { Clock::time_point t0 = Clock::now(); ~T() { g_seq_launch_ms += elapsed_ms(t0); } } timer;
     // pinned h_ctl: H2D, kernel and D2H are stream-ordered; the host does not touch h_ctl until the next synchronize
     if (upload) HIPCHK(hipMemcpyAsync(P.d_ctl, P.h_ctl, sizeof(Ctl), hipMemcpyHostToDevice, P.stream));
     ++P.layout_epoch;
@@ -146,18 +144,18 @@ void seq_start(SeqRun& r, Pma& P, const std::vector<Op>& ops) {
 namespace {
 static thread_local double g_seq_wait_ms = 0, g_seq_host_ms[8] = {0};
 struct SeqStepTimer {
-    std::chrono::steady_clock::time_point t0; int kind;
-    SeqStepTimer(int k) : t0(std::chrono::steady_clock::now()), kind(k) {}
-    ~SeqStepTimer() { g_seq_host_ms[kind & 7] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+    Clock::time_point t0; int kind;
+    SeqStepTimer(int k) : t0(Clock::now()), kind(k) {}
+    ~SeqStepTimer() { g_seq_host_ms[kind & 7] += elapsed_ms(t0); }
 };
 }  // namespace
 bool seq_step(SeqRun& r) {
     if (!r.active) return false;
     Pma& P = *r.P;
     {
-        const auto tw0 = std::chrono::steady_clock::now();
+        const auto tw0 = Clock::now();
         wait_published(P);
-        g_seq_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw0).count();
+        g_seq_wait_ms += elapsed_ms(tw0);
     }
     Ctl& c = *P.h_ctl;
     SeqStepTimer timer(c.status);
@@ -297,12 +295,11 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
     ensure_key_width(P, ops);
     ensure_ops(P, n);
     {
-        const auto tu0 = std::chrono::steady_clock::now();
+        const auto tu0 = Clock::now();
         upload_batch(P, ops);
         enqueue_op_breaks(P, n);
         static const bool dbg_up = dev_env("DSA_DBG_SPLIT") != nullptr;
-        if (dbg_up) fprintf(stderr, "  [run_ops_parallel] upload of %lld ops (%.1f MB, pageable): %.3f ms on the host\n", (long long)n, n * sizeof(Op) / 1e6,
-                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tu0).count());
+        if (dbg_up) fprintf(stderr, "  [run_ops_parallel] upload of %lld ops (%.1f MB, pageable): %.3f ms on the host\n", (long long)n, n * sizeof(Op) / 1e6, elapsed_ms(tu0));
     }
     if (!P.d_plans) {
 #ifdef DSA_FP_CHECK
@@ -343,8 +340,6 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
     static const bool dbg_split = dev_env("DSA_DBG_SPLIT") != nullptr;
     double t_burst = 0, t_seq = 0, t_local = 0; int64_t n_burst = 0, n_seq = 0, n_yield = 0, n_local = 0, r_local = 0, o_local = 0;
     int64_t dbg_detour[32] = {0};
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     // A batch that starts like an append run — ascending keys (vector) / ascending (column, row) pairs (MappedPackedCSC) — goes to the
     // sequencer first, which detects the run (or, when the keys are not above the last cell after all, applies a few ops and hands
     // back to the rounds): a burst of rounds on ascending appends plans and applies one op per round (0.37 ms for nothing at 100 k ops)
@@ -362,7 +357,7 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
         }
     }
     while (i < n || np > 0) {
-        const auto tb0 = now();
+        const auto tb0 = Clock::now();
         bool to_sequencer = seq_first;
         if (!seq_first) {
         // ---- a burst of rounds driven by the device-resident cursor; one host synchronisation per burst
@@ -396,8 +391,8 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
                                                      burst_rounds, burst_rounds == ROUNDS_PER_SYNC ? &P.burst : &P.burst_short, pub, P.stream));
         }
         wait_published(P);
-        t_burst += ms(tb0, now()); ++n_burst;
-        if (use_local) { t_local += ms(tb0, now()); ++n_local; r_local += rs.rounds; o_local += rs.par_ops; }
+        t_burst += elapsed_ms(tb0); ++n_burst;
+        if (use_local) { t_local += elapsed_ms(tb0); ++n_local; r_local += rs.rounds; o_local += rs.par_ops; }
         // the prefix of the last round of the burst has been applied but is folded into the cursor only by the next round's resolve step
         if (rs.pad >= 10) fail(DSA_EASSERT, "DSA_FP_CHECK: a round of the batch-parallel writes is not equivalent to the sequential order (code " + std::to_string(rs.pad) + ", details on stdout)");
         if (rs.pad == 9) fail(DSA_EASSERT, "batch-parallel writes: a deferred op left the zone it was sealed in (internal invariant of the run-ahead rounds)");
@@ -452,7 +447,7 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
         if (np > 0) { drain = true; after_drain = 2; continue; }
         seq_first = false;
         // ---- short prefix at op i: sequential sequencer for ops [i, i + seq_chunk)
-        const auto ts0 = now();
+        const auto ts0 = Clock::now();
         int64_t no_run_at = -1;
         for (;;) {
             SeqRun r;
@@ -477,7 +472,7 @@ int64_t run_ops_parallel(Pma& P, const OpBatch& ops, int32_t* err, bool can_fail
             if (i < n && P.h_ctl->no_run_at == i) { no_run_at = i; seq_chunk = std::max<int64_t>(seq_chunk, 8); continue; }
             break;
         }
-        t_seq += ms(ts0, now());
+        t_seq += elapsed_ms(ts0);
         seq_chunk = std::min<int64_t>(seq_chunk * 2, 8192);
         G = 64;
     }

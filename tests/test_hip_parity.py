@@ -11,7 +11,8 @@ import pytest
 
 import ka
 from scenario import run_scenario
-from util import SplitMix64, check_key_order, check_semaphores, layouts_equal, splitmix_array, unit12_array
+from util import (SplitMix64, assert_mat_equal, check_key_order, check_semaphores, layouts_equal, orientation_equal, splitmix_array,
+                  unit12_array)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -41,18 +42,6 @@ def assert_vec_equal(a, b):
         assert ia[k] == ib[k], (k, ia, ib)
     assert len(a) == len(b)
     assert layouts_equal(a.export_layout(), b.export_layout())
-
-
-def assert_mat_equal(a, b):
-    assert a.size() == b.size()
-    for o in (0, 1):
-        La, Lb = a.export_layout(o), b.export_layout(o)
-        for k in ("capacity", "segment_capacity", "nb_segments", "nb_elements", "height", "nb_partitions", "table_len"):
-            assert La["info"][k] == Lb["info"][k], (o, k, La["info"], Lb["info"])
-        assert layouts_equal((La["keys"], La["vals"], La["occ"]), (Lb["keys"], Lb["vals"], Lb["occ"])), o
-        assert np.array_equal(La["semaphores"], Lb["semaphores"]), o
-        assert np.array_equal(La["col_live"], Lb["col_live"]), o
-        assert np.array_equal(La["col_keys"], Lb["col_keys"]), o
 
 
 # ---------------------------------------------------------------- golden vectors of the reference
@@ -402,7 +391,7 @@ def test_kbuild_buffers_sized_for_the_upper_bound_then_duplicates_fold(dsa, hip,
 def test_column_generation_with_deletions_matches_oracle(dsa, hip, oracle):
     """Column generation with deletions (Coluna's pattern: new columns get new, larger ids while old ones are deleted): batches of new
     columns streamed into a matrix whose colmajor tables hold tombstones.  A batch whose column keys never decrease and start at or
-    behind the last LIVE table entry cannot fail, so both orientations are updated side by side (mat_apply_sets: cannot_fail); deleting
+    behind the last LIVE table entry cannot fail, so both orientations are updated side by side (matwrite_host.hip: mat_apply_sets, cannot_fail); deleting
     the last column, writing to an older column, or a deleted row make the batch take the reference's statement order instead — same
     state and same error codes as the oracle either way."""
     m_rows, per, step = 400, 6, 60              # 360 element writes per batch (>= 128: the batch-parallel branch)
@@ -683,18 +672,6 @@ def test_error_codes_match_reference_sites(dsa, hip):
         p.deletepartition(7)                    # src/pcsr.jl:190
 
 
-def _orientation_equal(a, b, o):
-    try:
-        La, Lb = a.export_layout(o), b.export_layout(o)
-    except Exception:
-        return False
-    if any(La["info"][k] != Lb["info"][k] for k in ("capacity", "segment_capacity", "nb_segments", "nb_elements", "height", "nb_partitions", "table_len")):
-        return False
-    live = La["col_live"].astype(bool)
-    return bool(layouts_equal((La["keys"], La["vals"], La["occ"]), (Lb["keys"], Lb["vals"], Lb["occ"])) and np.array_equal(La["semaphores"], Lb["semaphores"])
-                and np.array_equal(La["col_live"], Lb["col_live"]) and np.array_equal(La["col_keys"][live], Lb["col_keys"][live]))
-
-
 @pytest.mark.parametrize("pad", [0, 300])
 def test_state_after_a_failed_batch_is_the_references(dsa, hip, oracle, pad):
     """src/matrix.jl:43-62 writes colmajor, then rowmajor: when write k of a batch throws, both orientations hold writes [0, k) and colmajor
@@ -735,7 +712,7 @@ def test_state_after_a_failed_batch_is_the_references(dsa, hip, oracle, pad):
             assert_mat_equal(*ms)
         else:
             assert codes[0] is not None
-            assert _orientation_equal(ms[0], ms[1], 1 - failing), ("the orientation that did not refuse the write differs", failing)
+            assert orientation_equal(ms[0], ms[1], 1 - failing), ("the orientation that did not refuse the write differs", failing)
         return codes[0]
 
     # rowmajor asserts (new row 31 in front of live row 33 while row 105 is a tombstone further up); writes behind it must not reach colmajor

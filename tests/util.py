@@ -94,3 +94,32 @@ def layouts_equal(a, b):
         return False
     m = oa.astype(bool)
     return bool(np.array_equal(ka[m], kb[m]) and np.array_equal(va[m].view(np.uint64), vb[m].view(np.uint64)))
+
+
+MAT_INFO_KEYS = ("capacity", "segment_capacity", "nb_segments", "nb_elements", "height", "nb_partitions", "table_len")
+
+
+def assert_mat_equal(a, b):
+    """size(m), geometry, slots, semaphores and partition tables of both orientations, slot for slot."""
+    assert a.size() == b.size()
+    for o in (0, 1):
+        La, Lb = a.export_layout(o), b.export_layout(o)
+        for k in MAT_INFO_KEYS:
+            assert La["info"][k] == Lb["info"][k], (o, k, La["info"], Lb["info"])
+        assert layouts_equal((La["keys"], La["vals"], La["occ"]), (Lb["keys"], Lb["vals"], Lb["occ"])), o
+        assert np.array_equal(La["semaphores"], Lb["semaphores"]), o
+        assert np.array_equal(La["col_live"], Lb["col_live"]), o
+        assert np.array_equal(La["col_keys"], Lb["col_keys"]), o
+
+
+def orientation_equal(a, b, o):
+    """one orientation after a FAILED batch: as assert_mat_equal, the keys of tombstoned table entries aside"""
+    try:
+        La, Lb = a.export_layout(o), b.export_layout(o)
+    except Exception:
+        return False
+    if any(La["info"][k] != Lb["info"][k] for k in MAT_INFO_KEYS):
+        return False
+    live = La["col_live"].astype(bool)
+    return bool(layouts_equal((La["keys"], La["vals"], La["occ"]), (Lb["keys"], Lb["vals"], Lb["occ"])) and np.array_equal(La["semaphores"], Lb["semaphores"])
+                and np.array_equal(La["col_live"], Lb["col_live"]) and np.array_equal(La["col_keys"][live], Lb["col_keys"][live]))

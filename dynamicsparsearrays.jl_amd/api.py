@@ -236,6 +236,12 @@ class PackedCSC(_Handle):
                     o.ctypes.data_as(P_U8), cap, s.ctypes.data_as(P_I64), tl)
         return k, v, o, s[:inf["table_len"]]
 
+    def check(self):
+        """device-side invariant checker (HIP library only): report[2..6] must be 0."""
+        r = np.zeros(8, dtype=np.int64)
+        self.b.call("pcsc_check", self.h, r.ctypes.data_as(P_I64))
+        return r
+
 
 def packedcsc(row_keys, values, combine="+", binding: Binding | None = None) -> PackedCSC:
     """PackedCSC(row_keys::Vector{Vector}, values::Vector{Vector}, combine)  src/pcsr.jl:26-63."""

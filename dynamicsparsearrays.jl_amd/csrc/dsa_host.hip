@@ -600,6 +600,7 @@ int32_t dsa_pcsc_export_layout(dsa_pcsc_t* h, int64_t* keys, double* vals, uint8
     export_tables(h->P, semaphores, nullptr, nullptr, table_cap);
     API_CATCH
 }
+int32_t dsa_pcsc_check(dsa_pcsc_t* h, int64_t* report) { API_TRY bind_device(h->P); pma_check(h->P, report); API_CATCH }
 
 }  // extern "C"
 

@@ -511,6 +511,7 @@ int32_t dsa_shard_spmv_allreduce_dev(dsa_mat_t* shard, dsa_comm_t* comm, const d
  * beyond the capacity, [6] 1 if report[0] != nb_elements or report[1] != live partitions.  A healthy structure has [2..6] == 0. */
 int32_t dsa_vec_check(dsa_vec_t* h, int64_t report[8]);
 int32_t dsa_mat_check(dsa_mat_t* h, int32_t orientation, int64_t report[8]);
+int32_t dsa_pcsc_check(dsa_pcsc_t* h, int64_t report[8]);
 /* stream control for *_dev entry points (hipStream_t passed as void*; NULL = legacy default stream) */
 int32_t dsa_mat_set_stream(dsa_mat_t* h, void* hip_stream);
 int32_t dsa_vec_set_stream(dsa_vec_t* h, void* hip_stream);

@@ -12,7 +12,7 @@ from . import binding  # noqa: F401
 from .api import (  # noqa: F401
     COLMAJOR, ROWMAJOR, DynamicSparseMatrix, DynamicSparseVector, PackedCSC, Transposed,
     addrow, closefillmode, deletecolumn, deletecolumns, deletepartition, deleterow, deleterows, droptol, dropzeros, dynamicsparse,
-    dynamicsparse_compressed_dev, dynamicsparse_dev, from_torch,
+    dynamicsparse_compressed_dev, dynamicsparse_dev, from_torch, hcat, vcat, blockdiag,
     dynamicsparsevec, import_packedcsc_layout, import_vector_layout, nbpartitions, nnz, packedcsc, packedcsc_empty, pool_idle_bytes,
     pool_trim, shrink_size, dev_switches,
 )

@@ -680,6 +680,48 @@ class DynamicSparseMatrix(_Handle):
                                           index_bits=bits)))
         return self._torch_tensor(orientation, arrays, nouter, ninner)
 
+    # ---- combine (include/dsa.h: dsa_mat_combine; HIP library only) ---------------------------------------------------------------
+    def combine(self, other=None, alpha=1.0, beta=1.0, row_off=0, col_off=0, m=None, n=None):
+        """alpha * self + beta * other as a NEW matrix, built on the device; `other`'s keys are shifted by (row_off, col_off).  It is
+        the matrix dynamicsparse(I, J, V, m, n) builds from the stored cells of self in findnz order, scaled by alpha, followed by
+        those of other, shifted and scaled by beta: a cell present in both is their sum (a stored zero when it cancels: dropzeros()).
+        other=None: a scaled copy.  m, n: size of the result (default: the smallest that holds both operands).  A non-zero offset
+        needs both operands inside their size() in that dimension (DsaBoundsError).  The operands are only read."""
+        self._require("mat_combine", "combining matrices needs the HIP product library")
+        if other is not None:
+            if not isinstance(other, DynamicSparseMatrix):
+                raise B.DsaArgumentError(B.EARG, "the second operand must be a DynamicSparseMatrix")
+            if other.b is not self.b:
+                raise B.DsaArgumentError(B.EARG, "matrices of two different libraries")
+        h = VP()
+        self.b.call("mat_combine", self.h, float(alpha), None if other is None else other.h, float(beta), int(row_off), int(col_off),
+                    -1 if m is None else int(m), -1 if n is None else int(n), C.byref(h))
+        return DynamicSparseMatrix(self.b, h)
+
+    def copy(self):
+        """an independent matrix with the same stored cells and size (a fresh build: the layout is that of dynamicsparse(findnz(A)...))"""
+        return self.combine()
+
+    def __add__(self, other):
+        if not isinstance(other, DynamicSparseMatrix):
+            return NotImplemented
+        return self.combine(other)
+
+    def __sub__(self, other):
+        if not isinstance(other, DynamicSparseMatrix):
+            return NotImplemented
+        return self.combine(other, beta=-1.0)
+
+    def __neg__(self):
+        return self.combine(alpha=-1.0)
+
+    def __mul__(self, alpha):
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)):
+            return NotImplemented
+        return self.combine(alpha=float(alpha))
+
+    __rmul__ = __mul__
+
     def check(self, orientation):
         """device-side invariant checker (HIP library only): report[2..6] must be 0."""
         r = np.zeros(8, dtype=np.int64)
@@ -1222,6 +1264,41 @@ def from_torch(t, binding: Binding | None = None) -> DynamicSparseMatrix:
                                             index_base=0, binding=b)
     return dynamicsparse_compressed_dev(COLMAJOR, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), n, m, nnz, index_bits=bits,
                                         index_base=0, binding=b)
+
+
+# ---- concatenation (dsa_mat_combine with an offset; HIP library only) ---------------------------------------------------------------
+def _arg_error(msg):
+    return B.DsaArgumentError(B.EARG, msg)
+
+
+def _concat_operands(lhs, rhs):
+    for x in (lhs, rhs):
+        if not isinstance(x, DynamicSparseMatrix):
+            raise _arg_error("both operands must be DynamicSparseMatrix")
+    lhs._require("mat_combine", "combining matrices needs the HIP product library")
+    return lhs.size(), rhs.size()
+
+
+def hcat(A, B):
+    """[A B]: the columns of B appended behind those of A (col_off = A.n); both need the same number of rows"""
+    (ma, na), (mb, _) = _concat_operands(A, B)
+    if ma != mb:
+        raise _arg_error(f"hcat: the operands have {ma} and {mb} rows")
+    return A.combine(B, col_off=na)
+
+
+def vcat(A, B):
+    """[A; B]: the rows of B appended below those of A (row_off = A.m); both need the same number of columns"""
+    (ma, na), (_, nb) = _concat_operands(A, B)
+    if na != nb:
+        raise _arg_error(f"vcat: the operands have {na} and {nb} columns")
+    return A.combine(B, row_off=ma)
+
+
+def blockdiag(A, B):
+    """[A 0; 0 B]"""
+    (ma, na), _ = _concat_operands(A, B)
+    return A.combine(B, row_off=ma, col_off=na)
 
 
 # free-function spellings of the exported names (src/DynamicSparseArrays.jl:5-16)

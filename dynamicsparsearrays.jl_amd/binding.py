@@ -180,6 +180,7 @@ _PRODUCT_ONLY_SIGS = {
     "mat_submatrix_compressed": [VP, I32, I32, P_I64, I64, P_I64, I64, P_I64, P_I64, P_F64, I64, P_I64],
     "mat_create_from_coo_dev": [VP, VP, VP, I64, I32, I32, I64, I64, C.POINTER(VP)],
     "mat_create_from_compressed_dev": [I32, I32, I32, VP, VP, VP, I64, I64, I64, C.POINTER(VP)],
+    "mat_combine": [VP, F64, VP, F64, I64, I64, I64, I64, C.POINTER(VP)],
     "pcsc_check": [VP, P_I64],
 }
 

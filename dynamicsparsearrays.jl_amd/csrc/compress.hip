@@ -4,7 +4,7 @@
 // live partition (the tables are in key order at every API boundary).  With O(s) = occupied slots in front of s and R(s) = semaphores
 // at or in front of s, the cell goes to position O(s) - R(s) of idx / val, and the partition whose semaphore sits at s starts at
 // O(s) - R(s) + 1.  Three launches, no host wait in between:
-//   k_cx_count  one wave per 2048-slot tile: occupied slots (a popcount of the tile's 32 bitmap words); the table: live semaphores per tile
+//   k_cx_count  (export_dev.h) one wave per 2048-slot tile: occupied slots (a popcount of the tile's 32 bitmap words); the table: live semaphores per tile
 //   k_cx_scan   one workgroup: exclusive prefixes of both counts, the totals checked against the host's counts, ptr behind the last
 //               live partition
 //   k_cx_emit   one wave per tile: keys and values streamed once (non-temporal), cells to idx / val, and at every semaphore the ptr run
@@ -19,62 +19,7 @@
 
 namespace dsa {
 
-// scratch: the four per-tile arrays, then the error word and the ticket of the emit (the memset covers sem_cnt .. ticket)
-struct CxScratch {
-    int64_t* occ_off; int64_t* sem_off;                  // exclusive prefixes (k_cx_scan)
-    uint32_t* occ_cnt; uint32_t* sem_cnt;                // per tile
-    uint32_t* err; uint32_t* ticket;
-    int64_t tiles;
-};
-static CxScratch cx_carve(void* base, int64_t tiles) {
-    CxScratch s;
-    s.occ_off = static_cast<int64_t*>(base);
-    s.sem_off = s.occ_off + tiles;
-    s.occ_cnt = reinterpret_cast<uint32_t*>(s.sem_off + tiles);
-    s.sem_cnt = s.occ_cnt + tiles;
-    s.err = s.sem_cnt + tiles;
-    s.ticket = s.err + 1;
-    s.tiles = tiles;
-    return s;
-}
-static int64_t cx_tiles(int64_t capacity) { return capacity > 0 ? (capacity + EX_TILE - 1) >> EX_TILE_SHIFT : 1; }
-size_t compress_scratch_bytes(int64_t capacity) { return (size_t)cx_tiles(capacity) * 24 + 8; }
-
-// blocks [0, tile_blocks): four tiles each; the rest: 256 table entries each.  Live semaphores ascend with the id, so the entries of
-// a wave fall into few tiles: one atomic per (wave, tile).
-__global__ __launch_bounds__(256) void k_cx_count(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
-                                                  const uint8_t* __restrict__ col_live, int64_t table_len, int64_t tile_blocks, CxScratch s) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if ((int64_t)blockIdx.x < tile_blocks) {
-        const int64_t t = (int64_t)blockIdx.x * 4 + wv;
-        if (t >= s.tiles) return;
-        const int64_t w = t * EX_WORDS + lane, nwords = (capacity + 63) >> 6;
-        int c = lane < EX_WORDS && w < nwords ? popc64(__builtin_nontemporal_load(occ + w)) : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        if (lane == 0) s.occ_cnt[t] = (uint32_t)c;
-        return;
-    }
-    const int64_t i = ((int64_t)blockIdx.x - tile_blocks) * 256 + threadIdx.x;
-    int64_t tile = -1;
-    uint32_t bad = 0;
-    if (i < table_len) {
-        const int64_t sp = sems[i];
-        const bool live = col_live == nullptr || col_live[i] != 0;
-        if ((sp != 0) != live || sp < 0 || sp > capacity) bad = 2;          // tables out of step with each other or with the slots
-        else if (sp != 0) tile = (sp - 1) >> EX_TILE_SHIFT;
-    }
-    uint64_t todo = __ballot(tile >= 0);
-    while (todo) {
-        const int leader = __ffsll((unsigned long long)todo) - 1;
-        const int64_t t0 = (int64_t)readlane64((uint64_t)tile, leader);
-        const uint64_t m = __ballot(tile == t0);
-        if (lane == leader) atomicAdd(s.sem_cnt + t0, (uint32_t)popc64(m));
-        todo &= ~m;
-    }
-    bad = wave_or(bad);
-    if (lane == 0 && bad) atomicOr(s.err, bad);
-}
+size_t compress_scratch_bytes(int64_t capacity) { return cx_scratch_bytes(cx_tiles(capacity)); }
 
 // one workgroup: occ_off / sem_off; totals against the host's counts; ptr[k] = base + nnz for k from the last live key to dim_out
 template <typename IT>
@@ -220,8 +165,8 @@ hipError_t launch_to_compressed(const SlotView& V, int64_t nparts, int64_t nnz, 
     hipError_t e = hipMemsetAsync(s.sem_cnt, 0, (size_t)tiles * sizeof(uint32_t) + 8, stream);
     if (e != hipSuccess) return e;
     const int64_t tile_blocks = (tiles + 3) / 4, table_blocks = (V.table_len + 255) / 256;
-    hipLaunchKernelGGL(k_cx_count, dim3((unsigned)(tile_blocks + table_blocks)), dim3(256), 0, stream, V.occ, V.capacity, V.sems, V.part_live,
-                       V.table_len, tile_blocks, s);
+    hipLaunchKernelGGL(k_cx_count<false>, dim3((unsigned)(tile_blocks + table_blocks)), dim3(256), 0, stream, V.occ, V.capacity, V.sems, V.part_live,
+                       V.table_len, tile_blocks, s, static_cast<unsigned long long*>(nullptr));
     if (index_bits == 32)
         hipLaunchKernelGGL(k_cx_scan<int32_t>, dim3(1), dim3(EX_SCAN_THREADS), 0, stream, s, V.sems, V.part_keys, V.table_len, nparts, nnz,
                            dim_out, base, static_cast<int32_t*>(d_ptr));

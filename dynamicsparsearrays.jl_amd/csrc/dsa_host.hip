@@ -634,6 +634,14 @@ int32_t dsa_mat_create_from_compressed_dev(int32_t orientation, int32_t index_bi
     *out = mat_from_compressed_dev(orientation, index_bits, index_base, d_ptr, d_idx, d_vals, outer, inner, nnz);
     API_CATCH
 }
+// alpha * a + beta * shift(b) as a new matrix: copy, A + B, hcat, vcat, blockdiag (combine_host.hip)
+int32_t dsa_mat_combine(dsa_mat_t* a, double alpha, dsa_mat_t* b, double beta, int64_t row_off, int64_t col_off, int64_t m, int64_t n,
+                        dsa_mat_t** out) {
+    API_TRY
+    if (!a || !out) fail(DSA_EARG, "the first operand or out is NULL");
+    *out = mat_combine(a, alpha, b, beta, row_off, col_off, m, n);
+    API_CATCH
+}
 // ---------------- column-range shards (the reference is single-process) ----------------
 // shard g of G owns the global column keys (col0, col0 + ncols]: n / G columns each, the first n % G shards one more
 int32_t dsa_shard_range(int64_t n, int32_t nshards, int32_t shard, int64_t* col0, int64_t* ncols) {

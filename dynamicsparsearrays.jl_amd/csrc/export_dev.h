@@ -1,6 +1,7 @@
 // csrc/export_dev.h — what the export kernel units share (compress.hip: the whole orientation, select.hip: the partitions of
 // a key list, submatrix.hip: those partitions restricted to an inner key list): the tile they cut the slot array into, the block
-// scan between their count and emit launches, and the ends of a scan and of an emit kernel.  For the two key-list exports also the
+// scan between their count and emit launches, and the ends of a scan and of an emit kernel; the tile count of a whole orientation
+// (k_cx_count), which compress.hip shares with combine.hip.  For the two key-list exports also the
 // whole work-item pipeline: the span kernel of the outer keys (k_key_spans, around key_span of find_dev.h), the owner of a work item (item_past, item_owner), its part of the
 // span and its bitmap words (span_chunk, chunk_word), the grid of the item kernels (ex_grid) and the choice of an emit instantiation (dispatch_wide_it).
 // Device code, and the two host helpers of its launches.
@@ -74,6 +75,71 @@ __device__ __forceinline__ void block_excl_scan2(const T* a, const T* b, int64_t
         __syncthreads();
     }
     tot_a = carry_o; tot_b = carry_s;
+}
+
+// ---- the tile pass over a whole orientation (compress.hip: CSC / CSR; combine.hip: shifted triples).  Scratch: the four per-tile
+// arrays, then the error word and the ticket of the emit (the memset of a launch covers sem_cnt .. ticket)
+struct CxScratch {
+    int64_t* occ_off; int64_t* sem_off;                  // exclusive prefixes (the scan kernel of the unit)
+    uint32_t* occ_cnt; uint32_t* sem_cnt;                // per tile
+    uint32_t* err; uint32_t* ticket;
+    int64_t tiles;
+};
+static inline CxScratch cx_carve(void* base, int64_t tiles) {
+    CxScratch s;
+    s.occ_off = static_cast<int64_t*>(base);
+    s.sem_off = s.occ_off + tiles;
+    s.occ_cnt = reinterpret_cast<uint32_t*>(s.sem_off + tiles);
+    s.sem_cnt = s.occ_cnt + tiles;
+    s.err = s.sem_cnt + tiles;
+    s.ticket = s.err + 1;
+    s.tiles = tiles;
+    return s;
+}
+static inline int64_t cx_tiles(int64_t capacity) { return capacity > 0 ? (capacity + EX_TILE - 1) >> EX_TILE_SHIFT : 1; }
+static inline size_t cx_scratch_bytes(int64_t tiles) { return (size_t)tiles * 24 + 8; }
+
+// blocks [0, tile_blocks): four tiles each; the rest: 256 table entries each.  Live semaphores ascend with the id, so the entries of
+// a wave fall into few tiles: one atomic per (wave, tile).  With LAST, last_id[t] (zeroed by the caller) also receives the id of the
+// last semaphore of tile t, 0 for a tile without one: a tombstoned id has no semaphore and never gets there.  (A template like
+// k_key_spans, so that only the units that launch it hold a copy.)
+template <bool LAST>
+__global__ __launch_bounds__(256) void k_cx_count(const uint64_t* __restrict__ occ, int64_t capacity, const int64_t* __restrict__ sems,
+                                                  const uint8_t* __restrict__ col_live, int64_t table_len, int64_t tile_blocks, CxScratch s,
+                                                  unsigned long long* __restrict__ last_id) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if ((int64_t)blockIdx.x < tile_blocks) {
+        const int64_t t = (int64_t)blockIdx.x * 4 + wv;
+        if (t >= s.tiles) return;
+        const int64_t w = t * EX_WORDS + lane, nwords = (capacity + 63) >> 6;
+        int c = lane < EX_WORDS && w < nwords ? popc64(__builtin_nontemporal_load(occ + w)) : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        if (lane == 0) s.occ_cnt[t] = (uint32_t)c;
+        return;
+    }
+    const int64_t i = ((int64_t)blockIdx.x - tile_blocks) * 256 + threadIdx.x;
+    int64_t tile = -1;
+    uint32_t bad = 0;
+    if (i < table_len) {
+        const int64_t sp = sems[i];
+        const bool live = col_live == nullptr || col_live[i] != 0;
+        if ((sp != 0) != live || sp < 0 || sp > capacity) bad = 2;          // tables out of step with each other or with the slots
+        else if (sp != 0) tile = (sp - 1) >> EX_TILE_SHIFT;
+    }
+    uint64_t todo = __ballot(tile >= 0);
+    while (todo) {
+        const int leader = __ffsll((unsigned long long)todo) - 1;
+        const int64_t t0 = (int64_t)readlane64((uint64_t)tile, leader);
+        const uint64_t m = __ballot(tile == t0);
+        if (lane == leader) {
+            atomicAdd(s.sem_cnt + t0, (uint32_t)popc64(m));
+            if (LAST) atomicMax(last_id + t0, (unsigned long long)(i - lane + (63 - __clzll((unsigned long long)m)) + 1));      // ids ascend with the lane
+        }
+        todo &= ~m;
+    }
+    bad = wave_or(bad);
+    if (lane == 0 && bad) atomicOr(s.err, bad);
 }
 
 // occupied slots of [from, to) (0-based, from < to): the lanes stride over the words, first and last word masked
@@ -223,20 +289,23 @@ __device__ __forceinline__ void hand_over(const uint32_t* err_word, unsigned lon
 }
 
 // The end of an emit kernel (256 threads, every one arrives): the error bits of the workgroup go into the scratch word, and the
-// workgroup that takes the last ticket hands {error word, seq} to pinned memory.
-__device__ __forceinline__ void emit_epilogue(uint32_t err, int lane, int wv, uint32_t* err_word, uint32_t* ticket,
-                                              unsigned long long* pinned, unsigned long long seq) {
+// workgroup that takes the last ticket hands {error word, seq} to pinned memory (emit_epilogue).  emit_last is the part in front of
+// the hand-over for an emit with more to hand over than the error word: true in the one thread that has to do it.
+__device__ __forceinline__ bool emit_last(uint32_t err, int lane, int wv, uint32_t* err_word, uint32_t* ticket) {
     __shared__ uint32_t sErr[4];
     err = wave_or(err);
     if (lane == 0) sErr[wv] = err;
     __syncthreads();
-    if (threadIdx.x != 0) return;
+    if (threadIdx.x != 0) return false;
     err = sErr[0] | sErr[1] | sErr[2] | sErr[3];
     if (err) __hip_atomic_fetch_or(err_word, err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_s_waitcnt(0);
     const uint32_t tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tk != gridDim.x - 1) return;
-    hand_over(err_word, pinned, seq);                            // the last workgroup: every other one has added its bits before its ticket
+    return tk == gridDim.x - 1;                                  // the last workgroup: every other one has added its bits before its ticket
+}
+__device__ __forceinline__ void emit_epilogue(uint32_t err, int lane, int wv, uint32_t* err_word, uint32_t* ticket,
+                                              unsigned long long* pinned, unsigned long long seq) {
+    if (emit_last(err, lane, wv, err_word, ticket)) hand_over(err_word, pinned, seq);
 }
 
 }  // namespace dsa

@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, fill_host.hip, matwrite_host.hip, pma_host.hip,
-// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip and raw_host.hip.  Host units only: a kernel unit
+// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -165,6 +165,9 @@ struct Pma {
     ExportArea del;
     // dropzeros! / droptol! (droptol.hip): the scale scratch, the counter and the drop masks; the pinned {error word, count, sequence number}
     ExportArea drp;
+    // combine (combine.hip): the tile arrays, range words and last-semaphore ids of a pass over this orientation; the pinned words of
+    // the two roles an operand can have (2 x {error word, four range words, sequence number})
+    ExportArea cmb;
     // thresholds  src/pma.jl:58,70,87
     double t_h = 0.7, t_0 = 0.92, p_h = 0.3, p_0 = 0.08, t_d = 0.0, p_d = 0.0;
 
@@ -313,6 +316,10 @@ dsa_mat* mat_from_coo_dev(const void* d_I, const void* d_J, const double* d_V, i
                           int64_t m, int64_t n);
 dsa_mat* mat_from_compressed_dev(int32_t orientation, int32_t index_bits, int32_t index_base, const void* d_ptr, const void* d_idx,
                                  const double* d_vals, int64_t outer, int64_t inner, int64_t nnz);
+
+// ---- combine_host.hip: alpha * a + beta * b with b's keys shifted by (row_off, col_off), as a new handle of size m x n (< 0: the
+// smallest that holds both operands); b may be nullptr (a copy, scaled) or a itself.  The operands are only read.
+dsa_mat* mat_combine(dsa_mat* a, double alpha, dsa_mat* b, double beta, int64_t row_off, int64_t col_off, int64_t m, int64_t n);
 
 // ---- spmm_host.hip: the dense multi-vector product (spmm_host: X and Y in host memory, staged packed through HBM)
 void spmm_dev(dsa_mat* h, int32_t transpose, const double* d_x, int64_t nx, int64_t k, int64_t ldx, double* d_y, int64_t ny, int64_t ldy,

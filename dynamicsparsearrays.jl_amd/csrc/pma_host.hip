@@ -71,6 +71,7 @@ void pma_destroy(Pma& P) {
     P.sc.release();
     P.del.release();
     P.drp.release();
+    P.cmb.release();
     P.spg.release();
     P.spgs.release();
     if (P.tmerge.sems2) hipFree(P.tmerge.sems2);

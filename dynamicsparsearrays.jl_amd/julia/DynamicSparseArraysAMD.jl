@@ -734,4 +734,39 @@ SparseArrays.dropzeros!(a::DynamicSparseMatrix) = SparseArrays.droptol!(a, 0.0)
 count_droptol(a::DynamicSparseMatrix, tol::Real; rows::Union{Nothing,AbstractVector{<:Real}} = nothing,
               cols::Union{Nothing,AbstractVector{<:Real}} = nothing) = _droptol(a, tol, rows, cols, true)
 
+# Combine on the device (include/dsa.h: dsa_mat_combine; not in the reference, whose Base.copy of a vector is an error and whose
+# MappedPackedCSC(mpcsc) is a host deepcopy): alpha * a + beta * b with b's integer keys shifted by (row_off, col_off), as a NEW matrix —
+# the one dynamicsparse builds from findnz(a), scaled, followed by findnz(b), shifted and scaled.  A cell of both operands is their sum; a
+# sum that cancels stays a stored zero (dropzeros!).  The operands are only read.  m, n < 0: the smallest size that holds both.
+_merge(x::KeyMap{K}, y::KeyMap{K}) where {K} = KeyMap{K}(x.seen === nothing ? nothing : merge(x.seen, y.seen))
+function _combine(a::DynamicSparseMatrix{K,L}, alpha::Real, b::Union{Nothing,DynamicSparseMatrix{K,L}}, beta::Real, row_off::Integer,
+                  col_off::Integer, m::Integer = -1, n::Integer = -1) where {K,L}
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve a b _check(ccall((:dsa_mat_combine, libdsa), Int32,
+        (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Float64, Int64, Int64, Int64, Int64, Ref{Ptr{Cvoid}}),
+        a.h, Float64(alpha), b === nothing ? C_NULL : b.h, Float64(beta), row_off, col_off, m, n, out))
+    b === nothing && return DynamicSparseMatrix{K,L}(out[], _merge(a.rows, a.rows), _merge(a.cols, a.cols))
+    return DynamicSparseMatrix{K,L}(out[], _merge(a.rows, b.rows), _merge(a.cols, b.cols))
+end
+Base.copy(a::DynamicSparseMatrix) = _combine(a, 1.0, nothing, 0.0, 0, 0)
+Base.:+(a::DynamicSparseMatrix{K,L}, b::DynamicSparseMatrix{K,L}) where {K,L} = _combine(a, 1.0, b, 1.0, 0, 0)
+Base.:-(a::DynamicSparseMatrix{K,L}, b::DynamicSparseMatrix{K,L}) where {K,L} = _combine(a, 1.0, b, -1.0, 0, 0)
+Base.:-(a::DynamicSparseMatrix) = _combine(a, -1.0, nothing, 0.0, 0, 0)
+Base.:*(alpha::Real, a::DynamicSparseMatrix) = _combine(a, alpha, nothing, 0.0, 0, 0)
+# concatenation shifts keys, so it is for integer keys: [a b] needs equal row counts, [a; b] equal column counts
+function Base.hcat(a::DynamicSparseMatrix{K,L}, b::DynamicSparseMatrix{K,L}) where {K<:Integer,L<:Integer}
+    (ma, na), (mb, _) = _size_int(a), _size_int(b)
+    ma == mb || throw(ArgumentError("hcat: the operands have $ma and $mb rows"))
+    return _combine(a, 1.0, b, 1.0, 0, na)
+end
+function Base.vcat(a::DynamicSparseMatrix{K,L}, b::DynamicSparseMatrix{K,L}) where {K<:Integer,L<:Integer}
+    (ma, na), (_, nb) = _size_int(a), _size_int(b)
+    na == nb || throw(ArgumentError("vcat: the operands have $na and $nb columns"))
+    return _combine(a, 1.0, b, 1.0, ma, 0)
+end
+function SparseArrays.blockdiag(a::DynamicSparseMatrix{K,L}, b::DynamicSparseMatrix{K,L}) where {K<:Integer,L<:Integer}
+    ma, na = _size_int(a)
+    return _combine(a, 1.0, b, 1.0, ma, na)
+end
+
 end # module

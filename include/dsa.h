@@ -172,6 +172,23 @@ int32_t dsa_mat_create_from_coo_dev(const void* d_I, const void* d_J, const doub
 int32_t dsa_mat_create_from_compressed_dev(int32_t orientation, int32_t index_bits, int32_t index_base,
                                            const void* d_ptr, const void* d_idx, const double* d_vals,
                                            int64_t outer, int64_t inner, int64_t nnz, dsa_mat_t** out);
+/* Combine: a new matrix out of one or two existing ones, on the device (not in the reference: Base.copy, +, -, hcat, vcat and
+ * blockdiag of the wrappers are all this call).  The result is the matrix dsa_mat_create_from_coo(I, J, V, m, n) builds, slot for
+ * slot, from this triple list in this order: every stored cell of `a` in the slot order of its colmajor orientation (the findnz
+ * order) as (i, j, alpha * v), then every stored cell of `b` in the same order as (i + row_off, j + col_off, beta * v).
+ * b == NULL: no second operand (beta, row_off, col_off ignored): copy / alpha * A.  b == a is allowed (A + A).
+ * One IEEE multiply per cell, also for a factor 1.0; no add: a key present in both operands is summed by the builder as it sums any
+ * duplicate in input order, a sum that cancels stays a stored zero (dsa_mat_droptol), stored zeros of the operands stay stored.
+ * m, n >= 0 give size(result); m < 0: max(a.m, b.m + row_off) (a.m without b), n < 0 likewise.
+ * The operands are only read: slots, tables, epochs and cached SpMV plans are untouched.  *out is a fresh handle out of fill mode.
+ * The number of launches and host waits does not depend on nnz or on the number of partitions.
+ * DSA_EMODE: an operand is in fill mode.  DSA_EARG: a or out NULL, nnz(a) + nnz(b) > 2^32 - 1, an offset whose sum with a stored key or
+ * with a dimension leaves int64.  DSA_EKEY: a shifted key equals 0 (found on the device).  DSA_EBOUNDS with col_off != 0: a or b holds
+ * a stored entry whose column key lies outside 1 .. n of its own size(); with row_off != 0 the same for rows (a shifted block must
+ * not silently land on the other operand's cells; with both offsets 0 nothing is bounds-checked: negative or out-of-size keys are
+ * copied and added as they are).  DSA_EASSERT: slots and tables disagree.  On any error *out is untouched and nothing stays allocated. */
+int32_t dsa_mat_combine(dsa_mat_t* a, double alpha, dsa_mat_t* b, double beta, int64_t row_off, int64_t col_off,
+                        int64_t m, int64_t n, dsa_mat_t** out);
 /* dynamicsparse(K, L, T; fill_mode)  src/matrix.jl:31-41 */
 int32_t dsa_mat_create_empty(int32_t fill_mode, dsa_mat_t** out);
 int32_t dsa_mat_destroy(dsa_mat_t* h);

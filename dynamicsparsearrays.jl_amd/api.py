@@ -23,6 +23,8 @@ from .binding import Binding, INFO, INFO_COUNT, P_F64, P_I64, P_U8, VP, _f64, _i
 
 COMBINE = {"+": 0, "add": 0, "*": 1, "mul": 1, "last": 2}
 COLMAJOR, ROWMAJOR = 0, 1
+UPD_SET, UPD_ADD = 0, 1                  # DSA_UPD_*: the op of update_values_dev
+UPD_SKIP_MISSING = 1                     # ... and its flag
 
 
 def _bind(b):
@@ -321,6 +323,13 @@ class Transposed:
         if per not in ("row", "column"):
             raise B.DsaArgumentError(B.EARG, "per must be 'row' or 'column'")
         return self.array.reduce(kind, "column" if per == "row" else "row", out=out)
+
+    def update_values(self, I, J, V, op="set", missing="error"):
+        """transpose(mat)[I[k], J[k]] = V[k] on stored cells: update_values of the matrix with the sides swapped"""
+        return self.array.update_values(J, I, V, op=op, missing=missing)
+
+    def add_values(self, I, J, V, missing="error"):
+        return self.array.update_values(J, I, V, op="add", missing=missing)
 
 
 class DynamicSparseMatrix(_Handle):
@@ -1174,6 +1183,84 @@ class DynamicSparseMatrix(_Handle):
         self.b.call("mat_droptol_dev", self.h, float(tol), C.c_void_p(int(d_r)) if d_r else None, int(nr),
                     C.c_void_p(int(d_c)) if d_c else None, int(nc), 1 if count_only else 0, C.byref(got))
         return got.value
+
+    # ---- update of stored values in place (include/dsa.h: dsa_mat_update_values[_dev], dsa_mat_get_batch_dev; HIP library only) ---
+    _UPDATE_NEEDS = "update_values, add_values and get_batch_dev need the HIP product library"
+
+    @staticmethod
+    def _update_op(op):
+        try:
+            return {"set": UPD_SET, "add": UPD_ADD, UPD_SET: UPD_SET, UPD_ADD: UPD_ADD}[op]
+        except (KeyError, TypeError):
+            raise B.DsaArgumentError(B.EARG, "op must be 'set' or 'add'") from None
+
+    def update_values(self, I, J, V, op="set", missing="error"):
+        """A[I[k], J[k]] = V[k] (op "set") or += V[k] ("add") for cells that are ALREADY STORED, in place on the device: no cell is
+        created, deleted or moved, so the call does not go through the write planner of set_batch.  "set" keeps the bits of V
+        (a 0.0 leaves a stored zero: dropzeros() removes it); a cell addressed more than once ends with the last value; "add"
+        must address a cell at most once.  missing="error": a cell that is not stored raises DsaArgumentError and nothing is
+        modified; "skip": such ops are skipped and the call returns (updated, missing_mask) — send the masked triples through
+        set_batch.  Otherwise returns the number of cells written.  I, J, V: sequences or numpy arrays, or tensors on the GPU
+        (int64, int64, float64; all three of the same kind), which are used where they are.  Cached SpMV plans are dropped only
+        when a value is written."""
+        self._require("mat_update_values", self._UPDATE_NEEDS)
+        opc = self._update_op(op)
+        if missing not in ("error", "skip"):
+            raise B.DsaArgumentError(B.EARG, "missing must be 'error' or 'skip'")
+        skip = missing == "skip"
+        flags = UPD_SKIP_MISSING if skip else 0
+        ops = (I, J, V)
+        is_t = [type(x).__module__.split(".")[0] == "torch" for x in ops]
+        if any(is_t):
+            import torch
+            if not all(is_t):
+                raise B.DsaArgumentError(B.EARG, "I, J and V must all be numpy arrays or all be tensors on the GPU")
+            for x, dt in zip(ops, (torch.int64, torch.int64, torch.float64)):
+                if x.dtype != dt or not x.is_cuda or x.dim() != 1 or x.numel() != I.numel():
+                    raise B.DsaArgumentError(B.EARG, "I, J, V must be 1-D int64, int64, float64 tensors of one length on the GPU")
+            i, j, v = (x.contiguous() for x in ops)
+            n = i.numel()
+            mask = torch.zeros(n, dtype=torch.uint8, device=i.device) if skip else None
+            # the library reads the triples on its own two streams: torch's pending work on them must be over first, and they must
+            # stay as they are until the stores have finished
+            torch.cuda.current_stream(i.device).synchronize()
+            updated, _ = self.update_values_dev(i.data_ptr(), j.data_ptr(), v.data_ptr(), n, opc, flags,
+                                                d_missing=mask.data_ptr() if skip and n else None)
+            self.sync()
+            return (updated, mask.bool()) if skip else updated
+        i, ip = _i64(np.asarray(I, dtype=np.int64).reshape(-1))
+        j, jp = _i64(np.asarray(J, dtype=np.int64).reshape(-1))
+        v, vp = _f64(np.asarray(V, dtype=np.float64).reshape(-1))
+        if not (len(i) == len(j) == len(v)):
+            raise B.DsaArgumentError(B.EARG, "rows, columns, and nonzeros do not have same length.")
+        mask = np.zeros(len(i), dtype=np.uint8)
+        upd, mis = C.c_int64(), C.c_int64()
+        self.b.call("mat_update_values", self.h, opc, flags, ip, jp, vp, len(i), mask.ctypes.data_as(P_U8) if skip else None,
+                    C.byref(upd), C.byref(mis))
+        return (upd.value, mask.astype(bool)) if skip else upd.value
+
+    def add_values(self, I, J, V, missing="error"):
+        """A[I[k], J[k]] += V[k] on stored cells: update_values(I, J, V, op="add")"""
+        return self.update_values(I, J, V, op="add", missing=missing)
+
+    def update_values_dev(self, d_I, d_J, d_V, n, op=UPD_SET, flags=0, d_missing=None):
+        """update_values with the triples in HBM (device addresses of n int64, int64, float64 entries, complete at the call and
+        unchanged until sync()); op UPD_SET | UPD_ADD, flags 0 | UPD_SKIP_MISSING, d_missing: device address of n bytes that receive
+        1 for an op without a stored cell, or None.  The host waits for the verdict only: the stores are enqueued on the two
+        streams (sync()).  Returns (updated, missing): cells written and ops without a stored cell."""
+        self._require("mat_update_values", self._UPDATE_NEEDS)
+        upd, mis = C.c_int64(), C.c_int64()
+        self.b.call("mat_update_values_dev", self.h, int(op), int(flags), C.c_void_p(int(d_I)) if d_I else None,
+                    C.c_void_p(int(d_J)) if d_J else None, C.c_void_p(int(d_V)) if d_V else None, int(n),
+                    C.c_void_p(int(d_missing)) if d_missing else None, C.byref(upd), C.byref(mis))
+        return upd.value, mis.value
+
+    def get_batch_dev(self, d_I, d_J, n, d_out, d_found=None):
+        """get_batch with everything in HBM: d_out[k] = A[d_I[k], d_J[k]] (0.0 when the cell is not stored), d_found[k] (n bytes,
+        optional) = 1 iff it is stored.  Device addresses; enqueued on the colmajor stream, no host wait (sync())."""
+        self._require("mat_update_values", self._UPDATE_NEEDS)
+        self.b.call("mat_get_batch_dev", self.h, C.c_void_p(int(d_I)) if d_I else None, C.c_void_p(int(d_J)) if d_J else None, int(n),
+                    C.c_void_p(int(d_out)) if d_out else None, C.c_void_p(int(d_found)) if d_found else None)
 
 
 def dynamicsparse(I=None, J=None, V=None, m=None, n=None, fill_mode=True,

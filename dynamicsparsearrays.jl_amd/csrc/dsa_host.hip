@@ -1070,6 +1070,50 @@ int32_t dsa_mat_droptol(dsa_mat_t* h, double tol, const double* rtol, int64_t nr
     API_CATCH
 }
 
+// ---- update of stored values in place (update.hip) and the batched read into HBM.  Locate, claim and resolve are in front of the
+// epoch bump: an error and a call without a winning write leave layouts and cached plans as they were
+namespace {
+void mat_update_values(dsa_mat_t* h, int32_t op, int32_t flags, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n,
+                       uint8_t* d_missing, int64_t* updated_out, int64_t* missing_out) {
+    const UpdateCounts c = update_prepare(h, op, flags, d_I, d_J, d_V, n, d_missing);
+    if (c.updated > 0) {
+        mat_content_changed(h);
+        update_apply(h, op, d_V, n);
+    }
+    if (updated_out) *updated_out = c.updated;
+    if (missing_out) *missing_out = c.missing;
+}
+}  // namespace
+int32_t dsa_mat_update_values_dev(dsa_mat_t* h, int32_t op, int32_t flags, const int64_t* d_I, const int64_t* d_J, const double* d_V,
+                                  int64_t n, uint8_t* d_missing, int64_t* updated_out, int64_t* missing_out) {
+    API_TRY
+    if (updated_out) *updated_out = 0;
+    if (missing_out) *missing_out = 0;
+    mat_update_values(h, op, flags, d_I, d_J, d_V, n, d_missing, updated_out, missing_out);
+    API_CATCH
+}
+int32_t dsa_mat_update_values(dsa_mat_t* h, int32_t op, int32_t flags, const int64_t* I, const int64_t* J, const double* V, int64_t n,
+                              uint8_t* missing, int64_t* updated_out, int64_t* missing_out) {
+    API_TRY
+    if (updated_out) *updated_out = 0;
+    if (missing_out) *missing_out = 0;
+    UpdateStaging st(h, op, flags, I, J, V, n, missing != nullptr);      // flush, DSA_EMODE / DSA_EARG, the triples in HBM until both streams have drained
+    if (n > 0) {
+        uint8_t* d_missing = static_cast<uint8_t*>(st.b.p[3]);
+        mat_update_values(h, op, flags, static_cast<const int64_t*>(st.b.p[0]), static_cast<const int64_t*>(st.b.p[1]),
+                          static_cast<const double*>(st.b.p[2]), n, d_missing, updated_out, missing_out);
+        if (missing) HIPCHK(hipMemcpyAsync(missing, d_missing, (size_t)n, hipMemcpyDeviceToHost, h->col.stream));
+        HIPCHK(hipStreamSynchronize(h->col.stream));
+        HIPCHK(hipStreamSynchronize(h->row.stream));
+    }
+    API_CATCH
+}
+int32_t dsa_mat_get_batch_dev(dsa_mat_t* h, const int64_t* d_I, const int64_t* d_J, int64_t n, double* d_out, uint8_t* d_found) {
+    API_TRY
+    get_batch_dev(h, d_I, d_J, n, d_out, d_found);
+    API_CATCH
+}
+
 int32_t dsa_mat_check(dsa_mat_t* h, int32_t o, int64_t* report) { API_TRY mat_flush(h); pma_check(orient(h, o), report); API_CATCH }
 int32_t dsa_mat_set_stream(dsa_mat_t* h, void* s) {
     API_TRY

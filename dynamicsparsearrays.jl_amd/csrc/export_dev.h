@@ -242,9 +242,10 @@ static inline size_t sub_key_block_bytes(int64_t nouter, int64_t ninner) {
 }
 static inline size_t sub_key_block_clear_bytes(const SubKeys& s) { return 16 + (size_t)(s.tmask + 1) * 8; }      // error word, ticket, every key word
 
-__device__ __forceinline__ uint64_t sub_slot(const SubKeys& s, int64_t key) {
-    return ((uint64_t)key * 0x9E3779B97F4A7C15ull) >> s.tshift;
-}
+// Fibonacci hashing into a table of 2^(64 - shift) entries: the first entry a key probes in every open-addressing table of the
+// library (the key tables here, the claim table of update.hip); a probe moves on by one entry, wrapping at the end
+__device__ __forceinline__ uint64_t fib_bucket(uint64_t key, int shift) { return (key * 0x9E3779B97F4A7C15ull) >> shift; }
+__device__ __forceinline__ uint64_t sub_slot(const SubKeys& s, int64_t key) { return fib_bucket((uint64_t)key, s.tshift); }
 // the entry that holds `key` (>= 1), given the key word t already loaded from its first entry p; SUB_NONE if the key is not listed
 __device__ __forceinline__ uint64_t sub_resolve(const SubKeys& s, int64_t key, uint64_t p, int64_t t) {
     for (uint64_t n = 0; n <= s.tmask; ++n) {

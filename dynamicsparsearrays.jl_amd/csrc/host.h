@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, fill_host.hip, matwrite_host.hip, pma_host.hip,
-// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
+// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -165,6 +165,10 @@ struct Pma {
     ExportArea del;
     // dropzeros! / droptol! (droptol.hip): the scale scratch, the counter and the drop masks; the pinned {error word, count, sequence number}
     ExportArea drp;
+    // update_values (update.hip): colmajor the resolve records, the claim table, the slots and the winner flags, rowmajor its slots; the
+    // pinned words of the one hand-over (colmajor); the event that orders the two streams of a call
+    ExportArea upd;
+    hipEvent_t ev_upd = nullptr;
     // combine (combine.hip): the tile arrays, range words and last-semaphore ids of a pass over this orientation; the pinned words of
     // the two roles an operand can have (2 x {error word, four range words, sequence number})
     ExportArea cmb;
@@ -391,6 +395,22 @@ void respread(Pma& X);
 // both control blocks uploaded and both streams drained).
 int64_t droptol_prepare(dsa_mat* h, double tol, const double* d_rtol, int64_t nr, const double* d_ctol, int64_t nc);
 void droptol_apply(dsa_mat* h, int64_t count);
+
+// ---- update_host.hip: the values of stored cells overwritten (DSA_UPD_SET) or added to (DSA_UPD_ADD) from triples in HBM, and the
+// batched read into HBM (d_* are device arrays).  Two steps so that the entry point can bump the content epoch between them:
+// update_prepare (flush, checks, locate + claim + resolve over both orientations: DSA_EMODE / DSA_EARG / DSA_EKEY / DSA_EASSERT with
+// nothing modified; returns the winning and the missing ops) and update_apply (the stores, enqueued on both streams).  UpdateStaging
+// holds triples that came from host memory (p[0..2]; p[3]: the missing flags) in HBM until both streams have drained.
+struct UpdateCounts { int64_t updated, missing; };
+UpdateCounts update_prepare(dsa_mat* h, int32_t op, int32_t flags, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n,
+                            uint8_t* d_missing);
+void update_apply(dsa_mat* h, int32_t op, const double* d_V, int64_t n);
+void get_batch_dev(dsa_mat* h, const int64_t* d_I, const int64_t* d_J, int64_t n, double* d_out, uint8_t* d_found);
+struct UpdateStaging {
+    dsa_mat* h; DevStaging b;
+    UpdateStaging(dsa_mat* h, int32_t op, int32_t flags, const int64_t* I, const int64_t* J, const double* V, int64_t n, bool want_missing);
+    ~UpdateStaging();
+};
 
 // Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks
 // and uploaded asynchronously as a chunk fills (the copy of chunk k overlaps the caller's appends into chunk k+1), so that

@@ -71,6 +71,8 @@ void pma_destroy(Pma& P) {
     P.sc.release();
     P.del.release();
     P.drp.release();
+    P.upd.release();
+    if (P.ev_upd) (void)hipEventDestroy(P.ev_upd);
     P.cmb.release();
     P.spg.release();
     P.spgs.release();

@@ -34,5 +34,8 @@ const deleterows! = DynamicSparseArraysAMD.deleterows!
 const dropzeros! = DynamicSparseArraysAMD.dropzeros!              # SparseArrays' dropzeros! / droptol! in place on the device (dsa_mat_droptol):
 const droptol! = DynamicSparseArraysAMD.droptol!                  # droptol!(A, tol; rows = nothing, cols = nothing)
 const count_droptol = DynamicSparseArraysAMD.count_droptol
+const update_values! = DynamicSparseArraysAMD.update_values!      # values of stored cells overwritten / added to in place (dsa_mat_update_values)
+const add_values! = DynamicSparseArraysAMD.add_values!
+const getstored = DynamicSparseArraysAMD.getstored                # getindex_batch with every operand in HBM (dsa_mat_get_batch_dev)
 
 end # module

@@ -25,7 +25,8 @@ export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC
        deletecolumn!, deleterow!, deletecolumns!, deleterows!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
        keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev,
-       scale!, reduce_rows, reduce_cols, mul_rows, mul_cols, mul_sparse, dropzeros!, droptol!, count_droptol
+       scale!, reduce_rows, reduce_cols, mul_rows, mul_cols, mul_sparse, dropzeros!, droptol!, count_droptol,
+       update_values!, add_values!, getstored
 
 const libdsa = get(ENV, "DSA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libdsa_hip.so"))
 
@@ -733,6 +734,34 @@ end
 SparseArrays.dropzeros!(a::DynamicSparseMatrix) = SparseArrays.droptol!(a, 0.0)
 count_droptol(a::DynamicSparseMatrix, tol::Real; rows::Union{Nothing,AbstractVector{<:Real}} = nothing,
               cols::Union{Nothing,AbstractVector{<:Real}} = nothing) = _droptol(a, tol, rows, cols, true)
+
+# The values of cells that are ALREADY STORED, overwritten or added to in place on the device (include/dsa.h: dsa_mat_update_values): no
+# cell is created, deleted or moved, so the call does not go through the write planner of setindex_batch!.  A zero leaves a STORED zero
+# (not the reference's delete-on-zero: dropzeros! removes it); a cell addressed more than once by update_values! ends with the last
+# value, add_values! must address a cell at most once.  skip_missing = false: a cell that is not stored is an ArgumentError and
+# nothing is modified; true: such ops are skipped.  Returns (number of cells written, mask of the ops without a stored cell).
+function _update_values(a::DynamicSparseMatrix, op::Int32, I::AbstractVector, J::AbstractVector, V::AbstractVector, skip_missing::Bool)
+    Ii = _in(a.rows, I); Ji = _in(a.cols, J); Vf = Vector{Float64}(V)
+    length(Ii) == length(Ji) == length(Vf) || throw(ArgumentError("rows, columns, and nonzeros do not have same length."))
+    missing_mask = zeros(UInt8, length(Ii))
+    updated = Ref{Int64}(0); nmissing = Ref{Int64}(0)
+    GC.@preserve Ii Ji Vf missing_mask _check(ccall((:dsa_mat_update_values, libdsa), Int32,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{UInt8}, Ref{Int64}, Ref{Int64}),
+        a.h, op, Int32(skip_missing), Ii, Ji, Vf, length(Ii), missing_mask, updated, nmissing))
+    return updated[], missing_mask .!= 0
+end
+update_values!(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector, V::AbstractVector; skip_missing::Bool = false) =
+    _update_values(a, Int32(0), I, J, V, skip_missing)          # DSA_UPD_SET
+add_values!(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector, V::AbstractVector; skip_missing::Bool = false) =
+    _update_values(a, Int32(1), I, J, V, skip_missing)          # DSA_UPD_ADD
+"n getindex calls with every operand in HBM (device pointers; mapped key integers): d_out[k] = A[d_I[k], d_J[k]], d_found[k] (n bytes, or
+C_NULL) = 1 iff the cell is stored, which tells a stored zero from an absent cell; enqueued on the colmajor stream, no host wait —
+dsa_mat_get_batch_dev"
+function getstored(a::DynamicSparseMatrix, d_I::Ptr{Cvoid}, d_J::Ptr{Cvoid}, n::Integer, d_out::Ptr{Cvoid}, d_found::Ptr{Cvoid} = C_NULL)
+    _check(ccall((:dsa_mat_get_batch_dev, libdsa), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                 a.h, d_I, d_J, n, d_out, d_found))
+    return a
+end
 
 # Combine on the device (include/dsa.h: dsa_mat_combine; not in the reference, whose Base.copy of a vector is an error and whose
 # MappedPackedCSC(mpcsc) is a host deepcopy): alpha * a + beta * b with b's integer keys shifted by (row_off, col_off), as a NEW matrix —

@@ -494,6 +494,44 @@ int32_t dsa_mat_droptol_dev(dsa_mat_t* h, double tol, const double* d_rtol, int6
                             int32_t count_only, int64_t* dropped_out);
 int32_t dsa_mat_droptol(dsa_mat_t* h, double tol, const double* rtol, int64_t nr, const double* ctol, int64_t nc,
                         int32_t count_only, int64_t* dropped_out);
+/* Update of STORED values in place (csrc/update.hip): A[I[k], J[k]] = V[k] (DSA_UPD_SET) or A[I[k], J[k]] += V[k] (DSA_UPD_ADD, one
+ * IEEE add) for n triples, for cells that are already stored.  No reference counterpart as a bulk call: it is setindex!
+ * (src/matrix.jl:43-62) restricted to the case in which no cell is created, deleted or moved — a Jacobian or coefficient refresh on a
+ * fixed pattern, values computed on the device from exported arrays — and so it does not go through the write planner of
+ * dsa_mat_set_batch.  A cell is STORED iff dsa_mat_get_batch finds it: its column and its row are live partitions and hold the key.
+ * SET stores V[k] bit for bit (NaN payloads and -0.0 are kept).  V[k] == 0.0 leaves a STORED zero, as dsa_mat_scale does — NOT the
+ * reference's delete-on-zero: nnz is unchanged and the cell is still exported; dsa_mat_droptol removes such cells.  A cell addressed
+ * by several ops of a SET ends with the value of the LAST of them (the largest k), which is what the ops one after the other leave.
+ * ADD must address a stored cell at most once: a second op on it is DSA_EARG (an ordered sum of duplicates is not offered).
+ * Both orientations end with identical bits in every cell, and the same call on the same state gives the same bits.  Only values
+ * are written: keys, occupancy, tables, counts, capacity and the rebalance / extend statistics stay as they are.  Cached SpMV plans
+ * are dropped iff at least one value is written.
+ * MISSING cells (no live column or row, an empty one, no such key in it): without DSA_UPD_SKIP_MISSING in flags the first of them
+ * is DSA_EARG (dsa_last_error names the op) and nothing at all is modified.  With the flag they are skipped, which makes the call
+ * the front end of a general write: the caller sends only the misses through dsa_mat_set_batch.  missing[k] (may be NULL) receives
+ * 1 for an op without a stored cell, else 0 (its contents are unspecified after an error); *missing_out and *updated_out (host
+ * pointers, may be NULL) the number of missing ops and of winning writes (distinct cells written).  A call in which nothing is
+ * written changes nothing: no epoch moves, cached plans survive.
+ * Every error is found before the first write — both orientations and the cached SpMV plans stay as they were: DSA_EMODE in fill
+ * mode; DSA_EARG: op or flags invalid, n < 0, an operand NULL with n > 0, n or a capacity of 2^32 or more, a miss in the strict
+ * form, a repeated stored cell under ADD; DSA_EKEY: an I[k] or J[k] of 0, the reserved semaphore key, in both forms (checked on the
+ * device: no kernel of this call writes a slot whose key is 0); DSA_EASSERT: a cell found in one orientation and not in the other.
+ * n = 0 does nothing.  Queued single writes are applied first.  The number of launches and the one host wait do not depend on n.
+ * _dev: d_I / d_J / d_V (and d_missing) are device arrays, read on BOTH orientations' streams: they must hold their final contents
+ * when the call is made and stay valid and unchanged until dsa_mat_sync.  The host waits for the verdict only; the stores are
+ * enqueued.  The host form stages the triples through pooled device memory and waits for both streams.  For a handful of cells
+ * dsa_mat_set_batch remains the cheaper call. */
+enum { DSA_UPD_SET = 0, DSA_UPD_ADD = 1 };
+enum { DSA_UPD_SKIP_MISSING = 1 };
+int32_t dsa_mat_update_values_dev(dsa_mat_t* h, int32_t op, int32_t flags, const int64_t* d_I, const int64_t* d_J, const double* d_V,
+                                  int64_t n, uint8_t* d_missing, int64_t* updated_out, int64_t* missing_out);
+int32_t dsa_mat_update_values(dsa_mat_t* h, int32_t op, int32_t flags, const int64_t* I, const int64_t* J, const double* V, int64_t n,
+                              uint8_t* missing, int64_t* updated_out, int64_t* missing_out);
+/* dsa_mat_get_batch with everything in HBM: d_out[k] = A[d_I[k], d_J[k]] (+0.0 for a cell that is not stored), d_found[k] (may be
+ * NULL) = 1 iff the cell is stored — it tells a stored 0.0 from an absent cell.  Enqueued on the colmajor stream (dsa_mat_set_stream /
+ * dsa_mat_sync); the host does not wait.  A key of 0 reads as absent.  DSA_EMODE in fill mode; DSA_EARG for n < 0 or a NULL operand
+ * with n > 0.  Queued single writes are applied first. */
+int32_t dsa_mat_get_batch_dev(dsa_mat_t* h, const int64_t* d_I, const int64_t* d_J, int64_t n, double* d_out, uint8_t* d_found);
 /* ---- column-range shards. No reference counterpart: the reference is single-process.  One PROCESS per GPU:
  * each process selects its device (dsa_set_device), builds ITS shard and runs the local SpMV; the single data-path collective —
  * the all-reduce (sum) of the partial y — is dsa_shard_allreduce_dev below (RCCL behind this ABI), or whatever the host layer has

@@ -24,6 +24,7 @@ from .binding import Binding, INFO, INFO_COUNT, P_F64, P_I64, P_U8, VP, _f64, _i
 COMBINE = {"+": 0, "add": 0, "*": 1, "mul": 1, "last": 2}
 COLMAJOR, ROWMAJOR = 0, 1
 UPD_SET, UPD_ADD = 0, 1                  # DSA_UPD_*: the op of update_values_dev
+INS_SKIP_EXISTING = 1                    # DSA_INS_SKIP_EXISTING: the flag of insert_values_dev
 UPD_SKIP_MISSING = 1                     # ... and its flag
 
 
@@ -330,6 +331,13 @@ class Transposed:
 
     def add_values(self, I, J, V, missing="error"):
         return self.array.update_values(J, I, V, op="add", missing=missing)
+
+    def insert_values(self, I, J, V, existing="error"):
+        """transpose(mat)[I[k], J[k]] created with V[k]: insert_values of the matrix with the sides swapped"""
+        return self.array.insert_values(J, I, V, existing=existing)
+
+    def upsert(self, I, J, V):
+        return self.array.upsert(J, I, V)
 
 
 class DynamicSparseMatrix(_Handle):
@@ -1262,6 +1270,73 @@ class DynamicSparseMatrix(_Handle):
         self.b.call("mat_get_batch_dev", self.h, C.c_void_p(int(d_I)) if d_I else None, C.c_void_p(int(d_J)) if d_J else None, int(n),
                     C.c_void_p(int(d_out)) if d_out else None, C.c_void_p(int(d_found)) if d_found else None)
 
+    # ---- insert of cells that are not stored yet, in place (include/dsa.h: dsa_mat_insert_batch[_dev]; HIP library only) ---------
+    _INSERT_NEEDS = "insert_values and upsert need the HIP product library"
+
+    def insert_values(self, I, J, V, existing="error"):
+        """Creates the cells (I[k], J[k]) with the values V[k] in place on the device, in both orientations: the back end of
+        update_values(..., missing="skip").  The cells must not be stored yet and must be distinct.  Content, nnz and size() end
+        as after set_batch of the same nonzero triples; the LAYOUT is the merged cell sequence spread by the root rebalance (as
+        after delete_columns), with the capacity doubled as often as the merged count needs, never shrunk.  V keeps its bits; a 0.0
+        creates a stored zero (dropzeros() removes it).  New columns / rows must lie behind the last entry of their table, which
+        must be live: one that would land in the middle raises DsaErrorException with code EMODE (use set_batch).  existing="error": a cell that is
+        already stored raises DsaArgumentError and nothing is modified; "skip": such ops are skipped and the call returns their
+        boolean mask.  I, J, V: sequences or numpy arrays, or tensors on the GPU (int64, int64, float64; all three of the same
+        kind), which are used where they are.  An error, an empty batch and a batch that is skipped entirely change nothing and
+        keep the cached SpMV plans."""
+        self._require("mat_insert_batch", self._INSERT_NEEDS)
+        if existing not in ("error", "skip"):
+            raise B.DsaArgumentError(B.EARG, "existing must be 'error' or 'skip'")
+        skip = existing == "skip"
+        flags = INS_SKIP_EXISTING if skip else 0
+        ops = (I, J, V)
+        is_t = [type(x).__module__.split(".")[0] == "torch" for x in ops]
+        if any(is_t):
+            import torch
+            if not all(is_t):
+                raise B.DsaArgumentError(B.EARG, "I, J and V must all be numpy arrays or all be tensors on the GPU")
+            for x, dt in zip(ops, (torch.int64, torch.int64, torch.float64)):
+                if x.dtype != dt or not x.is_cuda or x.dim() != 1 or x.numel() != I.numel():
+                    raise B.DsaArgumentError(B.EARG, "I, J, V must be 1-D int64, int64, float64 tensors of one length on the GPU")
+            i, j, v = (x.contiguous() for x in ops)
+            n = i.numel()
+            mask = torch.zeros(n, dtype=torch.uint8, device=i.device) if skip else None
+            # the library reads the triples on its own two streams: torch's pending work on them must be over first
+            torch.cuda.current_stream(i.device).synchronize()
+            self.insert_values_dev(i.data_ptr(), j.data_ptr(), v.data_ptr(), n, flags, d_existing=mask.data_ptr() if skip and n else None)
+            return mask.bool() if skip else None
+        i, ip = _i64(np.asarray(I, dtype=np.int64).reshape(-1))
+        j, jp = _i64(np.asarray(J, dtype=np.int64).reshape(-1))
+        v, vp = _f64(np.asarray(V, dtype=np.float64).reshape(-1))
+        if not (len(i) == len(j) == len(v)):
+            raise B.DsaArgumentError(B.EARG, "rows, columns, and nonzeros do not have same length.")
+        mask = np.zeros(len(i), dtype=np.uint8)
+        self.b.call("mat_insert_batch", self.h, ip, jp, vp, len(i), flags, mask.ctypes.data_as(P_U8) if skip else None)
+        return mask.astype(bool) if skip else None
+
+    def insert_values_dev(self, d_I, d_J, d_V, n, flags=0, d_existing=None):
+        """insert_values with the triples in HBM (device addresses of n int64, int64, float64 entries, complete at the call); flags
+        0 | INS_SKIP_EXISTING, d_existing: device address of n bytes that receive 1 for an op whose cell is already stored, or
+        None.  Returns with both streams drained."""
+        self._require("mat_insert_batch", self._INSERT_NEEDS)
+        self.b.call("mat_insert_batch_dev", self.h, C.c_void_p(int(d_I)) if d_I else None, C.c_void_p(int(d_J)) if d_J else None,
+                    C.c_void_p(int(d_V)) if d_V else None, int(n), int(flags), C.c_void_p(int(d_existing)) if d_existing else None)
+
+    def upsert(self, I, J, V):
+        """A[I[k], J[k]] = V[k] whether the cell is stored or not, for DISTINCT cells and host arrays: update_values(...,
+        missing="skip"), then insert_values of the ops it reports missing — the general write for nonzero values composed of its
+        two halves (a 0.0 leaves or creates a stored zero).  Returns (updated, inserted)."""
+        self._require("mat_insert_batch", self._INSERT_NEEDS)
+        i = np.asarray(I, dtype=np.int64).reshape(-1)
+        j = np.asarray(J, dtype=np.int64).reshape(-1)
+        v = np.asarray(V, dtype=np.float64).reshape(-1)
+        if not (len(i) == len(j) == len(v)):
+            raise B.DsaArgumentError(B.EARG, "rows, columns, and nonzeros do not have same length.")
+        updated, miss = self.update_values(i, j, v, missing="skip")
+        if miss.any():
+            self.insert_values(i[miss], j[miss], v[miss])
+        return updated, int(miss.sum())
+
 
 def dynamicsparse(I=None, J=None, V=None, m=None, n=None, fill_mode=True,
                   binding: Binding | None = None) -> DynamicSparseMatrix:
@@ -1405,6 +1480,15 @@ def deletecolumns(mat, cols):
 
 def deleterows(mat, rows):
     return mat.delete_rows(rows)
+
+
+def insert_values(mat, I, J, V, existing="error"):
+    """insert_values!(A, I, J, V): cells that are not stored yet created in place (DynamicSparseMatrix.insert_values)"""
+    return mat.insert_values(I, J, V, existing=existing)
+
+
+def upsert(mat, I, J, V):
+    return mat.upsert(I, J, V)
 
 
 def droptol(mat, tol, rows=None, cols=None):

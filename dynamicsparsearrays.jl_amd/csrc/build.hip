@@ -24,6 +24,7 @@
 // stable 64-bit sorts by key then by partition (rocPRIM) carrying the input index.
 // Bound: HBM (sort passes: 40 B per triple and pass).
 #include "wave_dev.h"
+#include "pairsort.h"
 #include <functional>
 
 #include <algorithm>
@@ -908,19 +909,44 @@ void build_abort(BuildScratch& s) {
 
 // ---- general path, host side ----
 // one stable LSD sort of (comp, payload) over `bits` bits with the kernels of the composite path; returns the buffer index of the result
-static hipError_t wide_sort(BuildScratch& s, int& cur, int bits, int64_t nblocks, hipStream_t stream) {
+static_assert(PAIR_SORT_TILE == RS_TILE, "pair_sort_bytes sizes the histogram by the tile of the radix pass");
+static hipError_t wide_sort(const PairSort& w, int64_t n, int& cur, int bits, int64_t nblocks, hipStream_t stream) {
     const size_t lds_bytes = (size_t)RS_TILE * (sizeof(uint64_t) + sizeof(double));
     const dim3 grid((unsigned)nblocks), block(RS_BLOCK);
     const int npass = (bits + 7) / 8;
     for (int pass = 0; pass < npass; ++pass) {
         const int shift = 8 * pass;
-        uint32_t* dtot = s.ghist + pass * RS_BINS;
-        hipLaunchKernelGGL(k_rs_hist, grid, block, 0, stream, (const uint64_t*)s.comp[cur], s.n, shift, s.hist, nblocks);
-        hipLaunchKernelGGL(k_rs_scan, dim3(RS_BINS), block, 0, stream, s.hist, dtot, nblocks);
-        hipLaunchKernelGGL(k_rs_scatter<true>, grid, block, lds_bytes, stream, (const uint64_t*)s.comp[cur], (const double*)s.val[cur], s.n, shift,
-                           (const uint32_t*)s.hist, (const uint32_t*)dtot, s.comp[1 - cur], s.val[1 - cur], nblocks);
+        uint32_t* dtot = w.ghist + pass * RS_BINS;
+        hipLaunchKernelGGL(k_rs_hist, grid, block, 0, stream, (const uint64_t*)w.comp[cur], n, shift, w.hist, nblocks);
+        hipLaunchKernelGGL(k_rs_scan, dim3(RS_BINS), block, 0, stream, w.hist, dtot, nblocks);
+        hipLaunchKernelGGL(k_rs_scatter<true>, grid, block, lds_bytes, stream, (const uint64_t*)w.comp[cur], (const double*)w.pay[cur], n, shift,
+                           (const uint32_t*)w.hist, (const uint32_t*)dtot, w.comp[1 - cur], w.pay[1 - cur], nblocks);
         cur = 1 - cur;
     }
+    return hipGetLastError();
+}
+
+// the two runs and the gather behind them (pairsort.h): what the general path of the builder and the batched insert share
+hipError_t launch_pair_sort(const int64_t* d_part, const int64_t* d_key, int64_t n, int64_t pmin, int pbits, int64_t kmin, int kbits,
+                            const PairSort& w, uint32_t* idx, int64_t* k2, int64_t* p2, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (n < 0 || n > (int64_t)UINT32_MAX || kbits < 0 || kbits > 64 || pbits < 0 || pbits > 64) return hipErrorInvalidValue;
+    const int64_t nblocks = (n + RS_TILE - 1) / RS_TILE;
+    static PerDeviceOnce once;
+    const size_t lds_bytes = (size_t)RS_TILE * (sizeof(uint64_t) + sizeof(double));
+    hipError_t e = once.run([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); });
+    if (e != hipSuccess) return e;
+    const unsigned gs = (unsigned)std::min<int64_t>((n + 255) / 256, 65535 * 4);
+    int cur = 0;
+    hipLaunchKernelGGL(k_wide_key0, dim3(gs), dim3(256), 0, stream, d_key, kmin, w.comp[0], w.pay[0], n);
+    e = wide_sort(w, n, cur, kbits, nblocks, stream);                                                       // by key
+    if (e != hipSuccess) return e;
+    if (d_part != nullptr) {
+        hipLaunchKernelGGL(k_wide_part, dim3(gs), dim3(256), 0, stream, d_part, pmin, (const double*)w.pay[cur], w.comp[cur], n);
+        e = wide_sort(w, n, cur, std::max(pbits, 1), nblocks, stream);                                      // then by partition (stable)
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_wide_finish, dim3(gs), dim3(256), 0, stream, d_part, d_key, (const double*)w.pay[cur], idx, k2, p2, n);
     return hipGetLastError();
 }
 
@@ -944,18 +970,8 @@ static hipError_t prepare_wide(const int64_t* d_part, const int64_t* d_key, int6
     }
     BuildCtl* dctl = static_cast<BuildCtl*>(s.d_ctl);
     BuildCtl* hctl = static_cast<BuildCtl*>(s.h_ctl);
-    static PerDeviceOnce once;
-    const size_t lds_bytes = (size_t)RS_TILE * (sizeof(uint64_t) + sizeof(double));
-    BCHK(once.run([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }));
-    const unsigned gs = (unsigned)std::min<int64_t>((nnz + 255) / 256, 65535 * 4);
-    int cur = 0;
-    hipLaunchKernelGGL(k_wide_key0, dim3(gs), dim3(256), 0, stream, d_key, kmin, s.comp[0], s.val[0], nnz);
-    BCHK(wide_sort(s, cur, kbits, nblocks, stream));                                                        // by key
-    if (d_part != nullptr) {
-        hipLaunchKernelGGL(k_wide_part, dim3(gs), dim3(256), 0, stream, d_part, pmin, (const double*)s.val[cur], s.comp[cur], nnz);
-        BCHK(wide_sort(s, cur, std::max(pbits, 1), nblocks, stream));                                       // then by partition (stable)
-    }
-    hipLaunchKernelGGL(k_wide_finish, dim3(gs), dim3(256), 0, stream, d_part, d_key, (const double*)s.val[cur], s.idx2, s.k2, s.p2, nnz);
+    const PairSort w{{s.comp[0], s.comp[1]}, {s.val[0], s.val[1]}, s.hist, s.ghist};
+    BCHK(launch_pair_sort(d_part, d_key, nnz, pmin, pbits, kmin, kbits, w, s.idx2, s.k2, s.p2, stream));
     const unsigned blocks = (unsigned)((nnz + 255) / 256);
     hipLaunchKernelGGL(k_flags, dim3(blocks), dim3(256), 0, stream, d_part != nullptr ? (const int64_t*)s.p2 : (const int64_t*)nullptr, s.k2, s.fpart, s.fcell, nnz);
     hipLaunchKernelGGL(k_flag_tile_sums, dim3((unsigned)nblocks), dim3(RS_BLOCK), 0, stream, (const uint32_t*)s.fpart, (const uint32_t*)s.fcell, nnz, s.cnt_c, s.cnt_p);

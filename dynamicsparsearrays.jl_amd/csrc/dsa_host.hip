@@ -1114,6 +1114,39 @@ int32_t dsa_mat_get_batch_dev(dsa_mat_t* h, const int64_t* d_I, const int64_t* d
     API_CATCH
 }
 
+// ---- insert of cells that are not stored yet (insert.hip).  Scan, sort, locate and verdict are in front of the epoch bump: an error
+// and a call that inserts nothing leave layouts and cached plans as they were
+namespace {
+void mat_insert_batch(dsa_mat_t* h, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int32_t flags, uint8_t* d_existing) {
+    const InsertCounts c = insert_prepare(h, d_I, d_J, d_V, n, flags, d_existing);
+    if (c.ops > 0) {
+        mat_content_changed(h);
+        insert_apply(h, c, d_V, n);
+        mat_prefetch_spmv_meta(h);
+    }
+}
+}  // namespace
+int32_t dsa_mat_insert_batch_dev(dsa_mat_t* h, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int32_t flags,
+                                 uint8_t* d_existing) {
+    API_TRY
+    mat_insert_batch(h, d_I, d_J, d_V, n, flags, d_existing);
+    if (n > 0 && h->has_major) { HIPCHK(hipStreamSynchronize(h->col.stream)); HIPCHK(hipStreamSynchronize(h->row.stream)); }
+    API_CATCH
+}
+int32_t dsa_mat_insert_batch(dsa_mat_t* h, const int64_t* I, const int64_t* J, const double* V, int64_t n, int32_t flags, uint8_t* existing) {
+    API_TRY
+    InsertStaging st(h, I, J, V, n, flags, existing != nullptr);      // flush, DSA_EMODE / DSA_EARG, the triples in HBM until both streams have drained
+    if (n > 0) {
+        uint8_t* d_existing = static_cast<uint8_t*>(st.b.p[3]);
+        mat_insert_batch(h, static_cast<const int64_t*>(st.b.p[0]), static_cast<const int64_t*>(st.b.p[1]), static_cast<const double*>(st.b.p[2]), n,
+                         flags, d_existing);
+        if (existing) HIPCHK(hipMemcpyAsync(existing, d_existing, (size_t)n, hipMemcpyDeviceToHost, h->col.stream));
+        HIPCHK(hipStreamSynchronize(h->col.stream));
+        HIPCHK(hipStreamSynchronize(h->row.stream));
+    }
+    API_CATCH
+}
+
 int32_t dsa_mat_check(dsa_mat_t* h, int32_t o, int64_t* report) { API_TRY mat_flush(h); pma_check(orient(h, o), report); API_CATCH }
 int32_t dsa_mat_set_stream(dsa_mat_t* h, void* s) {
     API_TRY

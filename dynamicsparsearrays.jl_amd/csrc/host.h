@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, fill_host.hip, matwrite_host.hip, pma_host.hip,
-// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
+// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, insert_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -169,6 +169,9 @@ struct Pma {
     // pinned words of the one hand-over (colmajor); the event that orders the two streams of a call
     ExportArea upd;
     hipEvent_t ev_upd = nullptr;
+    // insert_batch (insert.hip): the sorted ops, their predecessor slots, item counts and prefixes, the tile counts of the array; the
+    // pinned words of the orientation's hand-over
+    ExportArea ins;
     // combine (combine.hip): the tile arrays, range words and last-semaphore ids of a pass over this orientation; the pinned words of
     // the two roles an operand can have (2 x {error word, four range words, sequence number})
     ExportArea cmb;
@@ -410,6 +413,21 @@ struct UpdateStaging {
     dsa_mat* h; DevStaging b;
     UpdateStaging(dsa_mat* h, int32_t op, int32_t flags, const int64_t* I, const int64_t* J, const double* V, int64_t n, bool want_missing);
     ~UpdateStaging();
+};
+
+// ---- insert_host.hip: cells that are not stored yet created in both orientations from triples in HBM (d_* are device arrays).  Two
+// steps so that the entry point can bump the content epoch between them: insert_prepare (flush, checks, the key scan, then sort +
+// locate + verdict over both orientations: DSA_EMODE / DSA_EARG / DSA_EKEY / DSA_EASSERT with nothing modified; returns what the merge
+// adds, ops == 0 when there is nothing to insert) and insert_apply (capacity, tables, the merge of both orientations, control blocks
+// uploaded, both streams drained).  InsertStaging holds triples that came from host memory (p[0..2]; p[3]: the existing flags) in HBM
+// until both streams have drained.
+struct InsertCounts { int64_t ops = 0, existing = 0, items[2] = {0, 0}, parts[2] = {0, 0}; KeyRange rows, cols; };
+InsertCounts insert_prepare(dsa_mat* h, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int32_t flags, uint8_t* d_existing);
+void insert_apply(dsa_mat* h, const InsertCounts& c, const double* d_V, int64_t n);
+struct InsertStaging {
+    dsa_mat* h; DevStaging b;
+    InsertStaging(dsa_mat* h, const int64_t* I, const int64_t* J, const double* V, int64_t n, int32_t flags, bool want_existing);
+    ~InsertStaging();
 };
 
 // Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks

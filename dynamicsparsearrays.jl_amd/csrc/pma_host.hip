@@ -72,6 +72,7 @@ void pma_destroy(Pma& P) {
     P.del.release();
     P.drp.release();
     P.upd.release();
+    P.ins.release();
     if (P.ev_upd) (void)hipEventDestroy(P.ev_upd);
     P.cmb.release();
     P.spg.release();

@@ -36,6 +36,8 @@ const droptol! = DynamicSparseArraysAMD.droptol!                  # droptol!(A, 
 const count_droptol = DynamicSparseArraysAMD.count_droptol
 const update_values! = DynamicSparseArraysAMD.update_values!      # values of stored cells overwritten / added to in place (dsa_mat_update_values)
 const add_values! = DynamicSparseArraysAMD.add_values!
+const insert_values! = DynamicSparseArraysAMD.insert_values!      # cells that are not stored yet created in place (dsa_mat_insert_batch)
+const upsert! = DynamicSparseArraysAMD.upsert!                    # update_values! of the stored cells, insert_values! of the others
 const getstored = DynamicSparseArraysAMD.getstored                # getindex_batch with every operand in HBM (dsa_mat_get_batch_dev)
 
 end # module

@@ -26,7 +26,7 @@ export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
        keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev,
        scale!, reduce_rows, reduce_cols, mul_rows, mul_cols, mul_sparse, dropzeros!, droptol!, count_droptol,
-       update_values!, add_values!, getstored
+       update_values!, add_values!, getstored, insert_values!, upsert!
 
 const libdsa = get(ENV, "DSA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libdsa_hip.so"))
 
@@ -754,6 +754,28 @@ update_values!(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector, V::
     _update_values(a, Int32(0), I, J, V, skip_missing)          # DSA_UPD_SET
 add_values!(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector, V::AbstractVector; skip_missing::Bool = false) =
     _update_values(a, Int32(1), I, J, V, skip_missing)          # DSA_UPD_ADD
+# Cells that are NOT STORED yet, created in place on the device in both orientations (include/dsa.h: dsa_mat_insert_batch): the back end
+# of update_values!(...; skip_missing = true).  Content, nnz and size end as after setindex_batch! of the same nonzero triples; the layout
+# is the merged cell sequence spread by the root rebalance, the capacity doubled as often as the merged count needs.  A zero creates a
+# STORED zero (dropzeros! removes it).  New columns / rows must lie behind the last entry of their table, which must be live; one in the
+# middle is an error (use setindex_batch!).  skip_existing = false: a cell that is already stored is an ArgumentError and nothing is
+# modified; true: such ops are skipped.  Returns the mask of the skipped ops.
+function insert_values!(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector, V::AbstractVector; skip_existing::Bool = false)
+    Ii = _in(a.rows, I); Ji = _in(a.cols, J); Vf = Vector{Float64}(V)
+    length(Ii) == length(Ji) == length(Vf) || throw(ArgumentError("rows, columns, and nonzeros do not have same length."))
+    existing_mask = zeros(UInt8, length(Ii))
+    GC.@preserve Ii Ji Vf existing_mask _check(ccall((:dsa_mat_insert_batch, libdsa), Int32,
+        (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Int32, Ptr{UInt8}),
+        a.h, Ii, Ji, Vf, length(Ii), Int32(skip_existing), existing_mask))      # DSA_INS_SKIP_EXISTING
+    return existing_mask .!= 0
+end
+# A[I[k], J[k]] = V[k] whether the cell is stored or not, for distinct cells: update_values! with skip_missing, then insert_values! of
+# the ops it reports missing.  Host arrays only.  Returns (cells updated, cells inserted).
+function upsert!(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector, V::AbstractVector)
+    updated, miss = update_values!(a, I, J, V; skip_missing = true)
+    any(miss) && insert_values!(a, I[miss], J[miss], V[miss])
+    return updated, count(miss)
+end
 "n getindex calls with every operand in HBM (device pointers; mapped key integers): d_out[k] = A[d_I[k], d_J[k]], d_found[k] (n bytes, or
 C_NULL) = 1 iff the cell is stored, which tells a stored zero from an absent cell; enqueued on the colmajor stream, no host wait —
 dsa_mat_get_batch_dev"

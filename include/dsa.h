@@ -532,6 +532,37 @@ int32_t dsa_mat_update_values(dsa_mat_t* h, int32_t op, int32_t flags, const int
  * dsa_mat_sync); the host does not wait.  A key of 0 reads as absent.  DSA_EMODE in fill mode; DSA_EARG for n < 0 or a NULL operand
  * with n > 0.  Queued single writes are applied first. */
 int32_t dsa_mat_get_batch_dev(dsa_mat_t* h, const int64_t* d_I, const int64_t* d_J, int64_t n, double* d_out, uint8_t* d_found);
+/* Insert of cells that are NOT STORED yet, in place (csrc/insert.hip): cell (I[k], J[k]) is created with the value V[k], for n
+ * triples, in both orientations — the back end of dsa_mat_update_values' DSA_UPD_SKIP_MISSING.  No reference counterpart as a bulk
+ * call.  Afterwards the content, the partition tables as a key -> cells map, nnz and size(m) are those of dsa_mat_set_batch(I, J, V)
+ * with the same nonzero triples; V[k] is stored bit for bit (NaN payloads, -0.0), and V[k] == 0.0 creates a STORED zero, as
+ * dsa_mat_update_values leaves them: it counts in nnz, raises size(m) like any stored cell, and dsa_mat_droptol removes it.
+ * LAYOUT: not the one the writes one after the other leave.  Per orientation the merged cell sequence — old cells and semaphores, new
+ * cells, the semaphores of the new partitions, in key order — is spread over [1, capacity] the way dsa_mat_rebalance_root spreads it,
+ * as the batched delete does.  The capacity is the current one doubled the fewest times (possibly none) that lets the merged count
+ * fit the root's upper density bound; each doubling changes the geometry as the reference's _extend! does (src/pma.jl:143-151:
+ * capacity and segments doubled, one more level, the segment size kept).  The call never shrinks.
+ * WHERE a new cell may go: into any live partition (in front of its first cell, between two, behind its last), or into a NEW
+ * partition whose key is greater than the key of the last table entry, which must be live (an empty table takes any keys).  New
+ * partitions get the ids table_len + 1 ... in key order.  Tombstones elsewhere in the table stay.  A new partition that would land in
+ * the middle of the table is DSA_EMODE ("use set_batch"): it would shift ids, and the reference can refuse it.
+ * Every error is found before the first write — both orientations, the tables, every epoch and the cached SpMV plans stay as they
+ * were: DSA_EMODE in fill mode or for a partition in the middle; DSA_EKEY: an I[k] or J[k] below 1; DSA_EARG: unknown flags, n < 0,
+ * an operand NULL with n > 0, n or a capacity of 2^31 or more, the same cell twice in the batch (dsa_last_error names the later
+ * op), a cell that is already stored (names the op); DSA_EASSERT: the orientations disagree about the stored ops, or a live table
+ * entry without a semaphore.  With DSA_INS_SKIP_EXISTING in flags a stored cell is skipped instead: existing[k] (may be NULL) receives
+ * 1 for it and 0 for an inserted op (unspecified after an error).  n = 0, or every op skipped, changes nothing: no rebalance, no
+ * epoch, plans survive.  Otherwise content and layout epochs move once and the plans are dropped once.  A key beyond Int32 widens
+ * the orientation's keys first.  Queued single writes are applied first.  The number of launches and of host waits does not depend
+ * on n.
+ * _dev: d_I / d_J / d_V (and d_existing) are device arrays, read on BOTH orientations' streams: they must hold their final contents
+ * when the call is made and stay valid and unchanged until it returns (it returns with both streams drained).  The host form stages
+ * the triples through pooled device memory. */
+enum { DSA_INS_SKIP_EXISTING = 1 };
+int32_t dsa_mat_insert_batch_dev(dsa_mat_t* h, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int32_t flags,
+                                 uint8_t* d_existing);
+int32_t dsa_mat_insert_batch(dsa_mat_t* h, const int64_t* I, const int64_t* J, const double* V, int64_t n, int32_t flags,
+                             uint8_t* existing);
 /* ---- column-range shards. No reference counterpart: the reference is single-process.  One PROCESS per GPU:
  * each process selects its device (dsa_set_device), builds ITS shard and runs the local SpMV; the single data-path collective —
  * the all-reduce (sum) of the partial y — is dsa_shard_allreduce_dev below (RCCL behind this ABI), or whatever the host layer has

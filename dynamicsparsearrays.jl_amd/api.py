@@ -32,6 +32,82 @@ def _bind(b):
     return b if b is not None else B.product()
 
 
+def _dptr(x):
+    """a device address as a C argument: 0 and None are NULL"""
+    return C.c_void_p(int(x)) if x else None
+
+
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _factor_pair(rows, cols):
+    """A (rows, cols) factor pair, None = absent, in the form the library takes it: (True, (d_r, nr, d_c, nc), keep) for float64
+    tensors on the GPU (device addresses of contiguous tensors, 0 = absent; torch's current stream synchronised), else
+    (False, (r, nr, c, nc), keep) with pointers to float64 host arrays.  `keep` holds what the addresses point into."""
+    ops = [x for x in (rows, cols) if x is not None]
+    is_t = [_is_tensor(x) for x in ops]
+    if any(is_t):
+        import torch
+        if not all(is_t):
+            raise B.DsaArgumentError(B.EARG, "rows and cols must both be numpy arrays or both be tensors on the GPU")
+        for x in ops:
+            if x.dtype != torch.float64 or not x.is_cuda or x.dim() != 1:
+                raise B.DsaArgumentError(B.EARG, "rows and cols must be 1-D float64 tensors on the GPU")
+        keep = [None if x is None else x.contiguous() for x in (rows, cols)]
+        # the library reads the factors on its own two streams: torch's pending work on them must be over first, and they must
+        # stay as they are until the call has finished
+        torch.cuda.current_stream(ops[0].device).synchronize()
+        (r, nr), (c, nc) = ((0, 0) if x is None else (x.data_ptr(), x.numel()) for x in keep)
+        return True, (r, nr, c, nc), keep
+    keep = [np.zeros(1, dtype=np.float64)]
+    args = []
+    for x in (rows, cols):
+        a, p = (None, None) if x is None else _f64(np.asarray(x, dtype=np.float64))
+        # a factor of length 0 is still "given": a non-NULL pointer that is never read
+        if a is not None and len(a) == 0:
+            p = keep[0].ctypes.data_as(P_F64)
+        keep.append(a)
+        args += [p, 0 if a is None else len(a)]
+    return False, tuple(args), keep
+
+
+def _host_triple(I, J, V):
+    """(I, J, V) as flat contiguous int64, int64, float64 arrays of one length"""
+    i, j = (_i64(np.asarray(x, dtype=np.int64).reshape(-1))[0] for x in (I, J))
+    v = _f64(np.asarray(V, dtype=np.float64).reshape(-1))[0]
+    if not (len(i) == len(j) == len(v)):
+        raise B.DsaArgumentError(B.EARG, "rows, columns, and nonzeros do not have same length.")
+    return i, j, v
+
+
+def _triple(I, J, V, want_mask):
+    """An (I, J, V) triple in the form the library takes it, with a uint8 mask of one byte per op if one is wanted:
+    (True, (d_I, d_J, d_V, n, d_mask), mask, keep) for int64, int64, float64 tensors on the GPU (device addresses of contiguous
+    tensors; torch's current stream synchronised), else (False, (I, J, V, n, mask), mask, keep) with pointers to host arrays.
+    An absent mask, and the device mask of an empty batch, is None.  `keep` holds what the addresses point into."""
+    ops = (I, J, V)
+    is_t = [_is_tensor(x) for x in ops]
+    if any(is_t):
+        import torch
+        if not all(is_t):
+            raise B.DsaArgumentError(B.EARG, "I, J and V must all be numpy arrays or all be tensors on the GPU")
+        for x, dt in zip(ops, (torch.int64, torch.int64, torch.float64)):
+            if x.dtype != dt or not x.is_cuda or x.dim() != 1 or x.numel() != I.numel():
+                raise B.DsaArgumentError(B.EARG, "I, J, V must be 1-D int64, int64, float64 tensors of one length on the GPU")
+        keep = [x.contiguous() for x in ops]
+        n = keep[0].numel()
+        mask = torch.zeros(n, dtype=torch.uint8, device=keep[0].device) if want_mask else None
+        # the library reads the triples on its own two streams: torch's pending work on them must be over first, and they must
+        # stay as they are until the call has finished
+        torch.cuda.current_stream(keep[0].device).synchronize()
+        return True, (*(x.data_ptr() for x in keep), n, mask.data_ptr() if want_mask and n else None), mask, keep
+    i, j, v = keep = _host_triple(I, J, V)
+    mask = np.zeros(len(i), dtype=np.uint8) if want_mask else None
+    return False, (i.ctypes.data_as(P_I64), j.ctypes.data_as(P_I64), v.ctypes.data_as(P_F64), len(i),
+                   mask.ctypes.data_as(P_U8) if want_mask else None), mask, keep
+
+
 class _Handle:
     _destroy = None
 
@@ -408,7 +484,7 @@ class DynamicSparseMatrix(_Handle):
         """the view delivered into HBM: d_keys / d_vals are device addresses (int64 / float64 arrays of cap entries, e.g.
         tensor.data_ptr()); returns the number of cells; the copy is enqueued on the orientation's stream (sync())"""
         n = C.c_int64()
-        self.b.call(name, self.h, int(key), C.c_void_p(int(d_keys)), C.c_void_p(int(d_vals)), int(cap), C.byref(n))
+        self.b.call(name, self.h, int(key), _dptr(d_keys), _dptr(d_vals), int(cap), C.byref(n))
         return n.value
 
     def sync(self):                                   # dsa_mat_sync: everything enqueued on the handle's streams has finished
@@ -583,8 +659,8 @@ class DynamicSparseMatrix(_Handle):
         (sync()); returns nnz"""
         self._require("mat_to_compressed", "compressed export needs the HIP product library")
         got = C.c_int64()
-        self.b.call("mat_to_compressed_dev", self.h, int(orientation), int(index_bits), int(base), C.c_void_p(int(d_ptr)),
-                    C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)), int(cap), C.byref(got))
+        self.b.call("mat_to_compressed_dev", self.h, int(orientation), int(index_bits), int(base), _dptr(d_ptr),
+                    _dptr(d_idx), _dptr(d_vals), int(cap), C.byref(got))
         return got.value
 
     def to_torch(self, layout, index_dtype=None):
@@ -605,8 +681,8 @@ class DynamicSparseMatrix(_Handle):
         0 for idx / vals with cap = 0: the count-only call).  Enqueued on the orientation's stream (sync()).  Returns (total, fits):
         the number of selected cells and whether they were delivered; with fits False (cap < total) only ptr has been written."""
         self._require("mat_select_compressed", "the selected export needs the HIP product library")
-        return self._fits("mat_select_compressed_dev", int(orientation), int(index_bits), int(base), C.c_void_p(int(d_sel)), int(nsel),
-                          C.c_void_p(int(d_ptr)), C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)), int(cap))
+        return self._fits("mat_select_compressed_dev", int(orientation), int(index_bits), int(base), _dptr(d_sel), int(nsel),
+                          _dptr(d_ptr), _dptr(d_idx), _dptr(d_vals), int(cap))
 
     def _select(self, orientation, keys, base, count_only=False):
         self._require("mat_select_compressed", "the selected export needs the HIP product library")
@@ -652,8 +728,8 @@ class DynamicSparseMatrix(_Handle):
         cap = 0: the count-only call).  A delivered cell's index is the position of its key in the inner list + base.  Enqueued on the
         orientation's stream (sync()).  Returns (total, fits) like select_compressed_dev."""
         self._require("mat_submatrix_compressed", "the submatrix export needs the HIP product library")
-        return self._fits("mat_submatrix_compressed_dev", int(orientation), int(index_bits), int(base), C.c_void_p(int(d_outer)), int(nouter),
-                          C.c_void_p(int(d_inner)), int(ninner), C.c_void_p(int(d_ptr)), C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)),
+        return self._fits("mat_submatrix_compressed_dev", int(orientation), int(index_bits), int(base), _dptr(d_outer), int(nouter),
+                          _dptr(d_inner), int(ninner), _dptr(d_ptr), _dptr(d_idx), _dptr(d_vals),
                           int(cap))
 
     @staticmethod
@@ -802,8 +878,8 @@ class DynamicSparseMatrix(_Handle):
 
     def mul_dev(self, d_xi, d_xv, nx, d_yi, d_yv, cap, d_count, transpose=False):
         """the sparse product with every operand in HBM (device addresses, e.g. tensor.data_ptr()); stream-ordered, no host wait"""
-        self.b.call("mat_spmv_sparse_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_xi)), C.c_void_p(int(d_xv)), int(nx),
-                    C.c_void_p(int(d_yi)), C.c_void_p(int(d_yv)), int(cap), C.c_void_p(int(d_count)))
+        self.b.call("mat_spmv_sparse_dev", self.h, 1 if transpose else 0, _dptr(d_xi), _dptr(d_xv), int(nx),
+                    _dptr(d_yi), _dptr(d_yv), int(cap), _dptr(d_count))
 
     # ---- dense multi-vector product (include/dsa.h: dsa_mat_spmm_dense[_dev]; HIP library only) ------------------------------------
     def matmul(self, X, transpose=False):
@@ -853,8 +929,8 @@ class DynamicSparseMatrix(_Handle):
         """the multi-vector product with both operands in HBM (device addresses, e.g. tensor.data_ptr()), row-major with leading
         dimensions ldx / ldy (default k); stream-ordered on the orientation's stream, no host wait (sync())"""
         self._require("mat_spmm_dense", "the multi-vector product needs the HIP product library")
-        self.b.call("mat_spmm_dense_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_x)), int(nx), int(k),
-                    int(k if ldx is None else ldx), C.c_void_p(int(d_y)), int(ny), int(k if ldy is None else ldy))
+        self.b.call("mat_spmm_dense_dev", self.h, 1 if transpose else 0, _dptr(d_x), int(nx), int(k),
+                    int(k if ldx is None else ldx), _dptr(d_y), int(ny), int(k if ldy is None else ldy))
 
     # ---- selected-key product (include/dsa.h: dsa_mat_spmm_selected[_dev]; HIP library only) -------------------------------------
     def matmul_selected(self, keys, X, transpose=False):
@@ -912,8 +988,8 @@ class DynamicSparseMatrix(_Handle):
         Y row-major with leading dimensions ldx / ldy (default k); stream-ordered on the orientation's stream, no host wait (sync()).
         A key without a row / column (0 and negative keys included) gives a zero row: nothing is reported."""
         self._require("mat_spmm_selected", "the selected-key product needs the HIP product library")
-        self.b.call("mat_spmm_selected_dev", self.h, 1 if transpose else 0, C.c_void_p(int(d_sel)), int(nsel), C.c_void_p(int(d_x)),
-                    int(nx), int(k), int(k if ldx is None else ldx), C.c_void_p(int(d_y)), int(k if ldy is None else ldy))
+        self.b.call("mat_spmm_selected_dev", self.h, 1 if transpose else 0, _dptr(d_sel), int(nsel), _dptr(d_x),
+                    int(nx), int(k), int(k if ldx is None else ldx), _dptr(d_y), int(k if ldy is None else ldy))
 
     # ---- batched sparse-x product (include/dsa.h: dsa_mat_spgemm_csc[_dev]; HIP library only) ---------------------------------------
     def _require_spgemm(self):
@@ -926,9 +1002,9 @@ class DynamicSparseMatrix(_Handle):
         is mul() of column j of S, bit for bit.  Enqueued on the stream of the orientation that is walked (sync()).  Returns
         (total, fits) like select_compressed_dev: with fits False (cap < total) only yptr has been written."""
         self._require_spgemm()
-        return self._fits("mat_spgemm_csc_dev", 1 if transpose else 0, int(index_bits), int(base), C.c_void_p(int(d_xptr)),
-                          C.c_void_p(int(d_xidx)), C.c_void_p(int(d_xval)), int(k), int(nnzx), C.c_void_p(int(d_yptr)),
-                          C.c_void_p(int(d_yidx)), C.c_void_p(int(d_yval)), int(cap))
+        return self._fits("mat_spgemm_csc_dev", 1 if transpose else 0, int(index_bits), int(base), _dptr(d_xptr),
+                          _dptr(d_xidx), _dptr(d_xval), int(k), int(nnzx), _dptr(d_yptr),
+                          _dptr(d_yidx), _dptr(d_yval), int(cap))
 
     def matmul_sparse(self, S, transpose=False, base=0):
         """mat * S / transpose(mat) * S for a sparse S with k columns: column j of the result is mul() of column j of S (the touched
@@ -1035,7 +1111,7 @@ class DynamicSparseMatrix(_Handle):
     def reduce_dev(self, kind, per, d_out, n):
         """reduce with the result in HBM (device address of n doubles); stream-ordered on the orientation's stream (sync())"""
         k, o = self._reduce_args(kind, per)
-        self.b.call("mat_reduce_dev", self.h, o, k, C.c_void_p(int(d_out)), int(n))
+        self.b.call("mat_reduce_dev", self.h, o, k, _dptr(d_out), int(n))
 
     def _norms(self, p, per):
         if p == 1:
@@ -1058,46 +1134,25 @@ class DynamicSparseMatrix(_Handle):
         Structure is preserved: a zero factor leaves stored zeros (nnz unchanged).  rows / cols: numpy arrays (or sequences), or
         float64 tensors on the GPU (any stride; made contiguous first) — both of the same kind; None = factor absent."""
         self._require("mat_reduce", "reduce and scale need the HIP product library")
-        ops = [x for x in (rows, cols) if x is not None]
-        is_t = [type(x).__module__.split(".")[0] == "torch" for x in ops]
-        if any(is_t):
-            import torch
-            if not all(is_t):
-                raise B.DsaArgumentError(B.EARG, "rows and cols must both be numpy arrays or both be tensors on the GPU")
-            for x in ops:
-                if x.dtype != torch.float64 or not x.is_cuda or x.dim() != 1:
-                    raise B.DsaArgumentError(B.EARG, "rows and cols must be 1-D float64 tensors on the GPU")
-            r = None if rows is None else rows.contiguous()
-            c = None if cols is None else cols.contiguous()
-            # the library reads the factors on its own two streams: torch's pending work on them must be over first, and they must
-            # stay as they are until the scale has finished
-            torch.cuda.current_stream(ops[0].device).synchronize()
-            self.scale_dev(alpha, 0 if r is None else r.data_ptr(), 0 if r is None else r.numel(),
-                           0 if c is None else c.data_ptr(), 0 if c is None else c.numel())
+        dev, (r, nr, c, nc), _keep = _factor_pair(rows, cols)
+        if dev:
+            self.scale_dev(alpha, r, nr, c, nc)
             self.sync()
-            return self
-        rr, rp = (None, None) if rows is None else _f64(np.asarray(rows, dtype=np.float64))
-        cc, cp = (None, None) if cols is None else _f64(np.asarray(cols, dtype=np.float64))
-        # a factor of length 0 is still "given": a non-NULL pointer that is never read
-        dummy = np.zeros(1, dtype=np.float64)
-        if rr is not None and len(rr) == 0:
-            rp = dummy.ctypes.data_as(P_F64)
-        if cc is not None and len(cc) == 0:
-            cp = dummy.ctypes.data_as(P_F64)
-        self.b.call("mat_scale", self.h, float(alpha), rp, 0 if rr is None else len(rr), cp, 0 if cc is None else len(cc))
+        else:
+            self.b.call("mat_scale", self.h, float(alpha), r, nr, c, nc)
         return self
 
     def scale_dev(self, alpha, d_r, nr, d_c, nc):
         """scale with the factors in HBM (device addresses, 0 = factor absent): they are read on both orientations' streams and
         must stay valid and unchanged until sync()"""
         self._require("mat_reduce", "reduce and scale need the HIP product library")
-        self.b.call("mat_scale_dev", self.h, float(alpha), C.c_void_p(int(d_r)) if d_r else None, int(nr),
-                    C.c_void_p(int(d_c)) if d_c else None, int(nc))
+        self.b.call("mat_scale_dev", self.h, float(alpha), _dptr(d_r), int(nr),
+                    _dptr(d_c), int(nc))
 
     # ---- batched delete (include/dsa.h: dsa_mat_delete_batch[_dev]; HIP library only) --------------------------------------------
     def _delete_batch(self, orientation, keys):
         self._require("mat_delete_batch", "the batched delete needs the HIP product library")
-        if type(keys).__module__.split(".")[0] == "torch":
+        if _is_tensor(keys):
             import torch
             if keys.dtype != torch.int64 or keys.dim() != 1:
                 raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 tensor")
@@ -1128,41 +1183,19 @@ class DynamicSparseMatrix(_Handle):
         columns, ROWMAJOR rows; returns the number of entries removed"""
         self._require("mat_delete_batch", "the batched delete needs the HIP product library")
         got = C.c_int64()
-        self.b.call("mat_delete_batch_dev", self.h, int(orientation), C.c_void_p(int(d_keys)) if d_keys else None, int(n), C.byref(got))
+        self.b.call("mat_delete_batch_dev", self.h, int(orientation), _dptr(d_keys), int(n), C.byref(got))
         return got.value
 
     # ---- dropzeros! / droptol! (include/dsa.h: dsa_mat_droptol[_dev]; HIP library only) -------------------------------------------
     def _droptol(self, tol, rows, cols, count_only):
         self._require("mat_droptol", "dropzeros and droptol need the HIP product library")
-        ops = [x for x in (rows, cols) if x is not None]
-        is_t = [type(x).__module__.split(".")[0] == "torch" for x in ops]
-        if any(is_t):
-            import torch
-            if not all(is_t):
-                raise B.DsaArgumentError(B.EARG, "rows and cols must both be numpy arrays or both be tensors on the GPU")
-            for x in ops:
-                if x.dtype != torch.float64 or not x.is_cuda or x.dim() != 1:
-                    raise B.DsaArgumentError(B.EARG, "rows and cols must be 1-D float64 tensors on the GPU")
-            r = None if rows is None else rows.contiguous()
-            c = None if cols is None else cols.contiguous()
-            # the library reads the thresholds on its own two streams: torch's pending work on them must be over first, and they
-            # must stay as they are until the call has finished
-            torch.cuda.current_stream(ops[0].device).synchronize()
-            got = self.droptol_dev(tol, 0 if r is None else r.data_ptr(), 0 if r is None else r.numel(),
-                                   0 if c is None else c.data_ptr(), 0 if c is None else c.numel(), count_only=count_only)
+        dev, (r, nr, c, nc), _keep = _factor_pair(rows, cols)
+        if dev:
+            got = self.droptol_dev(tol, r, nr, c, nc, count_only=count_only)
             self.sync()
             return got
-        rr, rp = (None, None) if rows is None else _f64(np.asarray(rows, dtype=np.float64))
-        cc, cp = (None, None) if cols is None else _f64(np.asarray(cols, dtype=np.float64))
-        # a vector of length 0 is still "given": a non-NULL pointer that is never read
-        dummy = np.zeros(1, dtype=np.float64)
-        if rr is not None and len(rr) == 0:
-            rp = dummy.ctypes.data_as(P_F64)
-        if cc is not None and len(cc) == 0:
-            cp = dummy.ctypes.data_as(P_F64)
         got = C.c_int64()
-        self.b.call("mat_droptol", self.h, float(tol), rp, 0 if rr is None else len(rr), cp, 0 if cc is None else len(cc),
-                    1 if count_only else 0, C.byref(got))
+        self.b.call("mat_droptol", self.h, float(tol), r, nr, c, nc, 1 if count_only else 0, C.byref(got))
         return got.value
 
     def droptol(self, tol, rows=None, cols=None):
@@ -1188,8 +1221,8 @@ class DynamicSparseMatrix(_Handle):
         streams and must be complete at the call; returns the number of entries dropped (count_only: that would be dropped)"""
         self._require("mat_droptol", "dropzeros and droptol need the HIP product library")
         got = C.c_int64()
-        self.b.call("mat_droptol_dev", self.h, float(tol), C.c_void_p(int(d_r)) if d_r else None, int(nr),
-                    C.c_void_p(int(d_c)) if d_c else None, int(nc), 1 if count_only else 0, C.byref(got))
+        self.b.call("mat_droptol_dev", self.h, float(tol), _dptr(d_r), int(nr),
+                    _dptr(d_c), int(nc), 1 if count_only else 0, C.byref(got))
         return got.value
 
     # ---- update of stored values in place (include/dsa.h: dsa_mat_update_values[_dev], dsa_mat_get_batch_dev; HIP library only) ---
@@ -1217,34 +1250,13 @@ class DynamicSparseMatrix(_Handle):
             raise B.DsaArgumentError(B.EARG, "missing must be 'error' or 'skip'")
         skip = missing == "skip"
         flags = UPD_SKIP_MISSING if skip else 0
-        ops = (I, J, V)
-        is_t = [type(x).__module__.split(".")[0] == "torch" for x in ops]
-        if any(is_t):
-            import torch
-            if not all(is_t):
-                raise B.DsaArgumentError(B.EARG, "I, J and V must all be numpy arrays or all be tensors on the GPU")
-            for x, dt in zip(ops, (torch.int64, torch.int64, torch.float64)):
-                if x.dtype != dt or not x.is_cuda or x.dim() != 1 or x.numel() != I.numel():
-                    raise B.DsaArgumentError(B.EARG, "I, J, V must be 1-D int64, int64, float64 tensors of one length on the GPU")
-            i, j, v = (x.contiguous() for x in ops)
-            n = i.numel()
-            mask = torch.zeros(n, dtype=torch.uint8, device=i.device) if skip else None
-            # the library reads the triples on its own two streams: torch's pending work on them must be over first, and they must
-            # stay as they are until the stores have finished
-            torch.cuda.current_stream(i.device).synchronize()
-            updated, _ = self.update_values_dev(i.data_ptr(), j.data_ptr(), v.data_ptr(), n, opc, flags,
-                                                d_missing=mask.data_ptr() if skip and n else None)
+        dev, (i, j, v, n, mp), mask, _keep = _triple(I, J, V, skip)
+        if dev:
+            updated, _ = self.update_values_dev(i, j, v, n, opc, flags, d_missing=mp)
             self.sync()
             return (updated, mask.bool()) if skip else updated
-        i, ip = _i64(np.asarray(I, dtype=np.int64).reshape(-1))
-        j, jp = _i64(np.asarray(J, dtype=np.int64).reshape(-1))
-        v, vp = _f64(np.asarray(V, dtype=np.float64).reshape(-1))
-        if not (len(i) == len(j) == len(v)):
-            raise B.DsaArgumentError(B.EARG, "rows, columns, and nonzeros do not have same length.")
-        mask = np.zeros(len(i), dtype=np.uint8)
         upd, mis = C.c_int64(), C.c_int64()
-        self.b.call("mat_update_values", self.h, opc, flags, ip, jp, vp, len(i), mask.ctypes.data_as(P_U8) if skip else None,
-                    C.byref(upd), C.byref(mis))
+        self.b.call("mat_update_values", self.h, opc, flags, i, j, v, n, mp, C.byref(upd), C.byref(mis))
         return (upd.value, mask.astype(bool)) if skip else upd.value
 
     def add_values(self, I, J, V, missing="error"):
@@ -1258,17 +1270,17 @@ class DynamicSparseMatrix(_Handle):
         streams (sync()).  Returns (updated, missing): cells written and ops without a stored cell."""
         self._require("mat_update_values", self._UPDATE_NEEDS)
         upd, mis = C.c_int64(), C.c_int64()
-        self.b.call("mat_update_values_dev", self.h, int(op), int(flags), C.c_void_p(int(d_I)) if d_I else None,
-                    C.c_void_p(int(d_J)) if d_J else None, C.c_void_p(int(d_V)) if d_V else None, int(n),
-                    C.c_void_p(int(d_missing)) if d_missing else None, C.byref(upd), C.byref(mis))
+        self.b.call("mat_update_values_dev", self.h, int(op), int(flags), _dptr(d_I),
+                    _dptr(d_J), _dptr(d_V), int(n),
+                    _dptr(d_missing), C.byref(upd), C.byref(mis))
         return upd.value, mis.value
 
     def get_batch_dev(self, d_I, d_J, n, d_out, d_found=None):
         """get_batch with everything in HBM: d_out[k] = A[d_I[k], d_J[k]] (0.0 when the cell is not stored), d_found[k] (n bytes,
         optional) = 1 iff it is stored.  Device addresses; enqueued on the colmajor stream, no host wait (sync())."""
         self._require("mat_update_values", self._UPDATE_NEEDS)
-        self.b.call("mat_get_batch_dev", self.h, C.c_void_p(int(d_I)) if d_I else None, C.c_void_p(int(d_J)) if d_J else None, int(n),
-                    C.c_void_p(int(d_out)) if d_out else None, C.c_void_p(int(d_found)) if d_found else None)
+        self.b.call("mat_get_batch_dev", self.h, _dptr(d_I), _dptr(d_J), int(n),
+                    _dptr(d_out), _dptr(d_found))
 
     # ---- insert of cells that are not stored yet, in place (include/dsa.h: dsa_mat_insert_batch[_dev]; HIP library only) ---------
     _INSERT_NEEDS = "insert_values and upsert need the HIP product library"
@@ -1289,29 +1301,11 @@ class DynamicSparseMatrix(_Handle):
             raise B.DsaArgumentError(B.EARG, "existing must be 'error' or 'skip'")
         skip = existing == "skip"
         flags = INS_SKIP_EXISTING if skip else 0
-        ops = (I, J, V)
-        is_t = [type(x).__module__.split(".")[0] == "torch" for x in ops]
-        if any(is_t):
-            import torch
-            if not all(is_t):
-                raise B.DsaArgumentError(B.EARG, "I, J and V must all be numpy arrays or all be tensors on the GPU")
-            for x, dt in zip(ops, (torch.int64, torch.int64, torch.float64)):
-                if x.dtype != dt or not x.is_cuda or x.dim() != 1 or x.numel() != I.numel():
-                    raise B.DsaArgumentError(B.EARG, "I, J, V must be 1-D int64, int64, float64 tensors of one length on the GPU")
-            i, j, v = (x.contiguous() for x in ops)
-            n = i.numel()
-            mask = torch.zeros(n, dtype=torch.uint8, device=i.device) if skip else None
-            # the library reads the triples on its own two streams: torch's pending work on them must be over first
-            torch.cuda.current_stream(i.device).synchronize()
-            self.insert_values_dev(i.data_ptr(), j.data_ptr(), v.data_ptr(), n, flags, d_existing=mask.data_ptr() if skip and n else None)
+        dev, (i, j, v, n, mp), mask, _keep = _triple(I, J, V, skip)
+        if dev:
+            self.insert_values_dev(i, j, v, n, flags, d_existing=mp)
             return mask.bool() if skip else None
-        i, ip = _i64(np.asarray(I, dtype=np.int64).reshape(-1))
-        j, jp = _i64(np.asarray(J, dtype=np.int64).reshape(-1))
-        v, vp = _f64(np.asarray(V, dtype=np.float64).reshape(-1))
-        if not (len(i) == len(j) == len(v)):
-            raise B.DsaArgumentError(B.EARG, "rows, columns, and nonzeros do not have same length.")
-        mask = np.zeros(len(i), dtype=np.uint8)
-        self.b.call("mat_insert_batch", self.h, ip, jp, vp, len(i), flags, mask.ctypes.data_as(P_U8) if skip else None)
+        self.b.call("mat_insert_batch", self.h, i, j, v, n, flags, mp)
         return mask.astype(bool) if skip else None
 
     def insert_values_dev(self, d_I, d_J, d_V, n, flags=0, d_existing=None):
@@ -1319,19 +1313,15 @@ class DynamicSparseMatrix(_Handle):
         0 | INS_SKIP_EXISTING, d_existing: device address of n bytes that receive 1 for an op whose cell is already stored, or
         None.  Returns with both streams drained."""
         self._require("mat_insert_batch", self._INSERT_NEEDS)
-        self.b.call("mat_insert_batch_dev", self.h, C.c_void_p(int(d_I)) if d_I else None, C.c_void_p(int(d_J)) if d_J else None,
-                    C.c_void_p(int(d_V)) if d_V else None, int(n), int(flags), C.c_void_p(int(d_existing)) if d_existing else None)
+        self.b.call("mat_insert_batch_dev", self.h, _dptr(d_I), _dptr(d_J),
+                    _dptr(d_V), int(n), int(flags), _dptr(d_existing))
 
     def upsert(self, I, J, V):
         """A[I[k], J[k]] = V[k] whether the cell is stored or not, for DISTINCT cells and host arrays: update_values(...,
         missing="skip"), then insert_values of the ops it reports missing — the general write for nonzero values composed of its
         two halves (a 0.0 leaves or creates a stored zero).  Returns (updated, inserted)."""
         self._require("mat_insert_batch", self._INSERT_NEEDS)
-        i = np.asarray(I, dtype=np.int64).reshape(-1)
-        j = np.asarray(J, dtype=np.int64).reshape(-1)
-        v = np.asarray(V, dtype=np.float64).reshape(-1)
-        if not (len(i) == len(j) == len(v)):
-            raise B.DsaArgumentError(B.EARG, "rows, columns, and nonzeros do not have same length.")
+        i, j, v = _host_triple(I, J, V)
         updated, miss = self.update_values(i, j, v, missing="skip")
         if miss.any():
             self.insert_values(i[miss], j[miss], v[miss])
@@ -1369,7 +1359,7 @@ def dynamicsparse_dev(d_I, d_J, d_V, nnz, m=None, n=None, index_bits=64, index_b
     b = _bind(binding)
     _require_import(b)
     h = VP()
-    b.call("mat_create_from_coo_dev", C.c_void_p(int(d_I)), C.c_void_p(int(d_J)), C.c_void_p(int(d_V)), int(nnz), int(index_bits),
+    b.call("mat_create_from_coo_dev", _dptr(d_I), _dptr(d_J), _dptr(d_V), int(nnz), int(index_bits),
            int(index_base), -1 if m is None else int(m), -1 if n is None else int(n), C.byref(h))
     return DynamicSparseMatrix(b, h)
 
@@ -1381,8 +1371,8 @@ def dynamicsparse_compressed_dev(orientation, d_ptr, d_idx, d_vals, outer, inner
     b = _bind(binding)
     _require_import(b)
     h = VP()
-    b.call("mat_create_from_compressed_dev", int(orientation), int(index_bits), int(index_base), C.c_void_p(int(d_ptr)),
-           C.c_void_p(int(d_idx)), C.c_void_p(int(d_vals)), int(outer), int(inner), int(nnz), C.byref(h))
+    b.call("mat_create_from_compressed_dev", int(orientation), int(index_bits), int(index_base), _dptr(d_ptr),
+           _dptr(d_idx), _dptr(d_vals), int(outer), int(inner), int(nnz), C.byref(h))
     return DynamicSparseMatrix(b, h)
 
 

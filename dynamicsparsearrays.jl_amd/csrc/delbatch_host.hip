@@ -1,7 +1,7 @@
 // csrc/delbatch_host.hip — host side of the batched delete (dsa_mat_delete_batch[_dev]): argument checks, the scratch and pinned
 // words (Pma::del of the own orientation), the two hand-overs, the control blocks and the root rebalances behind the mark passes.
 // Host-only unit: the kernels are in delbatch.hip.
-// A delete is two steps so that the entry point (dsa_host.hip) can bump the content epoch between them, as for a scale:
+// A delete is two steps so that the entry point (mutate_host.hip) can bump the content epoch between them, as for a scale:
 // delete_batch_prepare (flush, checks, the validate pass: every error with nothing modified and every cached plan intact) and
 // delete_batch_apply (the writes).  The own orientation is the one whose partitions the keys name, the twin the other one.
 #include "host.h"

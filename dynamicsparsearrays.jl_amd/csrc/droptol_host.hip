@@ -1,7 +1,7 @@
 // csrc/droptol_host.hip — host side of the in-place pruning of small entries (dsa_mat_droptol[_dev]): argument checks, the scratch
 // and pinned words (Pma::drp), the one hand-over per orientation, the control blocks and the root rebalances behind the mark passes.
 // Host-only unit: the kernels are in droptol.hip.
-// A droptol is two steps so that the entry point (dsa_host.hip) can bump the content epoch between them, as for a scale or a batched
+// A droptol is two steps so that the entry point (mutate_host.hip) can bump the content epoch between them, as for a scale or a batched
 // delete: droptol_prepare (flush, checks, the decide pass: every error, "nothing to drop" and the count-only call with nothing
 // modified and every cached plan intact) and droptol_apply (the writes).  Delete-only: no slot is allocated, no table entry changes.
 #include "host.h"

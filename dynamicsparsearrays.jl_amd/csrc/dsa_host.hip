@@ -5,11 +5,11 @@
 // The matrix entry points are short wrappers: the argument checks that belong to the ABI plus one or two calls.  What they call is in
 // units of its own: the fill-mode buffer in fill_host.hip, every write to a matrix (the builds of both orientations, the set batch
 // and its strategies, the flush of queued writes, the delete of one column or row) in matwrite_host.hip; the exports, the products,
-// the device import, scale, the batched delete and droptol in export_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip,
-// ingest_host.hip, scale_host.hip, delbatch_host.hip and droptol_host.hip; the sparse-x product and the parity hooks have entry points
-// of their own in sparsex_host.hip and raw_host.hip.  Everything that works on ONE packed-memory array (the Pma of host.h) is in the
-// engine units pma_host.hip (lifecycle, geometry, rebalances, reads), writes_host.hip (yield loop around the sequencer, batch-parallel
-// rounds), build_host.hip (K-build) and spmv_host.hip (SpMV meta and plan).
+// the device import and the reductions in export_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, ingest_host.hip and
+// scale_host.hip; the in-place mutators (scale, batched delete, droptol, update, insert), the sparse-x product and the parity hooks
+// have entry points of their own in mutate_host.hip, sparsex_host.hip and raw_host.hip.  Everything that works on ONE packed-memory
+// array (the Pma of host.h) is in the engine units pma_host.hip (lifecycle, geometry, rebalances, reads), writes_host.hip (yield loop
+// around the sequencer, batch-parallel rounds), build_host.hip (K-build) and spmv_host.hip (SpMV meta and plan).
 //
 // Everything that touches slots runs on the GPU (rebalance.hip, sequencer.hip, spmv.hip).  The host
 // keeps only: the control scalars of each PMA (mirrored from the device control block), the integer
@@ -973,8 +973,7 @@ int32_t dsa_mat_spgemm_csc(dsa_mat_t* h, int32_t transpose, int32_t index_base,
     API_CATCH
 }
 
-// ---- reductions per row / column and the in-place scaling D_r A D_c (scale.hip).  Reduce is read-only; scale changes values: both
-// SpMV plans are dropped before the first write
+// ---- reductions per row / column (scale.hip): read-only
 int32_t dsa_mat_reduce_dev(dsa_mat_t* h, int32_t orientation, int32_t kind, double* d_out, int64_t n_out) {
     API_TRY
     reduce_dev(h, orientation, kind, d_out, n_out);
@@ -985,165 +984,11 @@ int32_t dsa_mat_reduce(dsa_mat_t* h, int32_t orientation, int32_t kind, double* 
     reduce_host(h, orientation, kind, out, n_out);
     API_CATCH
 }
-int32_t dsa_mat_scale_dev(dsa_mat_t* h, double alpha, const double* d_r, int64_t nr, const double* d_c, int64_t nc) {
-    API_TRY
-    scale_prepare(h, d_r, nr, d_c, nc);
-    mat_content_changed(h);
-    scale_apply(h, alpha, d_r, d_c);
-    mat_prefetch_spmv_meta(h);
-    API_CATCH
-}
-int32_t dsa_mat_scale(dsa_mat_t* h, double alpha, const double* r, int64_t nr, const double* c, int64_t nc) {
-    API_TRY
-    ScaleStaging st(h, r, nr, c, nc);
-    scale_prepare(h, st.d_r, nr, st.d_c, nc);
-    mat_content_changed(h);
-    scale_apply(h, alpha, st.d_r, st.d_c);
-    mat_prefetch_spmv_meta(h);
-    HIPCHK(hipStreamSynchronize(h->col.stream));
-    HIPCHK(hipStreamSynchronize(h->row.stream));
-    API_CATCH
-}
 
-// ---- batched delete (delbatch.hip): every column (row) of a key list leaves both orientations in one device pass.  The validate
-// pass is in front of the epoch bump: an error leaves layouts and cached plans as they were
-int32_t dsa_mat_delete_batch_dev(dsa_mat_t* h, int32_t orientation, const int64_t* d_keys, int64_t n, int64_t* removed_out) {
-    API_TRY
-    if (removed_out) *removed_out = 0;
-    const int64_t cells = delete_batch_prepare(h, orientation, d_keys, n);
-    if (cells >= 0) {
-        mat_content_changed(h);
-        delete_batch_apply(h, orientation, n, cells);
-        mat_prefetch_spmv_meta(h);
-        if (removed_out) *removed_out = cells;
-    }
-    API_CATCH
-}
-int32_t dsa_mat_delete_batch(dsa_mat_t* h, int32_t orientation, const int64_t* keys, int64_t n, int64_t* removed_out) {
-    API_TRY
-    if (removed_out) *removed_out = 0;
-    mat_flush(h);
-    if (h->fillmode || !h->has_major) fail(DSA_EMODE, "Cannot delete columns or rows in fill mode");
-    Pma& P = orient(h, orientation);
-    if (n < 0) fail(DSA_EARG, "delete batch: n is negative");
-    if (n > 0 && !keys) fail(DSA_EARG, "delete batch: the key list is NULL");
-    if (n > 0) {
-        DevStaging b(P.stream);                           // drains the own stream before the keys go back to the pool
-        HIPCHK(pool_alloc(&b.p[0], (size_t)n * sizeof(int64_t)));
-        HIPCHK(hipMemcpyAsync(b.p[0], keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, P.stream));
-        const int64_t cells = delete_batch_prepare(h, orientation, static_cast<const int64_t*>(b.p[0]), n);
-        mat_content_changed(h);
-        delete_batch_apply(h, orientation, n, cells);     // (returns with both streams drained: the twin is done with the table)
-        mat_prefetch_spmv_meta(h);
-        if (removed_out) *removed_out = cells;
-    }
-    API_CATCH
-}
-
-// ---- dropzeros! / droptol! (droptol.hip): every small cell leaves both orientations in place.  The decide pass is in front of the
-// epoch bump: an error, a call that drops nothing and the count-only call leave layouts and cached plans as they were
-namespace {
-void mat_droptol(dsa_mat_t* h, double tol, const double* d_rtol, int64_t nr, const double* d_ctol, int64_t nc, int32_t count_only,
-                 int64_t* dropped_out) {
-    const int64_t count = droptol_prepare(h, tol, d_rtol, nr, d_ctol, nc);
-    if (count > 0 && !count_only) {
-        mat_content_changed(h);
-        droptol_apply(h, count);
-        mat_prefetch_spmv_meta(h);
-    }
-    if (dropped_out) *dropped_out = count;
-}
-}  // namespace
-int32_t dsa_mat_droptol_dev(dsa_mat_t* h, double tol, const double* d_rtol, int64_t nr, const double* d_ctol, int64_t nc, int32_t count_only,
-                            int64_t* dropped_out) {
-    API_TRY
-    if (dropped_out) *dropped_out = 0;
-    mat_droptol(h, tol, d_rtol, nr, d_ctol, nc, count_only, dropped_out);
-    API_CATCH
-}
-int32_t dsa_mat_droptol(dsa_mat_t* h, double tol, const double* rtol, int64_t nr, const double* ctol, int64_t nc, int32_t count_only,
-                        int64_t* dropped_out) {
-    API_TRY
-    if (dropped_out) *dropped_out = 0;
-    ScaleStaging st(h, rtol, nr, ctol, nc);               // flush, DSA_EMODE / DSA_EARG, the vectors in HBM until both streams have drained
-    mat_droptol(h, tol, st.d_r, nr, st.d_c, nc, count_only, dropped_out);
-    API_CATCH
-}
-
-// ---- update of stored values in place (update.hip) and the batched read into HBM.  Locate, claim and resolve are in front of the
-// epoch bump: an error and a call without a winning write leave layouts and cached plans as they were
-namespace {
-void mat_update_values(dsa_mat_t* h, int32_t op, int32_t flags, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n,
-                       uint8_t* d_missing, int64_t* updated_out, int64_t* missing_out) {
-    const UpdateCounts c = update_prepare(h, op, flags, d_I, d_J, d_V, n, d_missing);
-    if (c.updated > 0) {
-        mat_content_changed(h);
-        update_apply(h, op, d_V, n);
-    }
-    if (updated_out) *updated_out = c.updated;
-    if (missing_out) *missing_out = c.missing;
-}
-}  // namespace
-int32_t dsa_mat_update_values_dev(dsa_mat_t* h, int32_t op, int32_t flags, const int64_t* d_I, const int64_t* d_J, const double* d_V,
-                                  int64_t n, uint8_t* d_missing, int64_t* updated_out, int64_t* missing_out) {
-    API_TRY
-    if (updated_out) *updated_out = 0;
-    if (missing_out) *missing_out = 0;
-    mat_update_values(h, op, flags, d_I, d_J, d_V, n, d_missing, updated_out, missing_out);
-    API_CATCH
-}
-int32_t dsa_mat_update_values(dsa_mat_t* h, int32_t op, int32_t flags, const int64_t* I, const int64_t* J, const double* V, int64_t n,
-                              uint8_t* missing, int64_t* updated_out, int64_t* missing_out) {
-    API_TRY
-    if (updated_out) *updated_out = 0;
-    if (missing_out) *missing_out = 0;
-    UpdateStaging st(h, op, flags, I, J, V, n, missing != nullptr);      // flush, DSA_EMODE / DSA_EARG, the triples in HBM until both streams have drained
-    if (n > 0) {
-        uint8_t* d_missing = static_cast<uint8_t*>(st.b.p[3]);
-        mat_update_values(h, op, flags, static_cast<const int64_t*>(st.b.p[0]), static_cast<const int64_t*>(st.b.p[1]),
-                          static_cast<const double*>(st.b.p[2]), n, d_missing, updated_out, missing_out);
-        if (missing) HIPCHK(hipMemcpyAsync(missing, d_missing, (size_t)n, hipMemcpyDeviceToHost, h->col.stream));
-        HIPCHK(hipStreamSynchronize(h->col.stream));
-        HIPCHK(hipStreamSynchronize(h->row.stream));
-    }
-    API_CATCH
-}
+// ---- the batched read that stays in HBM (update_host.hip)
 int32_t dsa_mat_get_batch_dev(dsa_mat_t* h, const int64_t* d_I, const int64_t* d_J, int64_t n, double* d_out, uint8_t* d_found) {
     API_TRY
     get_batch_dev(h, d_I, d_J, n, d_out, d_found);
-    API_CATCH
-}
-
-// ---- insert of cells that are not stored yet (insert.hip).  Scan, sort, locate and verdict are in front of the epoch bump: an error
-// and a call that inserts nothing leave layouts and cached plans as they were
-namespace {
-void mat_insert_batch(dsa_mat_t* h, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int32_t flags, uint8_t* d_existing) {
-    const InsertCounts c = insert_prepare(h, d_I, d_J, d_V, n, flags, d_existing);
-    if (c.ops > 0) {
-        mat_content_changed(h);
-        insert_apply(h, c, d_V, n);
-        mat_prefetch_spmv_meta(h);
-    }
-}
-}  // namespace
-int32_t dsa_mat_insert_batch_dev(dsa_mat_t* h, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int32_t flags,
-                                 uint8_t* d_existing) {
-    API_TRY
-    mat_insert_batch(h, d_I, d_J, d_V, n, flags, d_existing);
-    if (n > 0 && h->has_major) { HIPCHK(hipStreamSynchronize(h->col.stream)); HIPCHK(hipStreamSynchronize(h->row.stream)); }
-    API_CATCH
-}
-int32_t dsa_mat_insert_batch(dsa_mat_t* h, const int64_t* I, const int64_t* J, const double* V, int64_t n, int32_t flags, uint8_t* existing) {
-    API_TRY
-    InsertStaging st(h, I, J, V, n, flags, existing != nullptr);      // flush, DSA_EMODE / DSA_EARG, the triples in HBM until both streams have drained
-    if (n > 0) {
-        uint8_t* d_existing = static_cast<uint8_t*>(st.b.p[3]);
-        mat_insert_batch(h, static_cast<const int64_t*>(st.b.p[0]), static_cast<const int64_t*>(st.b.p[1]), static_cast<const double*>(st.b.p[2]), n,
-                         flags, d_existing);
-        if (existing) HIPCHK(hipMemcpyAsync(existing, d_existing, (size_t)n, hipMemcpyDeviceToHost, h->col.stream));
-        HIPCHK(hipStreamSynchronize(h->col.stream));
-        HIPCHK(hipStreamSynchronize(h->row.stream));
-    }
     API_CATCH
 }
 

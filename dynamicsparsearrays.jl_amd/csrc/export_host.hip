@@ -102,27 +102,25 @@ void keylist_host(const Side& e, const int64_t* outer, int64_t nouter, const int
     Pma& S = e.P;
     DevStaging b(S.stream);
     const size_t kb = (size_t)std::max<int64_t>(nouter + ninner, 1) * sizeof(int64_t), pb = (size_t)(nouter + 1) * sizeof(int64_t);
-    HIPCHK(pool_alloc(&b.p[0], kb));
-    HIPCHK(pool_alloc(&b.p[1], pb));
-    int64_t* d_outer = static_cast<int64_t*>(b.p[0]);
+    int64_t* d_outer = b.alloc<int64_t>(0, kb);
     int64_t* d_inner = d_outer + nouter;
-    if (nouter > 0) HIPCHK(hipMemcpyAsync(d_outer, outer, (size_t)nouter * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
-    if (ninner > 0) HIPCHK(hipMemcpyAsync(d_inner, inner, (size_t)ninner * sizeof(int64_t), hipMemcpyHostToDevice, S.stream));
+    b.alloc(1, pb);
+    if (nouter > 0) b.up(d_outer, outer, (size_t)nouter * sizeof(int64_t));
+    if (ninner > 0) b.up(d_inner, inner, (size_t)ninner * sizeof(int64_t));
     const KeyTotals t = count(d_outer, d_inner, b.p[1]);
-    HIPCHK(hipMemcpyAsync(ptr, b.p[1], pb, hipMemcpyDeviceToHost, S.stream));
+    b.down(ptr, b.p[1], pb);
     if (cap < t.total) {
-        HIPCHK(hipStreamSynchronize(S.stream));      // ptr is the caller's to read with DSA_ECAP
+        b.sync();      // ptr is the caller's to read with DSA_ECAP
         fail(DSA_ECAP, "output buffers too small");
     }
     if (t.total > 0) {
         const size_t cb = (size_t)t.total * sizeof(int64_t);
-        HIPCHK(pool_alloc(&b.p[2], cb));
-        HIPCHK(pool_alloc(&b.p[3], cb));
-        emit(t, b.p[2], static_cast<double*>(b.p[3]));
-        HIPCHK(hipMemcpyAsync(idx, b.p[2], cb, hipMemcpyDeviceToHost, S.stream));
-        HIPCHK(hipMemcpyAsync(vals, b.p[3], cb, hipMemcpyDeviceToHost, S.stream));
+        b.alloc(2, cb);
+        emit(t, b.p[2], b.alloc<double>(3, cb));
+        b.down(idx, b.p[2], cb);
+        b.down(vals, b.p[3], cb);
     }
-    HIPCHK(hipStreamSynchronize(S.stream));
+    b.sync();
 }
 
 // ---- the partitions of a key list
@@ -243,17 +241,16 @@ void to_compressed_host(dsa_mat* h, int32_t o, int32_t index_base, int64_t* ptr,
     if (nnz > 0 && (!idx || !vals)) fail(DSA_EARG, "output pointer is NULL");
     DevStaging b(P.stream);
     const size_t pb = (size_t)(e.dim_out + 1) * sizeof(int64_t), cb = (size_t)std::max<int64_t>(nnz, 1) * sizeof(int64_t);
-    HIPCHK(pool_alloc(&b.p[0], pb));
-    HIPCHK(pool_alloc(&b.p[1], cb));
-    HIPCHK(pool_alloc(&b.p[2], cb));
+    b.alloc(0, pb);
+    b.alloc(1, cb);
     int64_t n = 0;
-    compress_side(e, 64, index_base, b.p[0], b.p[1], static_cast<double*>(b.p[2]), nnz, &n);
-    HIPCHK(hipMemcpyAsync(ptr, b.p[0], pb, hipMemcpyDeviceToHost, P.stream));
+    compress_side(e, 64, index_base, b.p[0], b.p[1], b.alloc<double>(2, cb), nnz, &n);
+    b.down(ptr, b.p[0], pb);
     if (n > 0) {
-        HIPCHK(hipMemcpyAsync(idx, b.p[1], (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, P.stream));
-        HIPCHK(hipMemcpyAsync(vals, b.p[2], (size_t)n * sizeof(double), hipMemcpyDeviceToHost, P.stream));
+        b.down(idx, b.p[1], (size_t)n * sizeof(int64_t));
+        b.down(vals, b.p[2], (size_t)n * sizeof(double));
     }
-    HIPCHK(hipStreamSynchronize(P.stream));
+    b.sync();
 }
 
 void select_compressed_dev(dsa_mat* h, int32_t o, int32_t index_bits, int32_t index_base, const int64_t* d_sel, int64_t nsel,

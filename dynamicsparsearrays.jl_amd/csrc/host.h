@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, fill_host.hip, matwrite_host.hip, pma_host.hip,
-// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, insert_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
+// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, mutate_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, insert_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -77,12 +77,28 @@ struct ExportArea {
 };
 
 // Pooled device staging of a host-form entry point: up to four blocks, released once the stream has drained (also on an error
-// after a launch).
+// after a launch).  Every copy is enqueued on `s`; the caller decides where it waits (sync).
 struct DevStaging {
     hipStream_t s; void* p[4] = {nullptr, nullptr, nullptr, nullptr};
     explicit DevStaging(hipStream_t stream) : s(stream) {}
     DevStaging(const DevStaging&) = delete;
     ~DevStaging() { if (p[0] || p[1] || p[2] || p[3]) { (void)hipStreamSynchronize(s); for (void* q : p) pool_free(q); } }
+    template <typename T = void> T* at(int q) const { return static_cast<T*>(p[q]); }
+    template <typename T = void> T* alloc(int q, size_t bytes) { HIPCHK(pool_alloc(&p[q], bytes)); return at<T>(q); }
+    // host -> device and device -> host; `dev` is a block or a place inside one
+    void up(void* dev, const void* src, size_t bytes) { HIPCHK(hipMemcpyAsync(dev, src, bytes, hipMemcpyHostToDevice, s)); }
+    void down(void* dst, const void* dev, size_t bytes) { HIPCHK(hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, s)); }
+    template <typename T = void> T* upload(int q, const void* src, size_t bytes) { alloc(q, bytes); up(p[q], src, bytes); return at<T>(q); }
+    // `rows` rows of `row` bytes between block q, where they are packed, and host memory, where they are `pitch` bytes apart
+    template <typename T = void> T* upload_rows(int q, const void* src, size_t pitch, size_t row, size_t rows) {
+        alloc(q, rows * row);
+        HIPCHK(hipMemcpy2DAsync(p[q], row, src, pitch, row, rows, hipMemcpyHostToDevice, s));
+        return at<T>(q);
+    }
+    void down_rows(void* dst, size_t pitch, int q, size_t row, size_t rows) {
+        HIPCHK(hipMemcpy2DAsync(dst, pitch, p[q], row, row, rows, hipMemcpyDeviceToHost, s));
+    }
+    void sync() { HIPCHK(hipStreamSynchronize(s)); }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -369,18 +385,13 @@ void submatrix_compressed_host(dsa_mat* h, int32_t orientation, int32_t index_ba
 
 // ---- scale_host.hip: per-partition reductions and the in-place scaling D_r A D_c (d_* are device arrays).  A scale is two steps so
 // that the entry point can bump the content epoch between them: scale_prepare (flush, checks, the bounds pass over both orientations:
-// DSA_EBOUNDS with nothing modified) and scale_apply (the writes, enqueued on both streams).  ScaleStaging holds factors that came
-// from host memory in HBM until both streams have drained.
+// DSA_EBOUNDS with nothing modified) and scale_apply (the writes, enqueued on both streams).
 void reduce_dev(dsa_mat* h, int32_t orientation, int32_t kind, double* d_out, int64_t n_out);
 void reduce_host(dsa_mat* h, int32_t orientation, int32_t kind, double* out, int64_t n_out);
 bool stream_nt(const Pma& P, int64_t vector_bytes);      // the slot stream of P goes around the cache: it does not fit an XCD's L2 beside the vectors
 void scale_prepare(dsa_mat* h, const double* d_r, int64_t nr, const double* d_c, int64_t nc);
 void scale_apply(dsa_mat* h, double alpha, const double* d_r, const double* d_c);
-struct ScaleStaging {
-    dsa_mat* h; DevStaging b; const double* d_r = nullptr; const double* d_c = nullptr;
-    ScaleStaging(dsa_mat* h, const double* r, int64_t nr, const double* c, int64_t nc);
-    ~ScaleStaging();
-};
+void scale_check_args(dsa_mat* h, const double* r, int64_t nr, const double* c, int64_t nc);
 
 // ---- delbatch_host.hip: the batched delete of columns (DSA_COLMAJOR) or rows (DSA_ROWMAJOR), d_keys a device array.  Two steps so
 // that the entry point can bump the content epoch between them: delete_batch_prepare (flush, checks, the validate pass: DSA_EMODE /
@@ -402,33 +413,23 @@ void droptol_apply(dsa_mat* h, int64_t count);
 // ---- update_host.hip: the values of stored cells overwritten (DSA_UPD_SET) or added to (DSA_UPD_ADD) from triples in HBM, and the
 // batched read into HBM (d_* are device arrays).  Two steps so that the entry point can bump the content epoch between them:
 // update_prepare (flush, checks, locate + claim + resolve over both orientations: DSA_EMODE / DSA_EARG / DSA_EKEY / DSA_EASSERT with
-// nothing modified; returns the winning and the missing ops) and update_apply (the stores, enqueued on both streams).  UpdateStaging
-// holds triples that came from host memory (p[0..2]; p[3]: the missing flags) in HBM until both streams have drained.
+// nothing modified; returns the winning and the missing ops) and update_apply (the stores, enqueued on both streams).
 struct UpdateCounts { int64_t updated, missing; };
 UpdateCounts update_prepare(dsa_mat* h, int32_t op, int32_t flags, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n,
                             uint8_t* d_missing);
 void update_apply(dsa_mat* h, int32_t op, const double* d_V, int64_t n);
 void get_batch_dev(dsa_mat* h, const int64_t* d_I, const int64_t* d_J, int64_t n, double* d_out, uint8_t* d_found);
-struct UpdateStaging {
-    dsa_mat* h; DevStaging b;
-    UpdateStaging(dsa_mat* h, int32_t op, int32_t flags, const int64_t* I, const int64_t* J, const double* V, int64_t n, bool want_missing);
-    ~UpdateStaging();
-};
+void update_check_args(dsa_mat* h, int32_t op, int32_t flags, const void* I, const void* J, const void* V, int64_t n);
 
 // ---- insert_host.hip: cells that are not stored yet created in both orientations from triples in HBM (d_* are device arrays).  Two
 // steps so that the entry point can bump the content epoch between them: insert_prepare (flush, checks, the key scan, then sort +
 // locate + verdict over both orientations: DSA_EMODE / DSA_EARG / DSA_EKEY / DSA_EASSERT with nothing modified; returns what the merge
 // adds, ops == 0 when there is nothing to insert) and insert_apply (capacity, tables, the merge of both orientations, control blocks
-// uploaded, both streams drained).  InsertStaging holds triples that came from host memory (p[0..2]; p[3]: the existing flags) in HBM
-// until both streams have drained.
+// uploaded, both streams drained).
 struct InsertCounts { int64_t ops = 0, existing = 0, items[2] = {0, 0}, parts[2] = {0, 0}; KeyRange rows, cols; };
 InsertCounts insert_prepare(dsa_mat* h, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int32_t flags, uint8_t* d_existing);
 void insert_apply(dsa_mat* h, const InsertCounts& c, const double* d_V, int64_t n);
-struct InsertStaging {
-    dsa_mat* h; DevStaging b;
-    InsertStaging(dsa_mat* h, const int64_t* I, const int64_t* J, const double* V, int64_t n, int32_t flags, bool want_existing);
-    ~InsertStaging();
-};
+void insert_check_args(dsa_mat* h, const void* I, const void* J, const void* V, int64_t n, int32_t flags);
 
 // Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks
 // and uploaded asynchronously as a chunk fills (the copy of chunk k overlaps the caller's appends into chunk k+1), so that

@@ -1,7 +1,7 @@
 // csrc/insert_host.hip — host side of the batched insert of cells that are not stored yet (dsa_mat_insert_batch[_dev]): argument
 // checks, the key scan, the scratch and pinned words (Pma::ins), the hand-over of each orientation, the choice of the capacity, the
-// tables and control blocks around the merge, and the staging of the host form.  Host-only unit: the kernels are in insert.hip.
-// An insert is two steps so that the entry point (dsa_host.hip) can bump the content epoch between them, as for an update or a
+// tables and control blocks around the merge.  Host-only unit: the kernels are in insert.hip.
+// An insert is two steps so that the entry point (mutate_host.hip) can bump the content epoch between them, as for an update or a
 // batched delete: insert_prepare (flush, checks, scan, sort + locate + verdict: every error and the call without a new cell with
 // nothing modified and every cached plan intact) and insert_apply (the writes).
 #include "host.h"
@@ -17,6 +17,9 @@ namespace {
 
 std::string op_text(unsigned long long k) { return "op " + std::to_string(k) + " (0-based)"; }
 
+}  // namespace
+
+// what both forms check before anything is staged or launched (I, J, V: host or device addresses)
 void insert_check_args(dsa_mat* h, const void* I, const void* J, const void* V, int64_t n, int32_t flags) {
     if (h->fillmode || !h->has_major) fail(DSA_EMODE, "Cannot insert cells in fill mode");
     if ((flags & ~DSA_INS_SKIP_EXISTING) != 0) fail(DSA_EARG, "insert_batch: unknown flags");
@@ -24,6 +27,8 @@ void insert_check_args(dsa_mat* h, const void* I, const void* J, const void* V, 
     if (n > 0 && (!I || !J || !V)) fail(DSA_EARG, "insert_batch: an operand is NULL");
     if (n > INT32_MAX) fail(DSA_EARG, "insert_batch: more than 2^31 - 1 ops");
 }
+
+namespace {
 
 // bits that hold every value of [r.lo, r.hi] - r.lo
 int range_bits(const KeyRange& r) {
@@ -146,24 +151,6 @@ void insert_apply(dsa_mat* h, const InsertCounts& c, const double* d_V, int64_t 
     if (dbg_time())
         fprintf(stderr, "[insert_batch] merge launches %.1f us, control blocks up and both streams drained %.1f us\n", elapsed_us(t0, t1), elapsed_us(t1));
 }
-
-// I, J, V in host memory: uploaded on the colmajor stream, which is drained before the rowmajor stream may read them
-InsertStaging::InsertStaging(dsa_mat* h_, const int64_t* I, const int64_t* J, const double* V, int64_t n, int32_t flags, bool want_existing)
-    : h(h_), b(h_->col.stream) {
-    mat_flush(h);
-    insert_check_args(h, I, J, V, n, flags);
-    if (n == 0) return;
-    hipStream_t s = h->col.stream;
-    const void* src[3] = {I, J, V};
-    for (int q = 0; q < 3; ++q) {
-        HIPCHK(pool_alloc(&b.p[q], (size_t)n * 8));
-        HIPCHK(hipMemcpyAsync(b.p[q], src[q], (size_t)n * 8, hipMemcpyHostToDevice, s));
-    }
-    if (want_existing) HIPCHK(pool_alloc(&b.p[3], (size_t)n));
-    HIPCHK(hipStreamSynchronize(s));
-}
-// the rowmajor stream may still read the staged triples (also after an error behind a launch); DevStaging drains the colmajor one
-InsertStaging::~InsertStaging() { if (h->has_major) (void)hipStreamSynchronize(h->row.stream); }
 
 }  // namespace host
 }  // namespace dsa

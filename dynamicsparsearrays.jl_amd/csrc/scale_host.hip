@@ -1,8 +1,8 @@
 // csrc/scale_host.hip — host side of the per-partition reductions (dsa_mat_reduce[_dev]) and of the in-place diagonal scaling
 // (dsa_mat_scale[_dev]): argument checks, the orientation that is walked, the scratch and pinned words (Pma::sc), the hand-overs of
-// the bounds word and the staging of operands in host memory.  Host-only unit: the kernels are in scale.hip.
+// the bounds word and the staging of a reduce into host memory.  Host-only unit: the kernels are in scale.hip.
 // Reduce is read-only: no epoch moves, a cached SpMV plan survives.  Scale changes values only — no slot moves, no layout epoch —
-// and the entry point (dsa_host.hip) bumps the content epoch between scale_prepare and scale_apply.
+// and the entry point (mutate_host.hip) bumps the content epoch between scale_prepare and scale_apply.
 #include "host.h"
 #include "scale.h"
 
@@ -16,15 +16,12 @@ bool stream_nt(const Pma& P, int64_t vector_bytes) {
     return P.capacity() * (int64_t)(P.kb() + sizeof(double)) + vector_bytes > (3 << 20);
 }
 
-namespace {
-
-void check_factors(dsa_mat* h, const double* r, int64_t nr, const double* c, int64_t nc) {
+// what both forms of a scale, and the host form of a droptol, check before anything is staged or launched (r, c: host or device addresses)
+void scale_check_args(dsa_mat* h, const double* r, int64_t nr, const double* c, int64_t nc) {
     if (h->fillmode || !h->has_major) fail(DSA_EMODE, "matrix is in fill mode");
     if (r && nr != h->m) fail(DSA_EARG, "nr must equal the number of rows");
     if (c && nc != h->n) fail(DSA_EARG, "nc must equal the number of columns");
 }
-
-}  // namespace
 
 // out[key - 1] = reduction over the stored cells of partition `key` of the orientation, enqueued on its stream; waits for the bounds word
 void reduce_dev(dsa_mat* h, int32_t orientation, int32_t kind, double* d_out, int64_t n_out) {
@@ -55,17 +52,16 @@ void reduce_host(dsa_mat* h, int32_t orientation, int32_t kind, double* out, int
     if (n_out < 0 || (n_out > 0 && !out)) fail(DSA_EARG, "output is NULL");
     Pma& P = orientation == DSA_ROWMAJOR ? h->row : h->col;
     DevStaging b(P.stream);
-    HIPCHK(pool_alloc(&b.p[0], (size_t)std::max<int64_t>(n_out, 1) * sizeof(double)));
-    reduce_dev(h, orientation, kind, static_cast<double*>(b.p[0]), n_out);
-    if (n_out > 0) HIPCHK(hipMemcpyAsync(out, b.p[0], (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, P.stream));
-    HIPCHK(hipStreamSynchronize(P.stream));
+    reduce_dev(h, orientation, kind, b.alloc<double>(0, (size_t)std::max<int64_t>(n_out, 1) * sizeof(double)), n_out);
+    if (n_out > 0) b.down(out, b.p[0], (size_t)n_out * sizeof(double));
+    b.sync();
 }
 
 // Everything of a scale in front of the first write: queued writes applied, arguments checked, and the pass over both orientations
 // that finds the carry of every span and checks every stored entry against size(m).  Throws DSA_EBOUNDS with nothing modified.
 void scale_prepare(dsa_mat* h, const double* d_r, int64_t nr, const double* d_c, int64_t nc) {
     mat_flush(h);
-    check_factors(h, d_r, nr, d_c, nc);
+    scale_check_args(h, d_r, nr, d_c, nc);
     unsigned long long seq[2] = {0, 0};
     Pma* const side[2] = {&h->col, &h->row};
     if (h->col.capacity() <= 0 || h->row.capacity() <= 0) return;      // no slot array: nothing is stored
@@ -93,27 +89,6 @@ void scale_apply(dsa_mat* h, double alpha, const double* d_r, const double* d_c)
     LAUNCH("scale", launch_scale_apply(R.K(), R.V(), R.O(), R.capacity(), R.col_keys, R.h_ctl->table_len, alpha, d_c, h->n, d_r, h->m, false,
                                        stream_nt(R, vb), R.sc.scratch, R.stream));
 }
-
-// r and c in host memory: uploaded on the colmajor stream, which is drained before the rowmajor stream may read them
-ScaleStaging::ScaleStaging(dsa_mat* h_, const double* r, int64_t nr, const double* c, int64_t nc) : h(h_), b(h_->col.stream) {
-    mat_flush(h);
-    check_factors(h, r, nr, c, nc);
-    hipStream_t s = h->col.stream;
-    if (r && nr > 0) {
-        HIPCHK(pool_alloc(&b.p[0], (size_t)nr * sizeof(double)));
-        HIPCHK(hipMemcpyAsync(b.p[0], r, (size_t)nr * sizeof(double), hipMemcpyHostToDevice, s));
-    }
-    if (c && nc > 0) {
-        HIPCHK(pool_alloc(&b.p[1], (size_t)nc * sizeof(double)));
-        HIPCHK(hipMemcpyAsync(b.p[1], c, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    // a factor of length 0 is handed on as a non-NULL pointer that is never read: "given" and "absent" stay apart
-    d_r = r ? (b.p[0] ? static_cast<const double*>(b.p[0]) : r) : nullptr;
-    d_c = c ? (b.p[1] ? static_cast<const double*>(b.p[1]) : c) : nullptr;
-}
-// the rowmajor stream may still read the staged factors (also after an error behind a launch); DevStaging drains the colmajor one
-ScaleStaging::~ScaleStaging() { if (h->has_major) (void)hipStreamSynchronize(h->row.stream); }
 
 }  // namespace host
 }  // namespace dsa

@@ -46,17 +46,11 @@ void selprod_host(dsa_mat* h, int32_t transpose, const int64_t* sel, int64_t nse
     Pma& P = transpose ? h->col : h->row;
     DevStaging b(P.stream);
     const size_t row = (size_t)k * sizeof(double);
-    HIPCHK(pool_alloc(&b.p[0], (size_t)nsel * sizeof(int64_t)));
-    HIPCHK(hipMemcpyAsync(b.p[0], sel, (size_t)nsel * sizeof(int64_t), hipMemcpyHostToDevice, P.stream));
-    if (nx > 0) {
-        HIPCHK(pool_alloc(&b.p[1], (size_t)nx * row));
-        HIPCHK(hipMemcpy2DAsync(b.p[1], row, x, (size_t)ldx * sizeof(double), row, (size_t)nx, hipMemcpyHostToDevice, P.stream));
-    }
-    HIPCHK(pool_alloc(&b.p[2], (size_t)nsel * row));
-    selprod_dev(h, transpose, static_cast<const int64_t*>(b.p[0]), nsel, static_cast<const double*>(b.p[1]), nx, k, k,
-                static_cast<double*>(b.p[2]), k, P.stream);
-    HIPCHK(hipMemcpy2DAsync(y, (size_t)ldy * sizeof(double), b.p[2], row, row, (size_t)nsel, hipMemcpyDeviceToHost, P.stream));
-    HIPCHK(hipStreamSynchronize(P.stream));
+    const int64_t* d_sel = b.upload<int64_t>(0, sel, (size_t)nsel * sizeof(int64_t));
+    if (nx > 0) b.upload_rows(1, x, (size_t)ldx * sizeof(double), row, (size_t)nx);
+    selprod_dev(h, transpose, d_sel, nsel, b.at<double>(1), nx, k, k, b.alloc<double>(2, (size_t)nsel * row), k, P.stream);
+    b.down_rows(y, (size_t)ldy * sizeof(double), 2, row, (size_t)nsel);
+    b.sync();
 }
 
 }  // namespace host

@@ -119,33 +119,30 @@ void spgemm_csc_host(dsa_mat* h, int32_t transpose, int32_t index_base, const in
     DevStaging b(S.stream);
     // block 0: xptr, then xidx; block 1: xval; block 2: yptr; block 3: yidx, then yval
     const size_t pb = (size_t)(k + 1) * sizeof(int64_t), xb = (size_t)nnzx * sizeof(int64_t);
-    HIPCHK(pool_alloc(&b.p[0], pb + std::max<size_t>(xb, 8)));
-    HIPCHK(pool_alloc(&b.p[1], std::max<size_t>(xb, 8)));
-    HIPCHK(pool_alloc(&b.p[2], pb));
-    int64_t* d_xptr = static_cast<int64_t*>(b.p[0]);
+    int64_t* d_xptr = b.alloc<int64_t>(0, pb + std::max<size_t>(xb, 8));
     int64_t* d_xidx = d_xptr + k + 1;
-    double* d_xval = static_cast<double*>(b.p[1]);
-    HIPCHK(hipMemcpyAsync(d_xptr, xptr, pb, hipMemcpyHostToDevice, S.stream));
+    double* d_xval = b.alloc<double>(1, std::max<size_t>(xb, 8));
+    b.alloc(2, pb);
+    b.up(d_xptr, xptr, pb);
     if (nnzx > 0) {
-        HIPCHK(hipMemcpyAsync(d_xidx, xidx, xb, hipMemcpyHostToDevice, S.stream));
-        HIPCHK(hipMemcpyAsync(d_xval, xval, xb, hipMemcpyHostToDevice, S.stream));
+        b.up(d_xidx, xidx, xb);
+        b.up(d_xval, xval, xb);
     }
     const SpgTotals t = spgemm_count(e, 64, index_base, d_xptr, d_xidx, d_xval, k, nnzx, b.p[2], nnz_out);
-    HIPCHK(hipMemcpyAsync(yptr, b.p[2], pb, hipMemcpyDeviceToHost, S.stream));
+    b.down(yptr, b.p[2], pb);
     if (cap < t.total) {
-        HIPCHK(hipStreamSynchronize(S.stream));      // yptr is the caller's to read with DSA_ECAP
+        b.sync();      // yptr is the caller's to read with DSA_ECAP
         fail(DSA_ECAP, "output buffers too small");
     }
     if (t.total > 0) {
         const size_t cb = (size_t)t.total * sizeof(int64_t);
-        HIPCHK(pool_alloc(&b.p[3], 2 * cb));
-        int64_t* d_yidx = static_cast<int64_t*>(b.p[3]);
+        int64_t* d_yidx = b.alloc<int64_t>(3, 2 * cb);
         double* d_yval = reinterpret_cast<double*>(d_yidx + t.total);
         spgemm_emit(e, t, 64, index_base, d_xval, k, nnzx, d_yidx, d_yval);
-        HIPCHK(hipMemcpyAsync(yidx, d_yidx, cb, hipMemcpyDeviceToHost, S.stream));
-        HIPCHK(hipMemcpyAsync(yval, d_yval, cb, hipMemcpyDeviceToHost, S.stream));
+        b.down(yidx, d_yidx, cb);
+        b.down(yval, d_yval, cb);
     }
-    HIPCHK(hipStreamSynchronize(S.stream));
+    b.sync();
 }
 
 }  // namespace host

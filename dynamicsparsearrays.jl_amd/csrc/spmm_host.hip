@@ -37,16 +37,12 @@ void spmm_host(dsa_mat* h, int32_t transpose, const double* x, int64_t nx, int64
     Pma& P = transpose ? h->col : h->row;
     DevStaging b(P.stream);
     const size_t row = (size_t)k * sizeof(double);
-    if (nx > 0) {
-        HIPCHK(pool_alloc(&b.p[0], (size_t)nx * row));
-        HIPCHK(hipMemcpy2DAsync(b.p[0], row, x, (size_t)ldx * sizeof(double), row, (size_t)nx, hipMemcpyHostToDevice, P.stream));
-    }
+    if (nx > 0) b.upload_rows(0, x, (size_t)ldx * sizeof(double), row, (size_t)nx);
     if (ny > 0) {
-        HIPCHK(pool_alloc(&b.p[1], (size_t)ny * row));
-        spmm_dev(h, transpose, static_cast<const double*>(b.p[0]), nx, k, k, static_cast<double*>(b.p[1]), ny, k, P.stream);
-        HIPCHK(hipMemcpy2DAsync(y, (size_t)ldy * sizeof(double), b.p[1], row, row, (size_t)ny, hipMemcpyDeviceToHost, P.stream));
+        spmm_dev(h, transpose, b.at<double>(0), nx, k, k, b.alloc<double>(1, (size_t)ny * row), ny, k, P.stream);
+        b.down_rows(y, (size_t)ldy * sizeof(double), 1, row, (size_t)ny);
     }
-    HIPCHK(hipStreamSynchronize(P.stream));
+    b.sync();
 }
 
 }  // namespace host

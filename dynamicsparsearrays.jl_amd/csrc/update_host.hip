@@ -1,8 +1,7 @@
 // csrc/update_host.hip — host side of the in-place value update (dsa_mat_update_values[_dev]) and of the batched read that stays in
 // HBM (dsa_mat_get_batch_dev): argument checks, the scratch and pinned words (Pma::upd), the event that lets the colmajor stream
-// resolve behind the rowmajor locate, the one hand-over, and the staging of the host form.  Host-only unit: the kernels are in
-// update.hip.
-// An update is two steps so that the entry point (dsa_host.hip) can bump the content epoch between them, as for a scale or a
+// resolve behind the rowmajor locate and the one hand-over.  Host-only unit: the kernels are in update.hip.
+// An update is two steps so that the entry point (mutate_host.hip) can bump the content epoch between them, as for a scale or a
 // droptol: update_prepare (flush, checks, locate + claim + resolve: every error and the call without a winner with nothing modified
 // and every cached plan intact) and update_apply (the stores).  Values only: no slot moves, no table entry or counter changes.
 #include "host.h"
@@ -22,7 +21,9 @@ void stream_after(Pma& rec, hipStream_t from, hipStream_t to) {
 
 std::string op_text(unsigned long long k) { return "op " + std::to_string(k) + " (0-based)"; }
 
-// what both forms check before anything is staged or launched
+}  // namespace
+
+// what both forms check before anything is staged or launched (I, J, V: host or device addresses)
 void update_check_args(dsa_mat* h, int32_t op, int32_t flags, const void* I, const void* J, const void* V, int64_t n) {
     if (h->fillmode || !h->has_major) fail(DSA_EMODE, "Cannot update stored values in fill mode");
     if (op != DSA_UPD_SET && op != DSA_UPD_ADD) fail(DSA_EARG, "update_values: op must be DSA_UPD_SET or DSA_UPD_ADD");
@@ -32,8 +33,6 @@ void update_check_args(dsa_mat* h, int32_t op, int32_t flags, const void* I, con
     if (n >= (int64_t(1) << UPD_K_BITS) || h->col.capacity() >= (int64_t(1) << UPD_K_BITS) || h->row.capacity() >= (int64_t(1) << UPD_K_BITS))
         fail(DSA_EARG, "update_values: more than 2^32 - 1 ops or slots");
 }
-
-}  // namespace
 
 // Everything of an update in front of its first write: both locates, each on its own stream, the claims, the resolve pass and one
 // wait.  The slots and winner flags are left in the scratch of the orientations for update_apply.
@@ -84,24 +83,6 @@ void get_batch_dev(dsa_mat* h, const int64_t* d_I, const int64_t* d_J, int64_t n
     if (n > 0 && (!d_I || !d_J || !d_out)) fail(DSA_EARG, "get_batch: an operand is NULL");
     LAUNCH("get_batch", launch_get_batch_dev(h->col.view(), d_I, d_J, n, d_out, d_found, h->col.stream));
 }
-
-// I, J, V in host memory: uploaded on the colmajor stream, which is drained before the rowmajor stream may read them
-UpdateStaging::UpdateStaging(dsa_mat* h_, int32_t op, int32_t flags, const int64_t* I, const int64_t* J, const double* V, int64_t n,
-                             bool want_missing) : h(h_), b(h_->col.stream) {
-    mat_flush(h);
-    update_check_args(h, op, flags, I, J, V, n);
-    if (n == 0) return;
-    hipStream_t s = h->col.stream;
-    const void* src[3] = {I, J, V};
-    for (int q = 0; q < 3; ++q) {
-        HIPCHK(pool_alloc(&b.p[q], (size_t)n * 8));
-        HIPCHK(hipMemcpyAsync(b.p[q], src[q], (size_t)n * 8, hipMemcpyHostToDevice, s));
-    }
-    if (want_missing) HIPCHK(pool_alloc(&b.p[3], (size_t)n));
-    HIPCHK(hipStreamSynchronize(s));
-}
-// the rowmajor stream may still read the staged triples (also after an error behind a launch); DevStaging drains the colmajor one
-UpdateStaging::~UpdateStaging() { if (h->has_major) (void)hipStreamSynchronize(h->row.stream); }
 
 }  // namespace host
 }  // namespace dsa

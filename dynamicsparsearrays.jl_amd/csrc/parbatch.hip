@@ -11,24 +11,22 @@
 //             PB_MAX_W slots (big rebalance, _extend!, _shrink!), or that are not vector writes, are BARRIERs.
 //   resolve   (the workgroup of k_plan that finishes last, found by a ticket — no launch of its own): d = min(first BARRIER,
 //             smallest j whose footprint overlaps the footprint of an EARLIER op).  Ops [0, d) are pairwise disjoint: each of
-//             them sees, when executed alone in order, exactly the state it was planned on.
-//   k_apply   (one wave per op): shift, write, occupancy update (atomics: footprints are disjoint in slots, not in 64-slot
+//             them sees, when executed alone in order, exactly the state it was planned on.  pb_resolve.h: one function per
+//             stage, on one LDS state.
+//   k_apply  (one wave per op): shift, write, occupancy update (atomics: footprints are disjoint in slots, not in 64-slot
 //             bitmap words), then the small-window pack + spread through the wave's LDS slice.
 //
-// The host (dsa_host.hip) applies the prefix in parallel and hands the op at d (and a growing chunk after it when the
+// The host (writes_host.hip) applies the prefix in parallel and hands the op at d (and a growing chunk after it when the
 // prefixes stay short, e.g. ascending appends) to the sequential sequencer.  Result: bit-identical to the sequential order.
+//
+// This file is the only translation unit; it includes two headers of its own.  pb_fpcheck.h: the footprint-check build
+// (-DDSA_FP_CHECK) — recorders, check kernels, and the fp_* hooks the kernels here call (empty in the default build).
+// pb_resolve.h: the resolve step.
 #include "wave_dev.h"
 #include "find_dev.h"
 
 namespace dsa {
-#ifdef DSA_PB_PROF
-__device__ unsigned long long g_pbprof[32];
-#define PBW(j_, code_) (sCutWhy[(j_)] = (unsigned char)(code_))
-#else
-#define PBW(j_, code_) ((void)0)
-#endif
-
-constexpr int PB_BLOCK = 256;                 // k_apply: 4 waves = 4 ops per workgroup (32 KB of LDS per wave)
+constexpr int PB_BLOCK = 256;                // k_apply: 4 waves = 4 ops per workgroup (32 KB of LDS per wave)
 constexpr int PL_BLOCK = 1024;                // k_plan: 16 waves = 16 ops per workgroup; the workgroup that finishes last resolves the round with
                                               // one thread per op (with 256 threads the chain walks of the resolve step were the longest part of a round)
 constexpr int PB_MAX_W_LOG2 = 11;
@@ -38,61 +36,35 @@ constexpr int PB_GMAX = ROUND_GMAX;           // ops planned per round at most (
 enum : int32_t { PB_NOOP = 0, PB_OVERWRITE = 1, PB_INS_R = 2, PB_INS_L = 3, PB_DELETE = 4, PB_BARRIER = 5, PB_NEWCOL = 6,
                  PB_DEFER = 7 /* written by the resolve step over the action of an op it defers: k_apply skips it */ };
 constexpr int64_t PB_PEND_MAX = TABLE_PEND_MAX;  // the sequencer imports, tables.hip merges the pending table entries
+constexpr size_t PB_WAVE_LDS = (size_t)PB_MAX_W * (sizeof(int64_t) + sizeof(double));      // dynamic LDS of one applying wave: the keys and values of its window
 
-// ---- footprint-check build (-DDSA_FP_CHECK; make libdsa_hip_fpcheck.so) -------------------------------------------------------------
-// The resolve step lets ops run side by side on the strength of their DECLARED footprints.  Three footprint-class defects hid behind green
-// suites for two rounds (Oracle and parity); this build makes the soundness of a round mechanical instead of argued:
-//   mode 1 (recorded sets)  the plan records what it literally scanned for its shift target (the occupancy runs of _nextemptypos /
-//            _previousemptypos) and every window whose cell count it consulted; the apply records the hull of every slot it wrote or
-//            re-read live.  k_fp_pre then re-derives the resolver's verdict by BRUTE FORCE, without its spatial hash: the final footprints of
-//            the prefix are pairwise disjoint, every scanned run lies inside the op's footprint, every counted window either lies inside it
-//            (and no other op of the prefix changes a bit there) or is the leaf of a leaf-accepted op whose thresholds hold for the count
-//            recounted from the bitmap plus / minus ALL changes the prefix makes in that leaf.  k_fp_post: what the apply touched lies inside
-//            the footprint.
-//   mode 2 (sequential shadow)  the prefix is applied one op after the other by ONE wave; before each op its plan is recomputed on the
-//            LIVE state and must equal the plan the round was resolved on (action, positions, accepted window, count when a rebalance
-//            follows): "each op sees exactly the state it was planned on", checked, for every semantic dependency at once (also the ones
-//            of the 64-ary find, whose literal probes are far outside any footprint).
-// A violation prints its details and raises RoundState::pad (the host fails the batch).  DSA_FP_REGRESS=1 / 2 re-introduce the two
-// resolver bugs of round 4 (the leaf walk of ONE hash cell; the footprint of a left-falling insert ending at p + 1), = 3 the one this build
-// found itself (a widened new column whose window ends on a hash-cell boundary is not chained in the next cell): the check must fire.
-#ifdef DSA_FP_CHECK
-constexpr int FP_MAXCNT = 12;
-struct FpRec {                                    // what ONE op of a round literally read (plan) and touched (apply)
-    int64_t rlo, rhi;                             // occupancy runs scanned for the shift target (1-based, inclusive; rlo > rhi: none)
-    int64_t tlo, thi;                             // slots written, bits changed, cells re-read live by the apply
-    int32_t ncnt, pad;
-    int32_t cnt[FP_MAXCNT][2];                    // windows whose cell count the plan consulted
-};
-struct FpIv { int32_t lo, hi; };                  // the FINAL footprint the resolve step used (after widening)
-static_assert(sizeof(FpRec) + sizeof(FpIv) <= FP_BYTES_PER_OP, "the host sizes the plan array for the records behind it");
-__shared__ FpRec g_fpw[16];                       // one recorder per wave of the workgroup (k_plan: 16, k_apply: 4, k_local_rounds: 8)
-__device__ __forceinline__ void fp_reset() {
-    if (lane_id() == 0) { FpRec& f = g_fpw[threadIdx.x >> 6]; f.rlo = INT64_MAX; f.rhi = 0; f.tlo = INT64_MAX; f.thi = 0; f.ncnt = 0; f.pad = 0; }
+// an op whose density scan stopped at its leaf: nothing but the leaf's COUNT ties it to the rest of the leaf (Plan::lo / hi then hold
+// the tight hull, see pb_plan_one)
+__device__ __forceinline__ bool pb_is_leaf_only(int32_t action, int64_t ws, int64_t we, int64_t seg, int32_t count) {
+    if (action == PB_NEWCOL) return (count & 0x80) != 0;
+    return (action == PB_INS_R || action == PB_INS_L || action == PB_DELETE) && we - ws + 1 == seg;
 }
-__device__ __forceinline__ void fp_pos(int64_t a, int64_t b) {
-    if (lane_id() == 0 && a <= b) { FpRec& f = g_fpw[threadIdx.x >> 6]; if (a < f.rlo) f.rlo = a; if (b > f.rhi) f.rhi = b; }
+// slot whose occupancy the op changes, and by how much
+__device__ __forceinline__ int64_t pb_changed_slot(int32_t action, int64_t pos, int64_t aux) { return action == PB_DELETE ? pos : aux; }
+// (a new column accepted by its leaf fills two gaps — Plan::aux and the end of its tight hull; one whose footprint is its window counts
+// for nobody: no leaf-only op can share that window)
+__device__ __forceinline__ int pb_delta(int32_t action, bool leaf_only = false) {
+    return (action == PB_INS_R || action == PB_INS_L) ? 1 : (action == PB_DELETE ? -1 : ((action == PB_NEWCOL && leaf_only) ? 1 : 0));
 }
-__device__ __forceinline__ void fp_touch(int64_t a, int64_t b) {
-    if (lane_id() == 0 && a <= b) { FpRec& f = g_fpw[threadIdx.x >> 6]; if (a < f.tlo) f.tlo = a; if (b > f.thi) f.thi = b; }
-}
-__device__ __forceinline__ void fp_cnt(int64_t a, int64_t b) {
-    if (lane_id() == 0) {
-        FpRec& f = g_fpw[threadIdx.x >> 6];
-        if (f.ncnt < FP_MAXCNT) { f.cnt[f.ncnt][0] = (int32_t)a; f.cnt[f.ncnt][1] = (int32_t)b; }
-        f.ncnt += 1;
+// the FULL footprint of a plan where nobody keeps count per leaf (the local rounds): a leaf-only op is widened from its tight hull to its
+// window; a new column without a fallback window (level 0x7f) has none to be widened to and takes the whole array
+__device__ __forceinline__ void pb_full_footprint(const Plan& q, int64_t seg, int64_t capacity, int64_t& lo, int64_t& hi) {
+    lo = q.lo; hi = q.hi;
+    if (lo <= hi && pb_is_leaf_only(q.action, q.ws, q.we, seg, q.count)) {
+        if (q.action == PB_NEWCOL && (q.count & 0x7f) == 0x7f) { lo = 1; hi = capacity; }
+        else { if (q.ws < lo) lo = q.ws; if (q.we > hi) hi = q.we; }
     }
 }
-#else
-__device__ __forceinline__ void fp_reset() {}
-__device__ __forceinline__ void fp_pos(int64_t, int64_t) {}
-__device__ __forceinline__ void fp_touch(int64_t, int64_t) {}
-__device__ __forceinline__ void fp_cnt(int64_t, int64_t) {}
-#endif
-#ifndef DSA_FP_REGRESS
-#define DSA_FP_REGRESS 0
-#endif
+}  // namespace dsa
 
+#include "pb_fpcheck.h"      // fp_*: the hooks of the footprint-check build (empty in the default build)
+
+namespace dsa {
 __device__ __forceinline__ uint64_t pb_occ_load(const uint64_t* occ, int64_t w) {
     // L2-served load: other waves of the same launch update neighbouring bits of shared words with device-scope atomics
     return __hip_atomic_load(occ + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -306,57 +278,25 @@ __device__ Plan pb_plan_one(KeyArr keys, const double* vals, const uint64_t* occ
     if (pl.action == PB_BARRIER) pl.count = why;
     return pl;
 }
+}  // namespace dsa
 
-// an op whose density scan stopped at its leaf: nothing but the leaf's COUNT ties it to the rest of the leaf (Plan::lo / hi then hold
-// the tight hull, see pb_plan_one)
-__device__ __forceinline__ bool pb_is_leaf_only(int32_t action, int64_t ws, int64_t we, int64_t seg, int32_t count) {
-    if (action == PB_NEWCOL) return (count & 0x80) != 0;
-    return (action == PB_INS_R || action == PB_INS_L || action == PB_DELETE) && we - ws + 1 == seg;
-}
-// slot whose occupancy the op changes, and by how much
-__device__ __forceinline__ int64_t pb_changed_slot(int32_t action, int64_t pos, int64_t aux) { return action == PB_DELETE ? pos : aux; }
-// (a new column accepted by its leaf fills two gaps — Plan::aux and the end of its tight hull; one whose footprint is its window counts
-// for nobody: no leaf-only op can share that window)
-__device__ __forceinline__ int pb_delta(int32_t action, bool leaf_only = false) {
-    return (action == PB_INS_R || action == PB_INS_L) ? 1 : (action == PB_DELETE ? -1 : ((action == PB_NEWCOL && leaf_only) ? 1 : 0));
-}
+#include "pb_resolve.h"      // Round, Cells, Resolve and the resolve_* stages
 
+namespace dsa {
+// One wave per op plans it and publishes the plan; the workgroup that finishes last (a ticket; no second and third launch per round)
+// resolves the round: the stages of pb_resolve.h in order, on one LDS state.  The __syncthreads() between two stage calls is the barrier
+// that separates those stages; tk0 .. tr3 are the stage boundaries the dev profile (-DDSA_PB_PROF) sums cycles between.
 __global__ __launch_bounds__(PL_BLOCK) void k_plan(const DevBufs* bufs, const Ctl* ctl, const Op* ops, RoundState* rs, Plan* plans) {
     // the round's window of ops comes from the device-resident cursor: rounds are enqueued back to back without host syncs
-    [[maybe_unused]] const long long tk0 = clock64();      // dev profile, -DDSA_PB_PROF
+    const long long tk0 = clock64();
     if (rs->stop) return;
     const DevBufs db = *bufs;
     const KeyArr keys{db.keys, db.wide, 0};
-    const double* vals = db.vals; const uint64_t* occ = db.occ;
-    const int64_t* sems = db.sems; const int64_t* col_keys = db.col_keys; const uint8_t* col_live = db.col_live;
-    // scalars of the control block the resolve step needs: requested now, so that the last workgroup does not start with a dependent
-    // round trip to memory (~2 us across XCDs)
-    const int64_t cap0 = ctl->capacity, seg0 = ctl->segment_capacity, lo00 = ctl->lo[0], hi00 = ctl->hi[0];
-    // (the fields of the round state the resolve step folds at its very end: read now, scalar loads, instead of as dependent round trips of one
-    // thread behind the last barrier — nobody writes them while this kernel runs)
-    const int ema_prev = rs->ema, min_prefix = rs->min_prefix;
-    const int64_t rounds_prev = rs->rounds, par_ops_prev = rs->par_ops, deferred_prev = rs->deferred;
-    // the window of this round (written by the previous round's resolve step, committed by this one's): the pending ops — deferred by
-    // earlier rounds, ascending op index — followed by fresh ops
-    const int64_t i0 = rs->cursor_n;
-    const int np = rs->np_n, cur = rs->cur_n, run_ahead_rs = rs->run_ahead, drain = rs->drain;
-    const PendOp* pend = db.pend + (size_t)cur * PB_GMAX;
-    const int64_t left = drain ? 0 : (rs->limit - i0 > 0 ? rs->limit - i0 : 0);
-    int G;
-    {
-        int Gt = rs->G > np ? rs->G : np;                 // the pending ops are always part of the window
-        if (Gt > PB_GMAX) Gt = PB_GMAX;
-        const int64_t avail = (int64_t)np + left;
-        G = (int)(avail < Gt ? avail : Gt);
-    }
+    const Round R = pb_round_load(db, ctl, rs);                        // what the resolve step needs is requested NOW, in front of the plan (see Round)
+    const int G = R.G;
     const int w = blockIdx.x * (PL_BLOCK / 64) + (threadIdx.x >> 6);
-    // (short windows — a small, fast-growing array whose ops collide all the time: config 5's first batches plan ~60 ops a round — are the
-    //  prefix rule's: sealing costs the resolve step more than the few ops behind the first conflict are worth; pending ops keep the mode on)
-    const int run_ahead = run_ahead_rs && (G >= 128 || np > 0) ? 1 : 0;
-    auto op_index = [&](int q) -> int64_t { return q < np ? pend[q].op : i0 + (q - np); };
     if (w < G) {
-    const Plan pl = pb_plan_one(keys, vals, occ, sems, col_keys, col_live, ctl, ops[op_index(w)], w, PB_MAX_W);
-    {
+        const Plan pl = pb_plan_one(keys, db.vals, db.occ, db.sems, db.col_keys, db.col_live, ctl, ops[R.op_index(w)], w, PB_MAX_W);
         // device-scope (write-through) stores: the workgroup that resolves the round may sit on another XCD; a release FENCE per
         // workgroup instead would write back that XCD's L2 (measured slower).  Seven lanes store one 8-byte field each: ONE store
         // instruction for the 56-byte plan instead of eight by lane 0.
@@ -367,623 +307,58 @@ __global__ __launch_bounds__(PL_BLOCK) void k_plan(const DevBufs* bufs, const Ct
                               : (int64_t)((uint64_t)(uint32_t)pl.count | ((uint64_t)(uint32_t)pl.action << 32));
             __hip_atomic_store(reinterpret_cast<int64_t*>(plans + w) + l, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-#ifdef DSA_FP_CHECK
-        __builtin_amdgcn_wave_barrier();
-        if (l == 0) reinterpret_cast<FpRec*>(plans + PB_GMAX)[w] = g_fpw[threadIdx.x >> 6];      // read by k_fp_pre, the next kernel of the round
-#endif
+        fp_publish_plan(plans, w);
     }
-    }
-    // ---- resolve, by the workgroup that finishes last (a ticket; no second and third launch per round): folds the previous round's
-    //      prefix into the cursor and decides this round's prefix d = min(first BARRIER, smallest j whose footprint overlaps the footprint
-    //      of an earlier op): ops [0, d) are pairwise disjoint, each sees exactly the state it was planned on.  k_apply works on (cursor, d).
-    __shared__ int sLast, sC, sB, sSumDn, sSumRebN;
-    __shared__ unsigned int sSumRebW;
-    // footprints as 32-bit pairs (arrays beyond 2^31 slots: in units of 2^shift slots, rounded outwards — conservative)
-    struct alignas(8) Iv { int32_t lo, hi; };
-    __shared__ Iv sIv[PB_GMAX + 8];
+    // ---- the ticket ------------------------------------------------------------------------------------------------------------------
+    __shared__ Resolve S;
     __builtin_amdgcn_s_waitcnt(0);                                     // the plan stores of this wave have been acknowledged at device scope
-    [[maybe_unused]] const long long tk1 = clock64();
+    const long long tk1 = clock64();
     __syncthreads();
     if (threadIdx.x == 0) {
         const unsigned t = __hip_atomic_fetch_add(&rs->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sLast = t == gridDim.x - 1 ? 1 : 0;
-        sC = G; sB = G; sSumDn = 0; sSumRebN = 0; sSumRebW = 0u;
+        S.sLast = t == gridDim.x - 1 ? 1 : 0;
+        S.sC = G; S.sB = G; S.sSumDn = 0; S.sSumRebN = 0; S.sSumRebW = 0u;
     }
     __syncthreads();
-    if (!sLast) return;
-    [[maybe_unused]] const long long tr0 = clock64();      // dev profile, -DDSA_PB_PROF
-    const int tid = threadIdx.x;
-    int shift = 0;
-    while ((cap0 >> shift) > 0x7fffffffll) ++shift;
-    // Ops accepted by their LEAF move nothing but their shifted run; what else ties two of them together is the leaf's cell COUNT
-    // (src/pma.jl:118-126).  If the leaf accepts the count whatever subset of the window's ops has changed it — count0 + all inserts
-    // into the leaf <= hi[0], count0 - all deletes >= lo[0] — every order of those ops takes the same decisions, and the op's
-    // footprint is just its tight hull (predecessor .. filled gap): two inserts into one 16-slot leaf no longer collide, only
-    // overlapping runs do.  Otherwise the footprint is widened to the leaf, as for every op with a wider window.  (Round 2 always
-    // used the leaf: conflict-free prefixes of ~250 ops on a 2^21-slot array, birthday-bound by 16-slot footprints.)
-    // The sums per leaf come from a walk of the same spatial hash the overlap test uses: an op that changes the count of leaf L
-    // has the changed slot in its hull, so it is chained in the cell of L.
-    __shared__ int32_t sChg[PB_GMAX];                                  // slot whose occupancy the op changes (0: none), exact: tight mode needs shift == 0
-    __shared__ int32_t sChg2[PB_GMAX];                                 // the second gap a leaf-accepted new column fills (0: none)
-    __shared__ signed char sDl[PB_GMAX];                               // +1 insert, -1 delete, 0 otherwise
-    __shared__ unsigned char sLvl[PB_GMAX];                            // level of the window a leaf-only op falls back to (0 unless a new column)
-    __shared__ signed char sDn[PB_GMAX];                               // what an insert / delete adds to Ctl::nb_elements (a new column counts for itself in k_apply)
-    __shared__ unsigned short sRebW[PB_GMAX];                          // slots of the window an insert / delete rebalances (0: none)
-    __shared__ signed char sCnt02[PB_GMAX];                            // cells of the NEXT leaf if the op needs that one to accept as well (-1: no)
-    __shared__ int32_t sLeafLo[PB_GMAX];                               // first slot of the op's leaf if it is leaf-only, else 0
-    __shared__ int32_t sCnt0[PB_GMAX];                                 // cells of that leaf before the round
-    // run-ahead: ops that conflict with an earlier op (sConf), ops deferred because they lie in the sealed zone of an earlier deferred op
-    // (sDefer), the zone a deferred op is sealed in (sZid -> sZone; 0: none), which ops are plain writes (sSimple: nothing but a hull and
-    // their leaf's count ties them to the array), the compact list of the conflicting ops
-    constexpr int RA_MAX_CONF = 96;                                    // conflicting ops a round seals at most (more: the prefix rule)
-    __shared__ unsigned char sAct[PB_GMAX], sConf[PB_GMAX], sDefer[PB_GMAX], sSimple[PB_GMAX];
-    __shared__ unsigned char sZid[PB_GMAX];                            // zone the op is sealed in: 1 + index into the zone table (0: none)
-    struct Zone { int32_t lo, mid, hi; };                              // [A, B] + [B + 1, B + W]: lo = A, mid = B, hi = B + W (lo = 0: no zone)
-    __shared__ Zone sZone[RA_MAX_CONF];                                // ... of the q-th conflicting op (owner sConfList[q])
-    __shared__ int sConfList[RA_MAX_CONF];
-    __shared__ int sNConf, sNApplied, sNDeferred, sFault;
-    __shared__ uint32_t sScan[PL_BLOCK / 64];
-    const int64_t seg = seg0;
-    // (spatial hash of the overlap test below; emptied here, under the latency of the plan loads, behind the same barrier)
-    // Cell size: 2 * PB_MAX_W slots on large arrays; on a small array ~1/128 of it (not below the leaf, not below 64 slots) — with 4096-slot
-    // cells every op of a 32 k-slot array is chained into the same few buckets and each walk visits the whole window (config 5's first
-    // batch: 26 k cycles of the resolve step for 83 planned ops).  Footprints over more than two cells go to the list of wide ops.
-    constexpr int CS_MAX = PB_MAX_W_LOG2 + 1, NB = 4096;
-    int CS = CS_MAX;
-    {
-        const int lgcap = 63 - __clzll((unsigned long long)(cap0 > 1 ? cap0 : 1)), lgseg = 63 - __clzll((unsigned long long)(seg > 1 ? seg : 1));
-        int c = lgcap - 7;
-        if (c < lgseg) c = lgseg;
-        if (c < 6) c = 6;
-        if (shift == 0 && c < CS_MAX) CS = c;
-    }
-    __shared__ int sHead[NB];
-    __shared__ int sNext[2 * PB_GMAX];
-    __shared__ int sWide[PB_GMAX];
-    __shared__ int sNWide;
-    __shared__ int64_t sLoH[24], sHiH[24];                            // density bounds of the lower levels (run-ahead: the sealed zones)
-    __shared__ int sMinConf;
-#ifdef DSA_PB_PROF
-    __shared__ unsigned char sCutWhy[PB_GMAX + 8];      // dev profile: what cut the round at op j (see dsa_dbg_pbprof_dump)
-#endif
-    if (run_ahead && tid >= PL_BLOCK - 24) { const int q = tid - (PL_BLOCK - 24); sLoH[q] = ctl->lo[q]; sHiH[q] = ctl->hi[q]; }      // (the LAST wave: fewest plans to load)
-    for (int k = tid; k < NB; k += PL_BLOCK) sHead[k] = -1;
-    if (tid == 0) { sNWide = 0; sNConf = 0; sNApplied = 0; sNDeferred = 0; sFault = 0; sMinConf = INT32_MAX; }
-    for (int j = tid; j < G + 8 && j < PB_GMAX; j += PL_BLOCK) { sConf[j] = 0; sDefer[j] = 0; sSimple[j] = 0; sZid[j] = 0; sAct[j] = PB_BARRIER; }
-    if (tid < RA_MAX_CONF) { sZone[tid].lo = 0; sZone[tid].mid = 0; sZone[tid].hi = 0; }
-    for (int j = tid; j < G + 8; j += PL_BLOCK) {
-        Iv iv{INT32_MAX, INT32_MIN};                                   // an empty footprint overlaps nothing
-        if (j < G) {
-            const Plan* q = plans + j;
-            const int64_t lo = __hip_atomic_load(&q->lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int64_t hi = __hip_atomic_load(&q->hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int64_t ws = __hip_atomic_load(&q->ws, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int64_t we = __hip_atomic_load(&q->we, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int64_t pos = __hip_atomic_load(&q->pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int64_t aux = __hip_atomic_load(&q->aux, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int32_t cnt = __hip_atomic_load(&q->count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int32_t act = __hip_atomic_load(&q->action, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (act == PB_BARRIER) atomicMin(&sB, j);
-            sAct[j] = (unsigned char)act;
-            const bool leaf_only = pb_is_leaf_only(act, ws, we, seg, cnt);
-            const int dl = pb_delta(act, leaf_only);
-            const int64_t chg = pb_changed_slot(act, pos, aux);
-            const bool newcol = act == PB_NEWCOL;
-            sDl[j] = (signed char)dl;
-            sChg[j] = (dl != 0 && shift == 0) ? (int32_t)chg : 0;
-            sChg2[j] = (newcol && leaf_only && shift == 0) ? (int32_t)hi : 0;
-            sLvl[j] = newcol ? (unsigned char)(cnt & 0x7f) : 0;
-            const bool insdel = act == PB_INS_R || act == PB_INS_L || act == PB_DELETE;
-            sDn[j] = insdel ? (signed char)(act == PB_DELETE ? -1 : 1) : (signed char)0;
-            sRebW[j] = (insdel && we - ws + 1 != seg) ? (unsigned short)(we - ws + 1) : (unsigned short)0;      // (<= PB_MAX_W)
-            int64_t flo = lo, fhi = hi;
-            if (leaf_only && shift == 0) {
-                sLeafLo[j] = newcol ? (int32_t)((pos / seg) * seg + 1) : (int32_t)ws;      // (new column: the leaf of pos + 1, its semaphore)
-                sCnt0[j] = newcol ? ((cnt >> 8) & 0x7f) : cnt - ((chg >= ws && chg <= we) ? dl : 0);
-                sCnt02[j] = (newcol && (cnt & 0x8000)) ? (signed char)((cnt >> 16) & 0x7f) : (signed char)-1;
-            } else {
-                sLeafLo[j] = 0; sCnt0[j] = 0;
-                if (leaf_only && lo <= hi) { if (ws < flo) flo = ws; if (we > fhi) fhi = we; }      // (arrays beyond 2^31 slots: always the window)
-            }
-            if (flo <= fhi) { iv.lo = (int32_t)(flo >> shift); iv.hi = (int32_t)(fhi >> shift); }
-        }
-        sIv[j] = iv;
-    }
+    if (!S.sLast) return;
+    // ---- resolve, by the workgroup that finishes last --------------------------------------------------------------------------------
+    const long long tr0 = clock64();
+    const Cells hc = pb_cells(R.cap0, R.seg0);
+    resolve_load(S, R, hc, ctl, plans);
     __syncthreads();
-    [[maybe_unused]] const long long tr1 = clock64();
-    // smallest j that overlaps an earlier op: a spatial hash instead of all pairs (G^2 / 2 tests by one workgroup cost 7 .. 36 us).
-    // Cells of 2 * PB_MAX_W slots; a footprint of up to that many slots lies in one or two cells and is chained into their buckets, then every op
-    // walks the chains of its own cells and tests the earlier ops it meets there exactly.  The (rare) longer footprints are tested
-    // against everybody.  Ops at or behind the first BARRIER do not matter.
-    const int Gc = sB < G ? sB : G;
-    auto bucket = [](int cell) { return (int)(((uint32_t)cell * 0x9E3779B1u) >> 20) & (NB - 1); };
-    for (int j = tid; j < Gc; j += PL_BLOCK) {
-        const Iv iv = sIv[j];
-        if (iv.lo > iv.hi) continue;
-        const int c0 = iv.lo >> CS, c1 = iv.hi >> CS;
-        if (c1 - c0 > 1) { sWide[atomicAdd(&sNWide, 1)] = j; continue; }
-        for (int k = 0; k <= c1 - c0; ++k) { const int e = 2 * j + k; sNext[e] = atomicExch(&sHead[bucket(c0 + k)], e); }
-    }
+    const long long tr1 = clock64();
+    const int Gc = S.sB < G ? S.sB : G;                                // ops at or behind the first BARRIER do not matter
+    resolve_chain(S, hc, Gc);
     __syncthreads();
-    {   // leaf-only ops: inserts into / deletes from their leaf by ANY op of the window in front of the first BARRIER (themselves
-        // included); the leaf must accept every count in between, else the footprint is widened to the leaf
-        const int64_t lo0 = lo00, hi0 = hi00;
-        const int nwide0 = sNWide;
-        const int tight_mask = rs->tight;
-        bool widen[PB_GMAX / PL_BLOCK];
-#pragma unroll
-        for (int u = 0; u < PB_GMAX / PL_BLOCK; ++u) {
-            const int j = tid + u * PL_BLOCK;
-            widen[u] = false;
-            if (j >= Gc) continue;
-            const int32_t l0 = sLeafLo[j];
-            if (l0 == 0) continue;
-            const Iv me = sIv[j];
-            const int c0 = me.lo >> CS, c1 = me.hi >> CS;
-            if (c1 - c0 > 1) {                                           // (a tight hull over three cells: keep it simple)
-                // ... a new column without a fallback window (level 0x7f) has nothing to be widened to: W = seg << 0x7f below is undefined.
-                // The prefix ends in front of it, like further down
-                if (sLvl[j] == 0x7f) { PBW(j, 9); atomicMin(&sC, j); } else widen[u] = true;
-                continue;
-            }
-            // does the leaf [a, a + seg) with c cells before the round accept every count the window's ops can leave in it?
-            auto accepts = [&](int32_t a, int64_t c) {
-                const int32_t b = a + (int32_t)seg - 1;
-                int ins = 0, del = 0;
-                // The cells the leaf lies in.  Slots are 1-based, leaves start at k * seg + 1: the LAST slot of a leaf is a multiple of seg
-                // and, once in 2^CS / seg leaves, the first slot of the next cell — an op that changes that slot is chained THERE, not in
-                // the cell of the leaf's first slot (round 2-4 walked only that one: two deletes from one leaf, one of them of its last
-                // slot 237568 = 116 * 2048, ran in one round and left the leaf empty without the rebalance; tools/fuzz.py, FUZZ_BIG seed 91098).
-                const int cl0 = a >> CS, cl1 = DSA_FP_REGRESS == 1 ? cl0 : b >> CS;
-                for (int cl = cl0; cl <= cl1; ++cl) {
-                    if (cl != cl0 && bucket(cl) == bucket(cl0)) break;      // the same chain again
-                    for (int e = sHead[bucket(cl)]; e >= 0; e = sNext[e]) {
-                        const int i = e >> 1;
-                        const int first = sIv[i].lo >> CS;
-                        if ((e & 1) && first == cl) continue;               // an op chained twice into this bucket's cell is counted once
-                        if (cl != cl0 && first == cl0) continue;            // ... and so is an op whose hull lies in both cells of the leaf
-                        const int32_t ch = sChg[i], ch2 = sChg2[i];
-                        if (ch >= a && ch <= b) { if (sDl[i] > 0) ++ins; else ++del; }
-                        if (ch2 >= a && ch2 <= b) ++ins;
-                    }
-                }
-                for (int w2 = 0; w2 < nwide0; ++w2) {
-                    const int i = sWide[w2];
-                    const int32_t ch = sChg[i], ch2 = sChg2[i];
-                    if (ch >= a && ch <= b) { if (sDl[i] > 0) ++ins; else ++del; }
-                    if (ch2 >= a && ch2 <= b) ++ins;
-                }
-                return c + ins <= hi0 && c - del >= lo0;
-            };
-            bool ok = accepts(l0, sCnt0[j]);
-            if (ok && sCnt02[j] >= 0) ok = accepts(l0 + (int32_t)seg, sCnt02[j]);
-            widen[u] = !ok || !((tight_mask >> (sChg2[j] != 0 ? 1 : 0)) & 1);
-            // a new column without a fallback window (level 0x7f) cannot be widened: the prefix ends in front of it (alone at the head
-            // of the next round it is handed to the sequencer — d = 0 stops the rounds)
-            if (widen[u] && sLvl[j] == 0x7f) { widen[u] = false; PBW(j, 9); atomicMin(&sC, j); }
-            // "simple" (run-ahead): a leaf-accepted right insert / delete that keeps its tight hull
-            if (!widen[u] && (sAct[j] == PB_INS_R || sAct[j] == PB_DELETE)) sSimple[j] = 1;
-        }
-        __syncthreads();                                               // every walk has read the tight hulls
-#pragma unroll
-        for (int u = 0; u < PB_GMAX / PL_BLOCK; ++u) {
-            const int j = tid + u * PL_BLOCK;
-            if (j < Gc && widen[u]) {
-                Iv me = sIv[j];
-                // back to the window the plan was accepted in: the leaf, or the level-H window of a new column
-                const int32_t W = (int32_t)seg << sLvl[j];
-                const int32_t a = ((sLeafLo[j] - 1) / W) * W + 1, b = a + W - 1;
-                const int oc0 = me.lo >> CS, oc1 = me.hi >> CS;                  // the cells the op is chained in (its tight hull)
-                if (a < me.lo) me.lo = a;
-                if (b > me.hi) me.hi = b;
-                // The widened interval can reach into a cell the op is not chained in — slots are 1-based, an aligned window ends on a multiple
-                // of its size, e.g. [516081, 516096] with 516096 = 126 * 4096 the first slot of the next cell.  For a leaf-accepted insert /
-                // delete that is harmless (it writes only its tight hull; the widening stands for the count it read), but a widened NEW COLUMN
-                // scans and REBALANCES its whole window when it is applied: a later op that starts on that last slot walked only its own cell
-                // and ran in the same round (rounds 3-4; found by the footprint-check build of round 5, tools/fuzz.py run_same_leaf_matrix,
-                // first seed 9101: "op 52 writes inside [516081,516096]; the later op 54 has the footprint [516096,516098]").  Such an op is
-                // tested against everybody, like the footprints longer than two cells.
-                if (DSA_FP_REGRESS != 3 && ((me.lo >> CS) != oc0 || (me.hi >> CS) != oc1)) sWide[atomicAdd(&sNWide, 1)] = j;
-                sIv[j] = me;
-            }
-        }
-    }
+    resolve_leaf_counts(S, R, hc, Gc, rs);
     __syncthreads();
-    for (int j = tid; j < Gc; j += PL_BLOCK) {
-        const Iv me = sIv[j];
-        if (me.lo > me.hi) continue;
-        const int c0 = me.lo >> CS, c1 = me.hi >> CS;
-        if (c1 - c0 > 1) continue;
-        bool hit = false;
-        for (int k = 0; k <= c1 - c0; ++k)
-            for (int e = sHead[bucket(c0 + k)]; e >= 0; e = sNext[e]) {
-                const int i = e >> 1;
-                const Iv o = sIv[i];
-                hit = hit | ((i < j) & (o.lo <= me.hi) & (me.lo <= o.hi));
-            }
-        if (hit) { if (run_ahead) { sConf[j] = 1; atomicMin(&sMinConf, j); } else { PBW(j, 1); atomicMin(&sC, j); } }
-    }
+    resolve_overlaps(S, R, hc, Gc);
     __syncthreads();
-    const int nwide = sNWide;
-    for (int w = 0; w < nwide; ++w) {
-        const int j = sWide[w];
-        const Iv me = sIv[j];
-        for (int i = tid; i < Gc; i += PL_BLOCK) {
-            const Iv o = sIv[i];
-            if (i != j && o.lo <= me.hi && me.lo <= o.hi) { if (run_ahead) { sConf[i > j ? i : j] = 1; atomicMin(&sMinConf, i > j ? i : j); } else { PBW(i > j ? i : j, 1); atomicMin(&sC, i > j ? i : j); } }
-        }
-    }
-    __syncthreads();
-    [[maybe_unused]] const long long tr2 = clock64();
-    // Sealing costs the resolving workgroup a few dependent round trips to memory per round; it does not pay when the first conflict
-    // sits in the last eighth of the window anyway (a long prefix: the array is large against the window): the prefix rule then
-    if (run_ahead && sMinConf != INT32_MAX && sMinConf >= Gc - (Gc >> 3)) {
-        if (tid == 0) { PBW(sMinConf, 2); atomicMin(&sC, sMinConf); }
-        __syncthreads();
-    } else
-    if (run_ahead && sMinConf != INT32_MAX) {
-        // ---- run-ahead: which conflicting ops can be DEFERRED without holding back the ops behind them --------------------------------
-        // An op j that conflicts with an earlier one is deferred to the next round.  Ops behind it may still run in THIS round if nothing
-        // that j can touch when it is finally executed — on the state its earlier partners leave, which is not the state it was planned
-        // on — is theirs.  j is SEALED in a zone Z' = [A, B] + [B + 1, B + W]: the aligned window of some level h (W = seg << h slots,
-        // 64 <= W <= RA_MAX_W) that holds j's footprint and the footprints of the earlier ops it overlaps, plus the window to its right,
-        // such that
-        //   (0) more than D cells lie between A and the leftmost op inside (a predecessor moves left by one cell per deleted cell: it
-        //       stays inside);
-        //   (1) every op of the round's window that touches Z' lies inside [A, B] and is a plain write (overwrite, missing-key delete,
-        //       right-shifting insert, delete; whatever window <= [A, B] its density scan was planned to rebalance) or a new column IN
-        //       FRONT of j (applied in this round: a semaphore + its first element, two inserts): I potential inserts (every op with a
-        //       value, two per new column), D potential deletes (every op without);
-        //   (2) both windows accept at level h whatever those ops do: lo[h] <= c - D and c + I <= hi[h] for the cell counts c of
-        //       [A, B] and of [B + 1, B + W]: no density scan at a position inside Z' climbs above level h, rebalances stay inside;
-        //   (3) the right window keeps more than I + 1 gaps (W - hi[h] >= I + 2): an insert position can drift right by one slot per
-        //       earlier insert, to B + 1 + I at most, and a gap is left beyond it: every shifted run ends inside Z', nobody takes the
-        //       left branch of _insert!.
-        // So whatever happens in Z' from now on stays in Z', and Z' is touched by nobody else: ops behind j that lie inside [A, B] are
-        // deferred with it (in order), ops that touch Z' otherwise end the round in front of them (prefix rule from there), and
-        // everything else is applied.  The zone travels with the pending op (PendOp); when the op is applied its footprint must lie
-        // inside it — checked below, a violation fails the batch instead of diverging from the sequential order.  Whatever cannot be
-        // proven (no level fits, a new column or a left-shifting insert nearby, arrays beyond 2^31 slots) cuts the round at j.
-        constexpr int RA_MAX_W = 1024, RA_MAX_DEL = 8;
-        for (int j = tid; j < Gc; j += PL_BLOCK) {
-            const int a = sAct[j];
-            sSimple[j] = (a == PB_OVERWRITE || a == PB_NOOP || a == PB_INS_R || a == PB_DELETE) ? 1 : 0;      // "plain write"
-            if (sConf[j]) { const int q = atomicAdd(&sNConf, 1); if (q < RA_MAX_CONF) sConfList[q] = j; }
-        }
-        __syncthreads();
-        // (a window full of conflicts — hammering one leaf, a tiny array — is the prefix rule's: most zones would not hold anyway)
-        const int nconf = sNConf > RA_MAX_CONF ? 0 : sNConf;
-        if (sNConf > RA_MAX_CONF && tid == 0) { PBW(sMinConf, 3); atomicMin(&sC, sMinConf); }
-        // visits every op of the window whose footprint overlaps [a, b] (an op in two cells of the walk once; a widened op that is also in
-        // the list of wide ops twice — the counts below are upper bounds)
-        auto for_overlapping = [&](int64_t a, int64_t b, auto fn) {
-            const int ca = (int)(a >> CS), cb = (int)(b >> CS);
-            for (int cl = ca; cl <= cb; ++cl)
-                for (int e = sHead[bucket(cl)]; e >= 0; e = sNext[e]) {
-                    const int i = e >> 1;
-                    const Iv o = sIv[i];
-                    const int ci = (o.lo >> CS) + (e & 1);                 // the cell this entry stands for
-                    if (ci != cl) continue;                               // (another cell of the same bucket)
-                    if ((e & 1) && (o.lo >> CS) >= ca) continue;          // the op's first cell lies in the walked range too: visited there
-                    if (o.lo <= b && a <= o.hi) fn(i);
-                }
-            const int nw = sNWide;
-            for (int q = 0; q < nw; ++q) { const int i = sWide[q]; const Iv o = sIv[i]; if (o.lo <= b && a <= o.hi) fn(i); }
-        };
-        // one WAVE per conflicting op, ONE pass for all candidate levels: every zone a level could offer lies inside R = the aligned window
-        // of the widest level (RA_MAX_W slots) plus the window to its right.  Lane 0 walks the hash chains of R once and lists the ops it
-        // meets (one per lane from then on), lanes 0..31 load R's occupancy words in one round and a prefix sum over their popcounts
-        // gives the cell count of any aligned window; the levels are then tried narrowest first without touching memory again.  (Round 6's
-        // first form walked the chains and loaded the words once per level: 13-47 k cycles of the resolve step for 1-7 conflicts.)
-        {
-            const int lane = tid & 63, wave = tid >> 6;
-            __shared__ int sSealList[PL_BLOCK / 64][64];
-            for (int q = wave; q < nconf; q += PL_BLOCK / 64) {
-                const int j = sConfList[q];
-                const Iv me = sIv[j];
-                bool ok = shift == 0 && sSimple[j] && me.lo <= me.hi && me.lo >= 1;
-                int64_t A = 0, B = 0, W = 0;
-                int64_t a = me.lo, b = me.hi;
-                if (ok && lane == 0)
-                    for_overlapping(me.lo, me.hi, [&](int i) { if (i < j) { const Iv o = sIv[i]; if (o.lo < a) a = o.lo; if (o.hi > b) b = o.hi; } });
-                a = __shfl(a, 0, 64); b = __shfl(b, 0, 64);
-                int hmin = -1, hmax = -1, n = 0;
-                for (int h = 0; h < MAX_LEVELS; ++h) {
-                    const int64_t Wh = seg << h;
-                    if (Wh < 64) continue;
-                    if (Wh > RA_MAX_W) break;
-                    if (hmin < 0) hmin = h;
-                    hmax = h;
-                }
-                if (ok && hmax >= 0) {
-                    ok = false;
-                    const int64_t Wx = seg << hmax;
-                    const int64_t Ax = ((a - 1) / Wx) * Wx + 1;
-                    const int64_t Rhi = Ax + 2 * Wx - 1 < cap0 ? Ax + 2 * Wx - 1 : cap0;          // R = [Ax, Rhi]: whole words (64 | Wx, 64 | cap0)
-                    if (lane == 0) for_overlapping(Ax, Rhi, [&](int i) { if (n < 64) sSealList[wave][n] = i; ++n; });
-                    n = __shfl(n, 0, 64);
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    // the ops that touch R, one per lane (more than 64: nothing is proven, the round ends in front of j)
-                    Iv o{INT32_MAX, INT32_MIN};
-                    bool osimple = false, oins = false, onew = false;
-                    if (n <= 64 && lane < n) {
-                        const int i = sSealList[wave][lane];
-                        o = sIv[i]; osimple = sSimple[i] != 0; oins = sAct[i] == PB_OVERWRITE || sAct[i] == PB_INS_R;
-                        // an EARLIER new column (applied in this round — if it conflicted itself the round would end in front of it): a
-                        // semaphore and its first element, two right-shifting inserts as far as the zone is concerned
-                        onew = sAct[i] == PB_NEWCOL && i < j;
-                    }
-                    // the occupancy words of R and the inclusive prefix sum of their popcounts (lane t <-> word t of R)
-                    const int64_t w0 = (Ax - 1) >> 6;
-                    const int nwR = (int)((Rhi - Ax + 1) >> 6);                                   // <= 32
-                    const uint64_t word = (n <= 64 && lane < nwR) ? occ[w0 + lane] : 0ull;
-                    int incl = popc64(word);
-#pragma unroll
-                    for (int d = 1; d < 64; d <<= 1) { const int up = __shfl_up(incl, d, 64); if (lane >= d) incl += up; }
-                    auto cells_before = [&](int k) -> int { const int v = __shfl(incl, k > 0 ? k - 1 : 0, 64); return k > 0 ? v : 0; };      // words [0, k) of R
-                    for (int h = hmin; n <= 64 && h <= hmax; ++h) {
-                        W = seg << h;
-                        A = ((a - 1) / W) * W + 1; B = A + W - 1;
-                        if (b > B) continue;
-                        if (B + W > cap0) break;
-                        // (1) every op that touches Z' lies inside [A, B] and is a plain write
-                        const bool ov = o.lo <= B + W && A <= o.hi;                               // (an idle lane's empty interval overlaps nothing)
-                        const uint64_t ovm = __ballot(ov);
-                        if (__ballot(ov && (!(osimple || onew) || o.lo < A || o.hi > B)) != 0ull) continue;
-                        const int nins = popc64(__ballot(ov && oins)), nnew = popc64(__ballot(ov && onew));
-                        const int ins = nins + 2 * nnew, del = popc64(ovm) - nins - nnew;
-                        if (del > RA_MAX_DEL) continue;
-                        const int64_t lh = h < 24 ? sLoH[h] : ctl->lo[h], hh = h < 24 ? sHiH[h] : ctl->hi[h];
-                        if (W - hh < ins + 2) continue;
-                        int min_lo = ov ? o.lo : INT32_MAX;
-#pragma unroll
-                        for (int d = 32; d > 0; d >>= 1) { const int other = __shfl_xor(min_lo, d, 64); min_lo = other < min_lo ? other : min_lo; }
-                        const int wl = (int)(((A - 1) >> 6) - w0), nwd = (int)(W >> 6);
-                        const int c_a = cells_before(wl), c_b = cells_before(wl + nwd), c_c = cells_before(wl + 2 * nwd);
-                        const int64_t cl = c_b - c_a, cr = c_c - c_b;
-                        // (0) a predecessor moves left by one cell per deleted cell: more than `del` cells lie between A and the leftmost op
-                        int64_t cm = 0;
-                        const int64_t m1 = (int64_t)min_lo - 2;                                   // 0-based slots [A - 1, min_lo - 2]
-                        if (min_lo != INT32_MAX && m1 >= A - 1) {
-                            const int kw = (int)((m1 >> 6) - w0);
-                            const uint32_t wlo = (uint32_t)__shfl((int)(uint32_t)word, kw, 64), whi = (uint32_t)__shfl((int)(uint32_t)(word >> 32), kw, 64);
-                            const uint64_t wk = ((uint64_t)whi << 32) | wlo;
-                            const int r = (int)(m1 & 63);
-                            cm = cells_before(kw) - c_a + popc64(r == 63 ? wk : (wk & ((1ull << (r + 1)) - 1ull)));
-                        }
-                        if (cm < del + 1) continue;
-                        if (lh <= cl - del && cl + ins <= hh && lh <= cr - del && cr + ins <= hh) { ok = true; break; }
-                    }
-                } else ok = false;
-                if (lane == 0) {
-#ifdef DSA_FP_CHECK
-                    if (ok && (rs->tight & 0x400)) printf("DSA_FP_CHECK run-ahead: op %lld (position %d, act %d, footprint [%d,%d]) sealed in [%lld,%lld]+[..%lld]\n", (long long)op_index(j), j, (int)sAct[j], me.lo, me.hi, (long long)A, (long long)B, (long long)(B + W));
-#endif
-                    if (ok) { sZone[q].lo = (int32_t)A; sZone[q].mid = (int32_t)B; sZone[q].hi = (int32_t)(B + W); }
-                    else { PBW(j, !sSimple[j] ? 5 : (n > 64 ? 4 : 6)); atomicMin(&sC, j); }                                                    // not provable: the round ends in front of this op
-                }
-            }
-        }
-        __syncthreads();
-        // zones must not touch each other: a later conflicting op inside the left window of an earlier zone is a member of that one,
-        // otherwise the round ends at it
-        for (int q = tid; q < nconf; q += PL_BLOCK) {
-            const Zone zq = sZone[q];
-            if (zq.lo == 0) continue;
-            const int j = sConfList[q];
-            const Iv me = sIv[j];
-            bool member = false, cut = false;
-            for (int r = 0; r < nconf; ++r) {
-                const int i = sConfList[r];
-                const Zone zr = sZone[r];
-                if (i >= j || zr.lo == 0) continue;
-                if (zr.lo <= zq.hi && zq.lo <= zr.hi) { if (me.lo >= zr.lo && me.hi <= zr.mid) member = true; else cut = true; }
-            }
-            if (cut) { PBW(j, 7); atomicMin(&sC, j); }
-            else if (member) sDefer[j] = 2;                                            // (its own zone is dropped below, behind the barrier)
-        }
-        __syncthreads();
-        for (int q = tid; q < nconf; q += PL_BLOCK) { if (sDefer[sConfList[q]] == 2) sZone[q].lo = 0; else if (sZone[q].lo != 0) sZid[sConfList[q]] = (unsigned char)(q + 1); }
-        __syncthreads();
-        // every op behind a sealed op: inside the left window of the zone -> deferred with it; touching the zone otherwise -> the round ends there
-        for (int x = tid; x < Gc; x += PL_BLOCK) {
-            const Iv me = sIv[x];
-            if (me.lo > me.hi) continue;
-            int zid = 0;
-            for (int r = 0; r < nconf; ++r) {
-                const Zone zr = sZone[r];
-                if (sConfList[r] >= x || zr.lo == 0) continue;
-                if (me.lo <= zr.hi && zr.lo <= me.hi) {
-                    if (me.lo >= zr.lo && me.hi <= zr.mid && sSimple[x]) { if (zid == 0) zid = r + 1; }
-                    else { PBW(x, 8); atomicMin(&sC, x); }
-                }
-            }
-            if (zid != 0) { if (!sDefer[x]) sDefer[x] = 1; if (sZid[x] == 0) sZid[x] = (unsigned char)zid; }      // (only x's own entries: the owners' zones are final)
-        }
-        __syncthreads();
-    }
-    [[maybe_unused]] const long long tr3 = clock64();
-#ifdef DSA_FP_CHECK
-    {   // the final footprints, for the brute-force re-derivation of this verdict (k_fp_pre)
-        FpIv* fiv = reinterpret_cast<FpIv*>(reinterpret_cast<FpRec*>(plans + PB_GMAX) + PB_GMAX);
-        for (int j = tid; j < Gc; j += PL_BLOCK) { fiv[j].lo = sIv[j].lo; fiv[j].hi = sIv[j].hi; }
-    }
-#endif
-    // ---- the decision: ops [0, dd) are looked at; of those, the ones that neither conflict with an earlier op nor are sealed behind one
-    //      are applied by k_apply; the others go (in order) to the pending list of the next round, in front of the fresh ops
-    int dd = sC < sB ? sC : sB;
-    if (dd > G) dd = G;
-    bool stop_short = false;
-    {
-        // applied ops: element count and rebalance statistics, added to the control block ONCE, here (k_apply's waves used to add them
-        // one by one: ~500 atomics per round on the same words); zone check of the pending ones
-        int dn = 0, rn = 0, na = 0, nd = 0, bad = 0;
-        unsigned int rw = 0u;
-        const bool plain_round = sMinConf == INT32_MAX && np == 0;          // no conflict, nothing pending: every op of [0, dd) is applied
-        for (int j = tid; j < dd; j += PL_BLOCK) {
-            if (!plain_round && (sConf[j] || sDefer[j])) { ++nd; continue; }
-            ++na;
-            dn += sDn[j]; const unsigned int w2 = sRebW[j]; if (w2) { ++rn; rw += w2; }
-            if (j < np) {                                              // deferred earlier: it must still act inside the zone it was sealed in
-                const PendOp po = pend[j];
-                const Iv me = sIv[j];
-                if (po.zlo != 0 && sAct[j] != PB_NOOP && me.lo <= me.hi && (me.lo < po.zlo || me.hi > po.zhi)) {      // (a missing-key delete writes nothing)
-                    bad = 1;
-#ifdef DSA_FP_CHECK
-                    printf("DSA_FP_CHECK run-ahead: pending op %lld (window position %d of %d pending) is applied with the footprint [%d,%d] (act %d), outside the zone [%d,%d] it was sealed in\n",
-                           (long long)po.op, j, np, me.lo, me.hi, (int)sAct[j], po.zlo, po.zhi);
-#endif
-                }
-            }
-        }
-        if (tid == 0 && sB == 0 && np > 0 && pend[0].zlo != 0) bad = 1;          // a sealed op that cannot be planned any more
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { dn += __shfl_xor(dn, o, 64); rn += __shfl_xor(rn, o, 64); rw += __shfl_xor(rw, o, 64); }
-        if (!plain_round) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { na += __shfl_xor(na, o, 64); nd += __shfl_xor(nd, o, 64); bad |= __shfl_xor(bad, o, 64); }
-        }
-        if ((tid & 63) == 0) {
-            if (dn != 0 || rn != 0) { atomicAdd(&sSumDn, dn); atomicAdd(&sSumRebN, rn); atomicAdd(&sSumRebW, rw); }
-            if (plain_round) { if (tid == 0) sNApplied = dd; }
-            else {
-                if (na) atomicAdd(&sNApplied, na);
-                if (nd) atomicAdd(&sNDeferred, nd);
-                if (bad) atomicExch(&sFault, 1);
-            }
-        }
-    }
-    __syncthreads();
-    const int na = sNApplied;
-    const int ema = (3 * ema_prev + 16 * na) >> 2;
-    // short rounds one after the other mean the ops around the cursor collide (appends, one hot key): hand over to the
-    // sequencer.  A single short round between long ones (a small array, where windows are wide) is still cheaper as a round
-    // of >= 1 ops than as a sequencer launch.
-    // (with pending ops in the window only an op that cannot be planned stops the rounds: the sequencer takes ONE pending op at a time)
-    if (G > 0 && na < min_prefix && dd < G && (na == 0 || (np == 0 && ema < 16 * min_prefix))) stop_short = true;
-    if (G <= 0) stop_short = false;
-    // ---- the next window: pending list = the deferred ops of [0, dd) and the pending ops at or behind dd, in window order
-    PendOp* pend_next = const_cast<PendOp*>(db.pend) + (size_t)(1 - cur) * PB_GMAX;
-    int np_next = np;
-    int64_t cursor_next = i0;
-    const bool any_pending = sNDeferred > 0 || np > dd;               // (uniform: LDS word / kernel scalars)
-    if (!stop_short && G > 0 && !any_pending) { np_next = 0; cursor_next = i0 + (dd > np ? dd - np : 0); }
-    if (!stop_short && G > 0 && any_pending) {
-        // (PB_GMAX / PL_BLOCK consecutive window positions per thread)
-        constexpr int R = PB_GMAX / PL_BLOCK;
-        bool keep[R];
-        uint32_t mine = 0;
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            const int j = tid * R + u;
-            keep[u] = j < G && ((j < dd && (sConf[j] || sDefer[j])) || (j >= dd && j < np));
-            mine += keep[u] ? 1u : 0u;
-        }
-        uint32_t inc = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t y = __shfl_up(inc, o, 64); if ((tid & 63) >= o) inc += y; }
-        if ((tid & 63) == 63) sScan[tid >> 6] = inc;
-        __syncthreads();
-        uint32_t base = 0, total = 0;
-#pragma unroll
-        for (int v = 0; v < PL_BLOCK / 64; ++v) { const uint32_t c = sScan[v]; if (v < (tid >> 6)) base += c; total += c; }
-        uint32_t at = base + inc - mine;
-#pragma unroll
-        for (int u = 0; u < R; ++u) {
-            if (!keep[u]) continue;
-            const int j = tid * R + u;
-            PendOp po;
-            po.op = op_index(j);
-            int32_t zl = 0, zh = 0;
-            if (j < dd && sZid[j] != 0) { const Zone z = sZone[sZid[j] - 1]; zl = z.lo; zh = z.hi; }
-            if (j < np) {                                              // intersect with the zone it carries
-                const PendOp old = pend[j];
-                if (old.zlo != 0) { if (zl == 0) { zl = old.zlo; zh = old.zhi; } else { zl = zl > old.zlo ? zl : old.zlo; zh = zh < old.zhi ? zh : old.zhi; } }
-            }
-            po.zlo = zl; po.zhi = zh;
-            pend_next[at++] = po;
-        }
-        np_next = (int)total;
-        cursor_next = i0 + (dd > np ? dd - np : 0);
-    }
-    if (tid == 0) {
-#ifdef DSA_PB_PROF
-        {   // dev profile: cycle sums per phase of the resolving workgroup, read and reset by dsa_dbg_pbprof_dump (no printf: it distorts what it measures)
-            const long long ph[7] = {tk1 - tk0, tr0 - tk1, tr1 - tr0, tr2 - tr1, tr3 - tr2, (long long)clock64() - tr3, (long long)sNConf};
-            atomicAdd(&g_pbprof[0], 1ull);
-            for (int q = 0; q < 7; ++q) atomicAdd(&g_pbprof[1 + q], (unsigned long long)ph[q]);
-            atomicAdd(&g_pbprof[8], (unsigned long long)G); atomicAdd(&g_pbprof[9], (unsigned long long)na);
-            // why the round ended where it did: 0 the whole window, 10 a BARRIER op (11..17: its reason + 11), 1..9 see the cut sites
-            int code = 0;
-            if (dd < G) code = sB <= sC ? 11 + (__hip_atomic_load(&plans[sB < G ? sB : 0].count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 7) : (int)sCutWhy[sC];
-            atomicAdd(&g_pbprof[12 + code], 1ull);
-        }
-#endif
-        rs->ticket = 0u;                                               // re-armed for the next round
-        // commit the window of THIS round (k_apply reads it) ...
-        rs->cursor = i0; rs->np = np; rs->cur = cur;
-        if (sFault) atomicMax(&rs->pad, 9);
-        if (G <= 0) { rs->stop = drain ? 5 : 2; rs->d = 0; return; }    // finished (5: the pending list is drained)
-        rs->ema = ema;
-        if (stop_short) {
-            rs->why[sB <= sC ? (__hip_atomic_load(&plans[sB < G ? sB : 0].count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 7) : 7] += 1;
-            rs->stop = 1; rs->d = 0;
-            rs->pend0 = op_index(0);
-            return;                                                    // (the next window stays what this one was)
-        }
-        rs->d = dd;
-        // ... and describe the next one
-        rs->cursor_n = cursor_next; rs->np_n = np_next; rs->cur_n = 1 - cur;
-        rs->rounds = rounds_prev + (na > 0 ? 1 : 0); rs->par_ops = par_ops_prev + na; rs->deferred = deferred_prev + sNDeferred;
-        if (na > 0) {
-            Ctl* c = const_cast<Ctl*>(ctl);
-            if (sSumDn != 0) atomicAdd((unsigned long long*)&c->nb_elements, (unsigned long long)(long long)sSumDn);
-            if (sSumRebN != 0) {
-                atomicAdd((unsigned long long*)&c->stat_rebalances, (unsigned long long)sSumRebN);
-                atomicAdd((unsigned long long*)&c->stat_window_slots, (unsigned long long)sSumRebW);
-                atomicAdd((unsigned long long*)&c->stat_small_rebalances, (unsigned long long)sSumRebN);
-            }
-        }
-        // the next window: half as much again as what ran.  (The resolve step costs per planned op where ops collide: with a floor of 256 /
-        // 512 / 1024 ops under the window config 5's first batch takes 50.7 / 58.1 / 68.0 ms instead of 34.0, its first 14 batches 143 / 168 /
-        // 192 ms instead of 119; batch B and the matrix updates gain 0-3 % at 1024.)
-        int Gn = na + (na >> 1) + 32;
-        if (Gn < 64) Gn = 64;
-        if (Gn > PB_GMAX) Gn = PB_GMAX;
-        rs->G_next = Gn;
-    }
-    // the ops k_apply must skip: deferred ones inside [0, dd)
-    if (!stop_short && G > 0 && sNDeferred > 0)
-        for (int j = tid; j < dd; j += PL_BLOCK)
-            if (sConf[j] || sDefer[j]) __hip_atomic_store(&plans[j].action, (int32_t)PB_DEFER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const long long tr2 = clock64();
+    resolve_seal(S, R, hc, Gc, ctl, db.occ, rs);                       // (ends with its own barrier wherever it wrote)
+    const long long tr3 = clock64();
+    fp_publish_footprints(plans, S.sIv, Gc);
+    const Verdict V = resolve_decide(S, R);
+    const NextWindow N = resolve_next_window(S, R, V, const_cast<PendOp*>(db.pend) + (size_t)(1 - R.cur) * PB_GMAX);
+    if (threadIdx.x == 0) { const long long t[6] = {tk0, tk1, tr0, tr1, tr2, tr3}; pbprof_round(S, R, V, plans, t); }
+    resolve_commit(S, R, V, N, ctl, rs, plans);
 }
 
 // ---- apply ----------------------------------------------------------------------------------------------------------
-__device__ void pb_shift_right(KeyArr keys, double* vals, int64_t* sems, int64_t a, int64_t b) {      // cells [a, b-1] -> +1
-    const int lane = lane_id();
-    fp_touch(a, b);
-    for (int64_t hi = b - 1; hi >= a; hi -= 64) {
-        const int64_t p = hi - lane;
-        const bool act = p >= a;
-        int64_t k = 0; double v = 0.0;
-        if (act) { k = keys[p - 1]; v = vals[p - 1]; }
-        if (act) {
-            keys[p] = k; vals[p] = v;
-            if (sems != nullptr && k == SEM_KEY) sems[(int64_t)v - 1] = p + 1;       // _moverightloop!  src/moves.jl:32-36
-        }
-    }
-}
-// cells [a, b-1] -> +dist, highest chunk first (a chunk's stores land above every cell that is still to be read)
-__device__ void pb_shift_right_by(KeyArr keys, double* vals, int64_t* sems, int64_t a, int64_t b, int dist) {
+// cells [a, b-1] -> +dist (_moverightloop!  src/moves.jl:32-36), highest chunk first: a chunk's stores land above every cell that is still
+// to be read.  LIVE: the cells were just written by this wave (L2-served loads, see pb_next_empty_live).
+template <bool LIVE>
+__device__ void pb_shift_right(KeyArr keys, double* vals, int64_t* sems, int64_t a, int64_t b, int dist = 1) {
     const int lane = lane_id();
     fp_touch(a, b - 1 + dist);
     for (int64_t hi = b - 1; hi >= a; hi -= 64) {
         const int64_t p = hi - lane;
         const bool act = p >= a;
         int64_t k = 0; double v = 0.0;
-        if (act) { k = keys[p - 1]; v = vals[p - 1]; }
+        if (act) {
+            k = LIVE ? keys.ld_agent(p - 1) : keys.ld(p - 1);
+            v = LIVE ? __hip_atomic_load(vals + p - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : vals[p - 1];
+        }
         if (act) {
             keys[p - 1 + dist] = k; vals[p - 1 + dist] = v;
             if (sems != nullptr && k == SEM_KEY) sems[(int64_t)v - 1] = p + dist;
@@ -1100,23 +475,6 @@ __device__ int64_t pb_next_empty_live(const uint64_t* occ, int64_t from, int64_t
         word = ~pb_occ_load(occ, w);
     }
 }
-__device__ void pb_shift_right_live(KeyArr keys, double* vals, int64_t* sems, int64_t a, int64_t b) {      // cells [a, b-1] -> +1
-    const int lane = lane_id();
-    fp_touch(a, b);
-    for (int64_t hi = b - 1; hi >= a; hi -= 64) {
-        const int64_t p = hi - lane;
-        const bool act = p >= a;
-        int64_t k = 0; double v = 0.0;
-        if (act) {
-            k = keys.ld_agent(p - 1);
-            v = __hip_atomic_load(vals + p - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (act) {
-            keys[p] = k; vals[p] = v;
-            if (sems != nullptr && k == SEM_KEY) sems[(int64_t)v - 1] = p + 1;
-        }
-    }
-}
 // _look_for_rebalance! + _even_rebalance! (src/pma.jl:94-141) around `ip` on the live bitmap; the plan guarantees acceptance
 // at a level whose window fits one wave.  Returns true when cells were moved.
 __device__ bool pb_scan_and_rebalance_live(KeyArr keys, double* vals, uint64_t* occ, int64_t* sems, Ctl* ctl, int64_t ip, int64_t hmax,
@@ -1157,7 +515,7 @@ __device__ void pb_apply_one(KeyArr keys, double* vals, uint64_t* occ, int64_t* 
             break;
         case PB_INS_R: {                                           // _insert!, right branch  src/writes.jl:29-32
             const int64_t p = pl.pos, ne = pl.aux;
-            pb_shift_right(keys, vals, sems, p + 1, ne);
+            pb_shift_right<false>(keys, vals, sems, p + 1, ne);
             if (lane == 0) { keys[p] = op.a; vals[p] = op.v; pb_bit_set(occ, ne); }
             delta = 1;
             break;
@@ -1195,7 +553,7 @@ __device__ void pb_apply_one(KeyArr keys, double* vals, uint64_t* occ, int64_t* 
             }
             idx = __shfl(idx, 0, 64);
             // addpartition!: the semaphore cell (0, id) in front of the successor's semaphore  src/pcsr.jl:136-144
-            pb_shift_right(keys, vals, sems, p1 + 1, ne1);
+            pb_shift_right<false>(keys, vals, sems, p1 + 1, ne1);
             if (lane == 0) {
                 keys[p1] = SEM_KEY; vals[p1] = (double)(idx + 1);
                 sems[idx] = p1 + 1; col_keys[idx] = op.b; col_live[idx] = 1;
@@ -1212,7 +570,7 @@ __device__ void pb_apply_one(KeyArr keys, double* vals, uint64_t* occ, int64_t* 
                 if (lane == 0) atomicExch(fault, 1);      // RoundState::pad = fault flag, read by the host after every burst
                 break;
             }
-            pb_shift_right_live(keys, vals, sems, s1 + 1, ne2);
+            pb_shift_right<true>(keys, vals, sems, s1 + 1, ne2);
             if (lane == 0) { keys[s1] = op.a; vals[s1] = op.v; pb_bit_set(occ, ne2); }
             __builtin_amdgcn_s_waitcnt(0);
             pb_scan_and_rebalance_live(keys, vals, occ, sems, ctl, s1 + 1, hmax, sK, sV);
@@ -1256,190 +614,10 @@ __global__ __launch_bounds__(PB_BLOCK) void k_apply(const DevBufs* bufs, Ctl* ct
     const Op op = ops[oi];
     const Plan pl = plans[w];
     if (pl.action == PB_DEFER) return;                                          // deferred by the resolve step: pending for the next round
-#ifdef DSA_FP_CHECK
-    if (rs->tight & FP_MODE_SHADOW) return;                       // (the prefix was applied one op after the other by k_fp_pre)
-#endif
+    if (fp_shadow_applied(rs)) return;                                          // (footprint-check build, mode 2: k_fp_pre has applied the prefix)
     pb_apply_one(keys, vals, occ, sems, col_keys, col_live, ctl, &const_cast<RoundState*>(rs)->pad, op, pl, sK, sV, true);
-#ifdef DSA_FP_CHECK
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {
-        FpRec* rec = reinterpret_cast<FpRec*>(const_cast<Plan*>(plans) + PB_GMAX) + w;
-        rec->tlo = g_fpw[wv].tlo; rec->thi = g_fpw[wv].thi;
-    }
-#endif
+    fp_publish_touched(plans, w);
 }
-
-#ifdef DSA_FP_CHECK
-// do two plans of one op describe the same effect?  (footprints and the leaf counts carried for the resolver may differ)
-__device__ bool fp_same_plan(const Plan& a, const Plan& b, int64_t seg) {
-    if (a.action != b.action) return false;
-    switch (a.action) {
-        case PB_NOOP: case PB_BARRIER: return true;
-        case PB_OVERWRITE: return a.pos == b.pos;
-        case PB_NEWCOL: {
-            if (a.pos != b.pos || a.aux != b.aux) return false;
-            const bool ta = (a.count & 0x80) != 0, tb = (b.count & 0x80) != 0;
-            if (ta && tb) return a.hi == b.hi;                                      // both leaf-accepted: the same two gaps
-            return ta == tb && a.ws == b.ws && a.we == b.we && (a.count & 0x7f) == (b.count & 0x7f);
-        }
-        default:
-            if (a.pos != b.pos || a.aux != b.aux || a.ws != b.ws || a.we != b.we) return false;
-            return (a.we - a.ws + 1 == seg) || a.count == b.count;                  // a rebalance follows: it spreads `count` cells
-    }
-}
-__device__ __forceinline__ void fp_fault(RoundState* rs, int code) { atomicMax(&rs->pad, code); }
-
-// Between k_plan (+ resolve) and k_apply.  Mode 1: the brute-force re-derivation described at the top of this file.  Mode 2: the
-// sequential shadow — wave 0 re-plans every op of the prefix on the live state, compares, applies it.
-__global__ __launch_bounds__(PL_BLOCK) void k_fp_pre(const DevBufs* bufs, Ctl* ctl, const Op* ops, RoundState* rs, Plan* plans) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char pb_lds[];
-    if (rs->stop) return;
-    const int d = rs->d;
-    if (d <= 0) return;
-    const int mode = rs->tight;
-    const DevBufs db = *bufs;
-    const KeyArr keys{db.keys, db.wide, 0};
-    double* vals = db.vals; uint64_t* occ = db.occ;
-    int64_t* sems = db.sems; int64_t* col_keys = db.col_keys; uint8_t* col_live = db.col_live;
-    const int64_t i0 = rs->cursor, seg = ctl->segment_capacity;
-    const int tid = threadIdx.x;
-    if (mode & FP_MODE_SHADOW) {
-        if (tid >= 64) return;
-        int64_t* sK = reinterpret_cast<int64_t*>(pb_lds);
-        double* sV = reinterpret_cast<double*>(pb_lds + (size_t)PB_MAX_W * sizeof(int64_t));
-        const int np = rs->np;
-        const PendOp* pend = db.pend + (size_t)rs->cur * PB_GMAX;
-        for (int j = 0; j < d; ++j) {
-            const Plan want = plans[j];
-            if (want.action == PB_DEFER) continue;                  // deferred: not part of this round
-            const Op op = ops[j < np ? pend[j].op : i0 + (j - np)];
-            // (w = 0: the table entries of the earlier new columns exist by now)
-            const Plan live = pb_plan_one(keys, vals, occ, sems, col_keys, col_live, ctl, op, 0, PB_MAX_W);
-            if (!fp_same_plan(want, live, seg)) {
-                if (tid == 0) {
-                    printf("DSA_FP_CHECK shadow: op %lld (round op %d of %d; a %lld b %lld v %g) planned act %d pos %lld aux %lld win [%lld,%lld] count %d fp [%lld,%lld]"
-                           " | on the state left by the earlier ops of its round: act %d pos %lld aux %lld win [%lld,%lld] count %d fp [%lld,%lld]\n",
-                           (long long)(i0 + j), j, d, (long long)op.a, (long long)op.b, op.v, want.action, (long long)want.pos, (long long)want.aux,
-                           (long long)want.ws, (long long)want.we, want.count, (long long)want.lo, (long long)want.hi, live.action, (long long)live.pos,
-                           (long long)live.aux, (long long)live.ws, (long long)live.we, live.count, (long long)live.lo, (long long)live.hi);
-                    fp_fault(rs, 12);
-                }
-                return;                                              // nothing more is applied: the host fails the batch
-            }
-            pb_apply_one(keys, vals, occ, sems, col_keys, col_live, ctl, &rs->pad, op, want, sK, sV, true);
-            __builtin_amdgcn_s_waitcnt(0);                           // this wave's stores and atomics have been acknowledged (they are at the L2) ...
-            __builtin_amdgcn_s_dcache_inv();                         // ... and the next plan reads neither through a stale scalar cache
-            asm volatile("buffer_inv sc0" ::: "memory");            // nor through this CU's vector L1
-        }
-        return;
-    }
-    if (!(mode & FP_MODE_SETS)) return;
-    const FpRec* recs = reinterpret_cast<const FpRec*>(plans + PB_GMAX);
-    const FpIv* fiv = reinterpret_cast<const FpIv*>(recs + PB_GMAX);
-    __shared__ int32_t sLo[PB_GMAX], sHi[PB_GMAX], sC1[PB_GMAX], sC2[PB_GMAX], sWs[PB_GMAX], sWe[PB_GMAX], sTLo[PB_GMAX], sTHi[PB_GMAX];
-    __shared__ signed char sD1[PB_GMAX];
-    __shared__ unsigned char sTight[PB_GMAX];
-    __shared__ unsigned char sOff[PB_GMAX];                          // deferred by the resolve step: not part of this round
-    for (int j = tid; j < d; j += PL_BLOCK) {
-        const Plan q = plans[j];
-        sOff[j] = q.action == PB_DEFER ? 1 : 0;
-        const bool leaf_only = pb_is_leaf_only(q.action, q.ws, q.we, seg, q.count);
-        const int dl = pb_delta(q.action, leaf_only);
-        sLo[j] = fiv[j].lo; sHi[j] = fiv[j].hi;
-        if (sOff[j]) { sLo[j] = INT32_MAX; sHi[j] = INT32_MIN; }
-        sD1[j] = (signed char)dl;
-        sC1[j] = dl != 0 ? (int32_t)pb_changed_slot(q.action, q.pos, q.aux) : 0;
-        sC2[j] = (q.action == PB_NEWCOL && leaf_only) ? (int32_t)q.hi : 0;
-        // an op that rebalances (or a new column that may) changes any bit of its window
-        const bool reb = (q.action == PB_NEWCOL && !leaf_only) ||
-                         ((q.action == PB_INS_R || q.action == PB_INS_L || q.action == PB_DELETE) && q.we - q.ws + 1 != seg);
-        sWs[j] = reb ? (int32_t)q.ws : 1; sWe[j] = reb ? (int32_t)q.we : 0;
-        sTight[j] = leaf_only ? 1 : 0;
-        // what the apply may WRITE or re-read live: a leaf-accepted insert / delete moves nothing but its shifted run — its tight hull,
-        // also when the resolve step widened the footprint to the leaf (the widening stands for the COUNT the plan read) —, everybody
-        // else anything inside the final footprint (a new column that was widened scans and rebalances live inside its window)
-        const bool hull_only = leaf_only && q.action != PB_NEWCOL;
-        sTLo[j] = hull_only ? (int32_t)q.lo : fiv[j].lo; sTHi[j] = hull_only ? (int32_t)q.hi : fiv[j].hi;
-        if (sOff[j]) { sTLo[j] = INT32_MAX; sTHi[j] = INT32_MIN; }
-    }
-    __syncthreads();
-    const int64_t lo0 = ctl->lo[0], hi0 = ctl->hi[0];
-    for (int j = tid; j < d; j += PL_BLOCK) {
-        if (sOff[j]) continue;
-        const int32_t lo = sLo[j], hi = sHi[j];
-        const FpRec r = recs[j];
-        // (a) nothing an EARLIER op of the prefix writes lies in the final footprint of a later one (which holds everything that one read for
-        //     its decisions and everything it writes) — all pairs, no hash.  The converse — a later op writing where an earlier one only
-        //     COUNTED — is allowed: the earlier plan was made on the pre-round state either way, as the sequential order has it.
-        if (lo <= hi)
-            for (int i = 0; i < j; ++i)
-                if (sTLo[i] <= sTHi[i] && sTLo[i] <= hi && lo <= sTHi[i]) {
-                    printf("DSA_FP_CHECK sets: op %d of a prefix of %d writes inside [%d,%d] (footprint [%d,%d]); the later op %d has the footprint [%d,%d]\n", i, d,
-                           sTLo[i], sTHi[i], sLo[i], sHi[i], j, lo, hi);
-                    fp_fault(rs, 13);
-                }
-        if (sTLo[j] < lo || sTHi[j] > hi) { printf("DSA_FP_CHECK sets: op %d: write set [%d,%d] outside its footprint [%d,%d]\n", j, sTLo[j], sTHi[j], lo, hi); fp_fault(rs, 13); }
-        // (b) the occupancy runs the plan scanned for its shift target lie inside the footprint
-        if (r.rlo <= r.rhi && (r.rlo < lo || r.rhi > hi)) {
-            printf("DSA_FP_CHECK sets: op %d (act %d) scanned the occupancy of [%lld,%lld] for its shift target, its footprint is [%d,%d]\n", j, plans[j].action,
-                   (long long)r.rlo, (long long)r.rhi, lo, hi);
-            fp_fault(rs, 14);
-        }
-        // (c) every window whose count the plan consulted: inside the footprint and untouched by the others, or the leaf of a leaf-accepted
-        //     op whose thresholds hold whatever subset of the prefix's changes has happened
-        if (r.ncnt > FP_MAXCNT) { printf("DSA_FP_CHECK sets: op %d consulted %d windows (recorder holds %d)\n", j, r.ncnt, FP_MAXCNT); fp_fault(rs, 15); }
-        for (int c = 0; c < r.ncnt && c < FP_MAXCNT; ++c) {
-            const int32_t a = r.cnt[c][0], b = r.cnt[c][1];
-            const bool inside = a >= lo && b <= hi;
-            int ins = 0, del = 0, foreign = 0;
-            for (int i = 0; i < d; ++i) {
-                if (i != j && sWs[i] <= sWe[i] && sWs[i] <= b && a <= sWe[i]) ++foreign;       // somebody else's rebalance window reaches in
-                const int32_t c1 = sC1[i], c2 = sC2[i];
-                if (c1 >= a && c1 <= b) { if (sD1[i] > 0) ++ins; else ++del; if (i != j && inside) ++foreign; }
-                if (c2 >= a && c2 <= b) { ++ins; if (i != j && inside) ++foreign; }
-            }
-            if (inside) {
-                if (foreign) { printf("DSA_FP_CHECK sets: op %d counted [%d,%d] inside its footprint [%d,%d]; %d other ops of the prefix change it\n", j, a, b, lo, hi, foreign); fp_fault(rs, 16); }
-                continue;
-            }
-            if (sTight[j] && plans[j].action == PB_NEWCOL && b - a + 1 != seg) continue;      // the fallback window of a leaf-accepted new column: only consulted if the resolve step widens the op to it — then it is inside
-            if (!sTight[j] || b - a + 1 != seg) {
-                printf("DSA_FP_CHECK sets: op %d (act %d) counted [%d,%d] outside its footprint [%d,%d] and is not leaf-accepted\n", j, plans[j].action, a, b, lo, hi);
-                fp_fault(rs, 17);
-                continue;
-            }
-            if (foreign) { printf("DSA_FP_CHECK sets: leaf [%d,%d] of op %d lies in another op's rebalance window\n", a, b, j); fp_fault(rs, 18); continue; }
-            int64_t cnt = 0;                                                   // recounted from the pre-round bitmap
-            for (int64_t w = (a - 1) >> 6; w <= (b - 1) >> 6; ++w) cnt += popc64(occ[w] & word_range_mask(w, a - 1, b - 1));
-            if (!(cnt + ins <= hi0 && cnt - del >= lo0)) {
-                printf("DSA_FP_CHECK sets: leaf [%d,%d] of leaf-accepted op %d (act %d, footprint [%d,%d]) holds %lld cells; the prefix of %d ops inserts %d and deletes %d "
-                       "there: thresholds [%lld,%lld] do not hold for every order\n", a, b, j, plans[j].action, lo, hi, (long long)cnt, d, ins, del, (long long)lo0, (long long)hi0);
-                fp_fault(rs, 19);
-            }
-        }
-    }
-}
-// behind k_apply (mode 1): what every op of the prefix wrote, changed or re-read live lies inside its final footprint
-__global__ __launch_bounds__(PL_BLOCK) void k_fp_post(RoundState* rs, const Plan* plans, const Ctl* ctl) {
-    if (rs->stop || !(rs->tight & FP_MODE_SETS) || (rs->tight & FP_MODE_SHADOW)) return;
-    const int d = rs->d;
-    const int64_t seg = ctl->segment_capacity;
-    const FpRec* recs = reinterpret_cast<const FpRec*>(plans + PB_GMAX);
-    const FpIv* fiv = reinterpret_cast<const FpIv*>(recs + PB_GMAX);
-    for (int j = threadIdx.x; j < d; j += PL_BLOCK) {
-        const FpRec r = recs[j];
-        const Plan q = plans[j];
-        if (q.action == PB_DEFER) continue;
-        const bool hull_only = q.action != PB_NEWCOL && pb_is_leaf_only(q.action, q.ws, q.we, seg, q.count);      // (see k_fp_pre)
-        const int64_t tlo = hull_only ? q.lo : (int64_t)fiv[j].lo, thi = hull_only ? q.hi : (int64_t)fiv[j].hi;
-        if (r.tlo <= r.thi && (r.tlo < tlo || r.thi > thi)) {
-            printf("DSA_FP_CHECK sets: op %d (act %d) touched [%lld,%lld], it may write [%lld,%lld] (footprint [%d,%d])\n", j, q.action, (long long)r.tlo, (long long)r.thi,
-                   (long long)tlo, (long long)thi, fiv[j].lo, fiv[j].hi);
-            fp_fault(rs, 20);
-        }
-    }
-}
-#endif
 
 // ---- local rounds: the same plan / resolve / apply, by ONE workgroup, for phases with little parallelism --------------------------
 // A grid round costs two launches (~15 us) whatever it applies; while the conflict-free prefixes are short — a small, fast-growing
@@ -1473,30 +651,25 @@ __global__ __launch_bounds__(LR_BLOCK) void k_local_rounds(const DevBufs* bufs, 
         const int64_t left = limit - cursor;
         if (left <= 0) { stop = 2; break; }
         const int G = (int)(left < LR_WAVES ? left : LR_WAVES);
+        // ---- plan: one wave per op
         if (wv < G) {
             const Plan pl = pb_plan_one(keys, vals, occ, sems, col_keys, col_live, ctl, ops[cursor + wv], wv, LR_MAX_W);
             if (lane == 0) sPlan[wv] = pl;
         }
         __syncthreads();
+        // ---- decide: d = min(first BARRIER, smallest j whose footprint overlaps the footprint of an earlier op)
         if (threadIdx.x == 0) {
-            // d = min(first BARRIER, smallest j whose footprint overlaps the footprint of an earlier op)
+            const int64_t seg = ctl->segment_capacity, capacity = ctl->capacity;
             int dd = G;
             for (int j = 0; j < G && dd == G; ++j) {
                 if (sPlan[j].action == PB_BARRIER) { dd = j; break; }
                 // (leaf-only ops carry their tight hull: widened to their window here — no count bookkeeping in the mini-rounds)
-                auto full = [&](const Plan& q, int64_t& lo_, int64_t& hi_) {
-                    lo_ = q.lo; hi_ = q.hi;
-                    if (lo_ <= hi_ && pb_is_leaf_only(q.action, q.ws, q.we, ctl->segment_capacity, q.count)) {
-                        if (q.action == PB_NEWCOL && (q.count & 0x7f) == 0x7f) { lo_ = 1; hi_ = ctl->capacity; }      // no fallback window to widen to: alone in its mini-round
-                        else { if (q.ws < lo_) lo_ = q.ws; if (q.we > hi_) hi_ = q.we; }
-                    }
-                };
                 int64_t lo, hi;
-                full(sPlan[j], lo, hi);
+                pb_full_footprint(sPlan[j], seg, capacity, lo, hi);
                 if (lo > hi) continue;
                 for (int i = 0; i < j; ++i) {
                     int64_t l2, h2;
-                    full(sPlan[i], l2, h2);
+                    pb_full_footprint(sPlan[i], seg, capacity, l2, h2);
                     if (l2 <= h2 && l2 <= hi && lo <= h2) { dd = j; break; }
                 }
             }
@@ -1505,62 +678,13 @@ __global__ __launch_bounds__(LR_BLOCK) void k_local_rounds(const DevBufs* bufs, 
         __syncthreads();
         const int dd = sD;
         if (dd == 0) { stop = 1; why = sPlan[0].count & 7; break; }       // the op at the cursor cannot be planned: the sequencer's
-#ifdef DSA_FP_CHECK
-        if (rs->tight & FP_MODE_SHADOW) {
-            // sequential shadow of the mini-round: op j is planned again on the state the ops before it left, compared, applied
-            for (int j = 0; j < dd; ++j) {
-                if (wv == j) {
-                    const Op op = ops[cursor + j];
-                    const Plan live = pb_plan_one(keys, vals, occ, sems, col_keys, col_live, ctl, op, 0, LR_MAX_W);
-                    if (!fp_same_plan(sPlan[j], live, ctl->segment_capacity)) {
-                        if (lane == 0) {
-                            printf("DSA_FP_CHECK shadow (local rounds): op %lld (%d of %d) planned act %d pos %lld aux %lld win [%lld,%lld] | live act %d pos %lld aux %lld win [%lld,%lld]\n",
-                                   (long long)(cursor + j), j, dd, sPlan[j].action, (long long)sPlan[j].pos, (long long)sPlan[j].aux, (long long)sPlan[j].ws, (long long)sPlan[j].we,
-                                   live.action, (long long)live.pos, (long long)live.aux, (long long)live.ws, (long long)live.we);
-                            fp_fault(rs, 22);
-                        }
-                    } else pb_apply_one(keys, vals, occ, sems, col_keys, col_live, ctl, &rs->pad, op, sPlan[j], sK, sV, false);
-                }
-                __builtin_amdgcn_s_waitcnt(0);
-                __syncthreads();
-                __builtin_amdgcn_s_dcache_inv();
-                asm volatile("buffer_inv sc0" ::: "memory");
-            }
-        } else {
-            // recorded sets: the run the plan scanned and what the apply touched lie inside the op's FULL footprint (what this kernel's
-            // all-pairs test works on), and those are pairwise disjoint
-            __shared__ FpRec sRec[LR_WAVES];
-            if (wv < dd && lane == 0) sRec[wv] = g_fpw[wv];
+        // ---- apply: the prefix, one wave per op (footprint-check build: one op after the other in mode 2, records kept and checked in mode 1)
+        if (!fp_lr_shadow(keys, vals, occ, sems, col_keys, col_live, ctl, ops, rs, sPlan, dd, cursor, LR_MAX_W, sK, sV)) {
+            fp_lr_keep_plan_record(dd);
             if (wv < dd) pb_apply_one(keys, vals, occ, sems, col_keys, col_live, ctl, &rs->pad, ops[cursor + wv], sPlan[wv], sK, sV, false);
-            __builtin_amdgcn_wave_barrier();
-            if (wv < dd && lane == 0) { sRec[wv].tlo = g_fpw[wv].tlo; sRec[wv].thi = g_fpw[wv].thi; }
-            __syncthreads();
-            if ((rs->tight & FP_MODE_SETS) && threadIdx.x == 0) {
-                const int64_t segc = ctl->segment_capacity;
-                int64_t flo[LR_WAVES], fhi[LR_WAVES];
-                for (int j = 0; j < dd; ++j) {
-                    const Plan& q = sPlan[j];
-                    flo[j] = q.lo; fhi[j] = q.hi;
-                    if (flo[j] <= fhi[j] && pb_is_leaf_only(q.action, q.ws, q.we, segc, q.count)) {
-                        if (q.action == PB_NEWCOL && (q.count & 0x7f) == 0x7f) { flo[j] = 1; fhi[j] = ctl->capacity; }
-                        else { if (q.ws < flo[j]) flo[j] = q.ws; if (q.we > fhi[j]) fhi[j] = q.we; }
-                    }
-                    for (int i = 0; i < j; ++i)
-                        if (flo[i] <= fhi[i] && flo[j] <= fhi[j] && flo[i] <= fhi[j] && flo[j] <= fhi[i]) { printf("DSA_FP_CHECK sets (local rounds): ops %d and %d share slots\n", i, j); fp_fault(rs, 23); }
-                    const FpRec& r = sRec[j];
-                    if ((r.rlo <= r.rhi && (r.rlo < flo[j] || r.rhi > fhi[j])) || (r.tlo <= r.thi && (r.tlo < flo[j] || r.thi > fhi[j]))) {
-                        printf("DSA_FP_CHECK sets (local rounds): op %d (act %d) scanned [%lld,%lld] touched [%lld,%lld], footprint [%lld,%lld]\n", j, q.action,
-                               (long long)r.rlo, (long long)r.rhi, (long long)r.tlo, (long long)r.thi, (long long)flo[j], (long long)fhi[j]);
-                        fp_fault(rs, 24);
-                    }
-                    for (int c = 0; c < r.ncnt && c < FP_MAXCNT; ++c)
-                        if (r.cnt[c][0] < flo[j] || r.cnt[c][1] > fhi[j]) { printf("DSA_FP_CHECK sets (local rounds): op %d counted [%d,%d] outside [%lld,%lld]\n", j, r.cnt[c][0], r.cnt[c][1], (long long)flo[j], (long long)fhi[j]); fp_fault(rs, 25); }
-                }
-            }
+            fp_lr_check_sets<LR_WAVES>(rs, ctl, sPlan, dd);
         }
-#else
-        if (wv < dd) pb_apply_one(keys, vals, occ, sems, col_keys, col_live, ctl, &rs->pad, ops[cursor + wv], sPlan[wv], sK, sV, false);
-#endif
+        // ---- advance
         cursor += dd; par_ops += dd; ++rounds;
         full_streak = dd == LR_WAVES ? full_streak + 1 : 0;
         single_streak = (dd == 1 && G > 1) ? single_streak + 1 : 0;
@@ -1600,6 +724,9 @@ __global__ __launch_bounds__(256) void k_publish(const RoundState* rs, const Ctl
         publish_seq(pub.host_seq, (unsigned long long)(unsigned int)rs->seq);
     }
 }
+static void enqueue_publish(const RoundState* rs, const Ctl* ctl, BurstPublish pub, hipStream_t stream) {
+    if (pub.host_seq != nullptr) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, stream, rs, ctl, pub);      // (no mirror: the caller reads the state itself)
+}
 
 hipError_t launch_local_rounds(const DevBufs* bufs, Ctl* ctl, const Op* ops, RoundState* rs, int max_rounds, BurstPublish pub, hipStream_t stream) {
     constexpr size_t lds = (size_t)LR_WAVES * LR_MAX_W * (sizeof(int64_t) + sizeof(double));
@@ -1609,7 +736,7 @@ hipError_t launch_local_rounds(const DevBufs* bufs, Ctl* ctl, const Op* ops, Rou
     });
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_local_rounds, dim3(1), dim3(LR_BLOCK), lds, stream, bufs, ctl, ops, rs, max_rounds);
-    if (pub.host_seq != nullptr) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, stream, rs, ctl, pub);
+    enqueue_publish(rs, ctl, pub, stream);
     return hipGetLastError();
 }
 
@@ -1617,20 +744,14 @@ hipError_t launch_local_rounds(const DevBufs* bufs, Ctl* ctl, const Op* ops, Rou
 static hipError_t configure_apply() {
     static PerDeviceOnce once;
     return once.run([] {
-        const size_t lds = (size_t)(PB_BLOCK / 64) * PB_MAX_W * (sizeof(int64_t) + sizeof(double));
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_apply), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(k_apply), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((PB_BLOCK / 64) * PB_WAVE_LDS));
     });
 }
 static hipError_t enqueue_round(const DevBufs* bufs, Ctl* ctl, const Op* ops, RoundState* rs, Plan* plans, hipStream_t stream) {
-    const size_t lds = (size_t)(PB_BLOCK / 64) * PB_MAX_W * (sizeof(int64_t) + sizeof(double));
     hipLaunchKernelGGL(k_plan, dim3(PB_GMAX / (PL_BLOCK / 64)), dim3(PL_BLOCK), 0, stream, bufs, ctl, ops, rs, plans);
-#ifdef DSA_FP_CHECK
-    hipLaunchKernelGGL(k_fp_pre, dim3(1), dim3(PL_BLOCK), (size_t)PB_MAX_W * (sizeof(int64_t) + sizeof(double)), stream, bufs, ctl, ops, rs, plans);
-#endif
-    hipLaunchKernelGGL(k_apply, dim3(PB_GMAX / 4), dim3(PB_BLOCK), lds, stream, bufs, ctl, ops, rs, plans);
-#ifdef DSA_FP_CHECK
-    hipLaunchKernelGGL(k_fp_post, dim3(1), dim3(PL_BLOCK), 0, stream, rs, plans, ctl);
-#endif
+    fp_enqueue_pre(bufs, ctl, ops, rs, plans, stream);
+    hipLaunchKernelGGL(k_apply, dim3(PB_GMAX / 4), dim3(PB_BLOCK), (PB_BLOCK / 64) * PB_WAVE_LDS, stream, bufs, ctl, ops, rs, plans);
+    fp_enqueue_post(rs, plans, ctl, stream);
     return hipGetLastError();
 }
 
@@ -1651,7 +772,7 @@ hipError_t launch_burst(const DevBufs* bufs, Ctl* ctl, const Op* ops, RoundState
         if (cache->graph) { (void)hipGraphDestroy(cache->graph); cache->graph = nullptr; }
         if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
             for (int r = 0; r < rounds; ++r) (void)enqueue_round(bufs, ctl, ops, rs, plans, stream);
-            if (pub.host_seq != nullptr) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, stream, rs, ctl, pub);
+            enqueue_publish(rs, ctl, pub, stream);
             hipGraph_t g = nullptr;
             e = hipStreamEndCapture(stream, &g);
             if (e == hipSuccess && g != nullptr && hipGraphInstantiate(&cache->exec, g, nullptr, nullptr, 0) == hipSuccess) {
@@ -1673,7 +794,7 @@ hipError_t launch_burst(const DevBufs* bufs, Ctl* ctl, const Op* ops, RoundState
         e = enqueue_round(bufs, ctl, ops, rs, plans, stream);
         if (e != hipSuccess) return e;
     }
-    if (pub.host_seq != nullptr) hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, stream, rs, ctl, pub);
+    enqueue_publish(rs, ctl, pub, stream);
     return hipGetLastError();
 }
 
@@ -1711,7 +832,7 @@ __global__ __launch_bounds__(64) void k_dbg_raw_wave(KeyArr keys, double* vals, 
             const int64_t ne = d_next_empty(occ, p, len);
             r_flag = 1;
             if (ne != 0) {                                         // PB_INS_R
-                pb_shift_right(keys, vals, sems, p + 1, ne);
+                pb_shift_right<false>(keys, vals, sems, p + 1, ne);
                 if (lane == 0) { keys[p] = key; vals[p] = val; pb_bit_set(occ, ne); }
                 r_pos = p + 1;
                 break;
@@ -1745,8 +866,7 @@ __global__ __launch_bounds__(64) void k_dbg_raw_wave(KeyArr keys, double* vals, 
 
 hipError_t launch_dbg_raw_wave(KeyArr keys, double* vals, uint64_t* occ, int64_t* sems, int64_t len, int op, int64_t key, double val,
                                int64_t from, int64_t to, int64_t m, int64_t* out, hipStream_t stream) {
-    const size_t lds_bytes = (size_t)PB_MAX_W * (sizeof(int64_t) + sizeof(double));
-    hipLaunchKernelGGL(k_dbg_raw_wave, dim3(1), dim3(64), lds_bytes, stream, keys, vals, occ, sems, len, op, key, val, from, to, m, out);
+    hipLaunchKernelGGL(k_dbg_raw_wave, dim3(1), dim3(64), PB_WAVE_LDS, stream, keys, vals, occ, sems, len, op, key, val, from, to, m, out);
     return hipGetLastError();
 }
 

@@ -2302,7 +2302,7 @@ def _run_child(cmd, env, timeout=600):
 
 @pytest.mark.gpu
 def test_footprint_check_build_fires_on_the_two_resolver_bugs_of_round_4_and_is_clean_on_the_tree(dsa, hip, oracle):
-    """csrc/parbatch.hip, -DDSA_FP_CHECK (libdsa_hip_fpcheck.so): the soundness of a round of the batch-parallel writes checked mechanically —
+    """csrc/pb_fpcheck.h, -DDSA_FP_CHECK (libdsa_hip_fpcheck.so): the soundness of a round of the batch-parallel writes checked mechanically —
     mode 1 re-derives the resolver's verdict by brute force from what every plan literally scanned and counted and every apply touched, mode 2
     applies the prefix one op after the other and requires each op's plan, recomputed on the live state, to equal the plan the round was
     resolved on.  (a) Both modes FAIL on the two libraries that re-introduce the resolver defects of round 4 (DSA_FP_REGRESS=1: the leaf

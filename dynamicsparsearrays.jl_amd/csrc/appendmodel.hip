@@ -20,7 +20,7 @@
 // thresholds and the closed-form counts — and a final descent finds the last rebalance of every level that no wider one followed.
 // The bitmap is written once: those patterns, widest first, then the last leaf.  Nothing is committed before that point: any
 // precondition that fails (counts outside the tables, a leaf without its free slots) leaves the bitmap untouched and the run to
-// k_append_run (sequencer.hip), which also takes over whatever this kernel did not consume.
+// k_append_run (appendrun.hip), which also takes over whatever this kernel did not consume.
 #include "wave_dev.h"
 
 namespace dsa {
@@ -50,10 +50,6 @@ struct M3Shared {
     unsigned long long last_word;
 };
 
-__device__ __forceinline__ int ufl(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t ufl64(uint64_t v) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
 // LDS traffic between the lanes of ONE wave: its LDS instructions execute in order, the fence keeps the compiler from moving them
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -71,7 +67,6 @@ __device__ __forceinline__ int m3_leaf_reject(int c0, int lo0, int hi0) { return
 // its suffix count, the count of its surviving rebalance.  A level's value is broadcast with v_readlane (no memory round trip); the
 // only LDS traffic of a step is the table lookup itself, whose address depends on the time accumulated so far.
 struct M3Lane { int W, lo, hi, cmin, base; };
-__device__ __forceinline__ int rl(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
 struct M3Rec { int tau; uint32_t reb; uint64_t slots; };      // lane i: time of the first visit of level i, what the complete chains below added
 
 // time of the first visit of level `upto` from the suffix counts of the levels below (tables of levels 1 .. upto-1); adds the
@@ -79,15 +74,15 @@ struct M3Rec { int tau; uint32_t reb; uint64_t slots; };      // lane i: time of
 template <bool REC>
 __device__ __forceinline__ int m3_descent(const M3Lane& L, int cnt, const uint64_t* X, int upto, uint32_t& reb, uint64_t& slots, int& bail,
                                           int lane, M3Rec& rec) {
-    int tau = m3_leaf_reject(rl(cnt, 0), rl(L.lo, 0), rl(L.hi, 0));
+    int tau = m3_leaf_reject(readlane32(cnt, 0), readlane32(L.lo, 0), readlane32(L.hi, 0));
     if (REC && lane == 1) { rec.tau = tau; rec.reb = 0; rec.slots = 0; }
 #pragma clang loop unroll(disable)
     for (int i = 1; i < upto; ++i) {
-        const int ci = rl(cnt, i) + tau;
-        if (ci >= rl(L.lo, i) && ci <= rl(L.hi, i)) {
-            const int cm = rl(L.cmin, i);
+        const int ci = readlane32(cnt, i) + tau;
+        if (ci >= readlane32(L.lo, i) && ci <= readlane32(L.hi, i)) {
+            const int cm = readlane32(L.cmin, i);
             if (ci < cm) { bail = 10; return tau; }
-            const uint64_t x = ufl64(X[rl(L.base, i) + ci - cm]);
+            const uint64_t x = readfirstlane64(X[readlane32(L.base, i) + ci - cm]);
             tau += m3_dt(x); reb += m3_reb(x); slots += m3_slots(x);
         }
         if (REC && lane == i + 1) { rec.tau = tau; rec.reb = reb; rec.slots = slots; }
@@ -97,13 +92,13 @@ __device__ __forceinline__ int m3_descent(const M3Lane& L, int cnt, const uint64
 
 // event (k, c): the counts of the levels below k in closed form (lane <-> level); false: the last leaf lost its preconditions
 __device__ __forceinline__ bool m3_reset_below(const M3Lane& L, int& cnt, int k, int c, int lane, int maxc0) {
-    const int Wk = rl(L.W, k);
+    const int Wk = readlane32(L.W, k);
     SpreadGeom g;                                           // make_geom(Wk, c); E / W — only gaps_le's starting guess — by a multiply
     g.W = Wk; g.E = Wk - c;                                 // (W is a power of two: exact either way)
     g.f = g.E > 0 ? (double)Wk / (double)(Wk - c) : 0.0;
     g.inv_f = (double)(Wk - c) * (1.0 / (double)Wk);
     if (lane < k) cnt = m3_suffix_cells(g, Wk, L.W);
-    const int c0 = rl(cnt, 0);
+    const int c0 = readlane32(cnt, 0);
     return c0 >= 1 && c0 <= maxc0;
 }
 
@@ -118,23 +113,23 @@ __device__ int m3_final_descent(const M3Lane& L, int& cnt, const uint64_t* X, co
         M3Rec rec; rec.tau = 0; rec.reb = 0; rec.slots = 0;
         m3_descent<true>(L, cnt, X, kmax, r, s, bail, lane, rec);
         if (bail) return 0;
-        if (rl(rec.tau, 1) > b) return b;
+        if (readlane32(rec.tau, 1) > b) return b;
         int m = 1;
-        while (m + 1 <= kmax && rl(rec.tau, m + 1) <= b) ++m;
+        while (m + 1 <= kmax && readlane32(rec.tau, m + 1) <= b) ++m;
         if (m >= kmax) { bail = 11; return 0; }
-        reb_tot += (uint64_t)(uint32_t)rl((int)rec.reb, m); slots_tot += readlane64(rec.slots, m);
-        const int tt = rl(rec.tau, m);
-        const int c0 = rl(cnt, m) + tt;
-        const int lom = rl(L.lo, m), him = rl(L.hi, m), Wm = rl(L.W, m), cm = rl(L.cmin, m), bm = rl(L.base, m);
+        reb_tot += (uint64_t)(uint32_t)readlane32((int)rec.reb, m); slots_tot += readlane64(rec.slots, m);
+        const int tt = readlane32(rec.tau, m);
+        const int c0 = readlane32(cnt, m) + tt;
+        const int lom = readlane32(L.lo, m), him = readlane32(L.hi, m), Wm = readlane32(L.W, m), cm = readlane32(L.cmin, m), bm = readlane32(L.base, m);
         if (c0 < lom || c0 > him || c0 < cm) { bail = 12; return 0; }
         int c = c0;
         for (;;) {
-            const int dv = ufl((int)Vdt[bm + c - cm]);
+            const int dv = readfirstlane32((int)Vdt[bm + c - cm]);
             if (tt + (c - c0) + dv > b) break;
             c += dv;
             if (c > him) { bail = 14; return 0; }          // (the chain ends behind the budget: cannot happen)
         }
-        const uint64_t x0 = ufl64(X[bm + c0 - cm]), xf = ufl64(X[bm + c - cm]);
+        const uint64_t x0 = readfirstlane64(X[bm + c0 - cm]), xf = readfirstlane64(X[bm + c - cm]);
         reb_tot += (uint64_t)(m3_reb(x0) - m3_reb(xf)) + 1ull;
         slots_tot += (m3_slots(x0) - m3_slots(xf)) + (uint64_t)Wm;
         evmask = (evmask & ~((1ull << m) - 1ull)) | (1ull << m);
@@ -338,8 +333,8 @@ __global__ __launch_bounds__(M3_THREADS) void k_append_model3(uint64_t* occ, Ctl
             const int kacc = __ffsll(am) - 1;
             t += tau;
             if (lane > Lp && lane <= H) cnt = ck;
-            const int c = rl(cnt, kacc);
-            reb_tot += (uint64_t)r + 1ull; slots_tot += s + (uint64_t)rl(L.W, kacc);
+            const int c = readlane32(cnt, kacc);
+            reb_tot += (uint64_t)r + 1ull; slots_tot += s + (uint64_t)readlane32(L.W, kacc);
             evmask = (evmask & ~((1ull << kacc) - 1ull)) | (1ull << kacc);
             if (lane == kacc) evc = c;
             ++top;
@@ -564,7 +559,7 @@ __global__ __launch_bounds__(M3_THREADS) void k_append_model5(uint64_t* occ, Ctl
     const int64_t t_tables = wall_clock64();
     // ---- the epochs: wave 0, lane <-> level ----
     if (wave == 0) {
-        const int end32 = ufl(sEndEff), nsem = ufl(sNSem), KTu = ufl(KT);
+        const int end32 = readfirstlane32(sEndEff), nsem = readfirstlane32(sNSem), KTu = readfirstlane32(KT);
         // per-lane constants of the level; lanes that are no level (0, > H) never accept and never hold a gap
         const bool lvl = lane >= 1 && lane <= H;
         const int lol = lvl ? sh.lo[lane] : 0x7fffffff;
@@ -582,13 +577,13 @@ __global__ __launch_bounds__(M3_THREADS) void k_append_model5(uint64_t* occ, Ctl
             const int s0 = sh.cnt[0];
             const uint32_t leafbits = (uint32_t)(occ[nwords - 1] >> 56);
             const int g0 = __clz((int)leafbits) - 24;
-            e0 = ufl((8 - s0) | ((s0 + g0 == 8 ? 8 - s0 : 0) << 4));
+            e0 = readfirstlane32((8 - s0) | ((s0 + g0 == 8 ? 8 - s0 : 0) << 4));
         }
         int t = 0, sp = 0, bail = 0;
         constexpr int NOSEM = 0x7fffffff;
-        const int semb = ufl((int)(reinterpret_cast<uintptr_t>(Sem) & 0xffffffffu));      // LDS byte address of the semaphore list
-        int ns = nsem > 0 ? ufl((int)Sem[0]) : NOSEM;
-        int ns_next = nsem > 1 ? ufl((int)Sem[1]) : NOSEM;
+        const int semb = readfirstlane32((int)(reinterpret_cast<uintptr_t>(Sem) & 0xffffffffu));      // LDS byte address of the semaphore list
+        int ns = nsem > 0 ? readfirstlane32((int)Sem[0]) : NOSEM;
+        int ns_next = nsem > 1 ? readfirstlane32((int)Sem[1]) : NOSEM;
         // The common epoch — no cross-leaf shift, a level with a table row accepts, the next semaphore still ahead — is a hand-scheduled
         // block of 36 instructions (the compiler's version of the same loop: 55, with its exits merged through mask registers; measured
         // 165 ns per epoch against ~90): one LDS read per epoch, issued as early as its address is known, the bookkeeping of the
@@ -602,7 +597,7 @@ __global__ __launch_bounds__(M3_THREADS) void k_append_model5(uint64_t* occ, Ctl
             while (ns < t) {
                 ++sp;
                 ns = ns_next;
-                ns_next = sp + 1 < nsem ? ufl((int)Sem[sp + 1]) : NOSEM;
+                ns_next = sp + 1 < nsem ? readfirstlane32((int)Sem[sp + 1]) : NOSEM;
             }
             int status = 4;
             if (use_asm) {
@@ -698,14 +693,14 @@ __global__ __launch_bounds__(M3_THREADS) void k_append_model5(uint64_t* occ, Ctl
             const unsigned long long am = __builtin_amdgcn_ballot_w64((unsigned)(cn - lol) <= rngl);
             if (am == 0ull) break;                                   // no level accepts: _extend! — the epoch is k_append_run's too
             const int kacc = __ffsll(am) - 1;
-            const int c = rl(cn, kacc);
+            const int c = readlane32(cn, kacc);
             int nv;
             if (__builtin_expect(kacc <= KTu, 1)) {
-                const int rowaddr = rl(off2, kacc) + c * (kacc << 1);
+                const int rowaddr = readlane32(off2, kacc) + c * (kacc << 1);
                 nv = (int)*reinterpret_cast<const __attribute__((address_space(3))) uint16_t*>((uintptr_t)(unsigned)(rowaddr + lane2));
             } else {
                 // an event above the tables (windows beyond 4096 slots: one in a thousand): its row by lanes
-                const int Wk = rl(Wl, kacc);
+                const int Wk = readlane32(Wl, kacc);
                 const SpreadGeom gg = make_geom(Wk, c);
                 const int s1 = m3_suffix_cells(gg, Wk, 8), g1 = (int)(Wk - spread_last_cell(gg));
                 nv = lane == 0 ? ((8 - s1) | ((s1 + g1 == 8 ? 8 - s1 : 0) << 4)) : (lane < kacc ? m3_suffix_cells(gg, Wk, Wl) : 0);
@@ -718,7 +713,7 @@ __global__ __launch_bounds__(M3_THREADS) void k_append_model5(uint64_t* occ, Ctl
                 nev += me ? 1u : 0u;
             }
             cnt = lane < kacc ? nv : cn;
-            e0 = ufl(nv);
+            e0 = readfirstlane32(nv);
         }
         // rebalances and window slots: per level, summed over the lanes
         unsigned long long slots = (unsigned long long)nev * (unsigned long long)(lvl ? Wl : 0);
@@ -729,7 +724,7 @@ __global__ __launch_bounds__(M3_THREADS) void k_append_model5(uint64_t* occ, Ctl
         // the surviving rebalance of every level: no wider one came later
         int later = -1;
         for (int k = H; k >= 1; --k) {
-            const int e = rl(evt, k);
+            const int e = readlane32(evt, k);
             if (lane == 0 && e > later) sh.ev_mask |= 1ull << k;
             later = e > later ? e : later;
         }

@@ -3,7 +3,7 @@
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, fill_host.hip, matwrite_host.hip, pma_host.hip,
 // writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, mutate_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, insert_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
-// export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
+// seq_dev.h, export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
 #pragma once
 #include "../../include/dsa.h"
@@ -124,7 +124,7 @@ struct Pma {
     RebalanceWork work2{nullptr, nullptr, 0};   // second prefix table of K-permute (old and new bitmap)
     uint64_t* occ_old = nullptr;                // bitmap saved by the sequencer at the start of an append run
     Op* run_cells = nullptr; uint64_t* run_flags = nullptr; int64_t* run_out = nullptr; int64_t run_cap = 0;   // cell stream of a MappedPackedCSC append run
-    uint64_t* run_memo = nullptr;               // the append replay's memo between runs (sequencer.hip: k_append_run)
+    uint64_t* run_memo = nullptr;               // the append replay's memo between runs (appendrun.hip: k_append_run)
     Op* d_ops = nullptr; int64_t ops_cap = 0;
     int wait_policy = g_wait_policy_default;      // how blocking calls wait for a hand-over: 0 spin on the pinned word, 1 block in hipStreamSynchronize first (dsa_*_set_wait_policy)
     uint64_t* d_breaks = nullptr; bool breaks_valid = false;      // run-break bitmap of the ops in d_ops (sequencer.hip: k_op_breaks)

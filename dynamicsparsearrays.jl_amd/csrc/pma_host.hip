@@ -319,7 +319,7 @@ void build_from_packed(Pma& P, const std::vector<int64_t>& keys, const std::vect
     upload_ctl(P);
 }
 
-// An append run was simulated on the bitmap of the current buffer (sequencer.hip): the y_we cells that existed before the
+// An append run was simulated on the bitmap of the current buffer (appendrun.hip): the y_we cells that existed before the
 // run (positions: saved bitmap occ_old) followed by the cells cells[i0..] move to the set bits of the current bitmap,
 // written into the alternate buffer, which becomes current.
 void permute_run(Pma& P, const Op* cells, int64_t i0, int64_t n0) {

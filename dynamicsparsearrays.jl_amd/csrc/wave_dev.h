@@ -44,7 +44,15 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v) {
     return x - v;
 }
 
-// ---- a 64-bit value of lane l / of the first active lane, as a wave-uniform value
+// ---- a value of lane l / of the first active lane, as a wave-uniform value: 32 bits (int or uint32_t, the type is kept), 64 bits
+template <typename T> __device__ __forceinline__ T readlane32(T v, int l) {
+    static_assert(sizeof(T) == 4, "one register");
+    return (T)__builtin_amdgcn_readlane((int)v, l);
+}
+template <typename T> __device__ __forceinline__ T readfirstlane32(T v) {
+    static_assert(sizeof(T) == 4, "one register");
+    return (T)__builtin_amdgcn_readfirstlane((int)v);
+}
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int l) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);

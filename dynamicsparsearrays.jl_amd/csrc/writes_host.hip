@@ -220,7 +220,7 @@ bool seq_step(SeqRun& r) {
                 LAUNCH("run expand", launch_run_expand(P.d_ops, i0, R, P.d_ctl, P.col_keys, P.col_live, P.run_cells, P.run_flags, P.run_out, P.stream));
             }
             HIPCHK(hipMemcpyAsync(P.occ_old, P.O(), (size_t)words * sizeof(uint64_t), hipMemcpyDeviceToDevice, P.stream));
-            if (!P.run_memo) {                  // the memo of k_append_run, then the 8 result words of k_append_model3
+            if (!P.run_memo) {                  // the memo of k_append_run (appendrun.hip), then the 8 result words of k_append_model3
                 HIPCHK(hipMalloc(&P.run_memo, append_run_memo_bytes() + 8 * sizeof(int64_t)));
                 HIPCHK(hipMemsetAsync(P.run_memo, 0, append_run_memo_bytes() + 8 * sizeof(int64_t), P.stream));
             }

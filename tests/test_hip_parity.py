@@ -1903,7 +1903,7 @@ def test_append_runs_count_only_model_on_a_built_matrix_with_ragged_columns(dsa,
 
 def test_append_memo_survives_runs_on_one_geometry_and_is_dropped_at_extend(dsa, hip, oracle):
     """Several append runs on the SAME handle: the replay's memo (a pure function of the geometry) is reloaded from HBM while the
-    capacity is unchanged and rebuilt after _extend! (csrc/sequencer.hip: k_append_run, saved_memo).  Vector runs and matrix runs
+    capacity is unchanged and rebuilt after _extend! (csrc/appendrun.hip: k_append_run, saved_memo).  Vector runs and matrix runs
     with columns of different lengths (epochs through semaphore cells are keyed by the cell types)."""
     n0 = 300000
     keys0 = np.arange(1, n0 + 1, dtype=np.int64) * 2

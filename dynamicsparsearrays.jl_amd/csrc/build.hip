@@ -20,9 +20,11 @@
 //            rank-1 + partition_id ; every first-of-partition lane writes the semaphore cell (0, id) at rank-1 + id-1 and the
 //            partition key.  Runs longer than 64 duplicates are finished by a wave each (k_fold_long): coalesced loads, the same
 //            left-to-right order.
-// Composites that do not fit 64 bits (partition AND key ranges beyond 2^32) take the general path at the end of the file: two
-// stable 64-bit sorts by key then by partition (rocPRIM) carrying the input index.
+// Composites that do not fit 64 bits (partition AND key ranges beyond 2^32) take the general path: the same radix kernels in two
+// stable runs, by key and then by partition, carrying the input index as the payload (launch_pair_sort, shared with insert.hip).
 // Bound: HBM (sort passes: 40 B per triple and pass).
+// Order of the file: kernels; host side: launch helpers (scratch, min / max pass, radix run, count and emit tails), the composite
+// path, the general path, and the entry points that choose between the two.
 #include "wave_dev.h"
 #include "pairsort.h"
 #include <functional>
@@ -30,8 +32,6 @@
 #include <algorithm>
 #include <atomic>
 #include <cstring>
-#include <mutex>
-#include <vector>
 
 namespace dsa {
 
@@ -367,7 +367,6 @@ __global__ __launch_bounds__(1024) void k_bf_scan(uint32_t* __restrict__ cnt_c, 
         }
     }
 }
-static std::atomic<unsigned long long> g_count_seq{0x5eed0000ull};
 
 __device__ __forceinline__ double bld_combine(double a, double b, int32_t combine) {
     return combine == 0 ? a + b : (combine == 1 ? a * b : b);
@@ -604,41 +603,6 @@ __global__ void k_emit_sems_wide(const int64_t* __restrict__ part_sorted, const 
     out_vals[pos] = (double)p;
 }
 
-// ---- host side ----------------------------------------------------------------------------------------------------------
-// The scratch of a build is ONE block from the caching allocator (pool.hip), carved into its arrays: a second build of the same
-// size finds it again without a driver call.
-// the pinned mirror of BuildCtl: a handful of them are kept (hipHostMalloc / hipHostFree cost more than a sort pass)
-static std::mutex g_pin_mu;
-static std::vector<void*> g_pin_free;
-static hipError_t pinned_ctl_get(void** out) {
-    {
-        std::lock_guard<std::mutex> lk(g_pin_mu);
-        if (!g_pin_free.empty()) { *out = g_pin_free.back(); g_pin_free.pop_back(); return hipSuccess; }
-    }
-    return hipHostMalloc(out, 256, hipHostMallocDefault);
-}
-static void pinned_ctl_put(void* p) {
-    std::lock_guard<std::mutex> lk(g_pin_mu);
-    if (g_pin_free.size() < 16) g_pin_free.push_back(p); else (void)hipHostFree(p);
-}
-static void free_scratch(BuildScratch& s) {
-    if (s.base) pool_free(s.base);
-    if (s.base_val) pool_free(s.base_val);
-    if (s.h_ctl) pinned_ctl_put(s.h_ctl);
-    s = BuildScratch();
-}
-
-// error path: the scratch comes from the caching allocator (pool.hip), which hands a freed block out again at once — earlier passes
-// may still be in flight on it, so the build stream is drained first (build_abort does the same)
-#define BCHK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { if (s.stream) (void)hipStreamSynchronize(s.stream); free_scratch(s); return _e; } } while (0)
-
-static int bit_width_u64(uint64_t x) { int b = 0; while (x) { ++b; x >>= 1; } return b; }
-
-static hipError_t prepare_wide(const int64_t* d_part, const int64_t* d_key, int64_t nnz, BuildScratch& s, int64_t counts[2], hipStream_t stream,
-                               int64_t kmin, int kbits, int64_t pmin, int pbits);
-
-// value ranges and reserved-key check of two key arrays that are already in HBM (a and b: rows and columns of a triple stream): one
-// pass on the device instead of a host loop over arrays the host would otherwise not touch at all; synchronises the stream
 // ---- a vector of up to 1024 entries in ONE launch (dynamicsparsevec of a small input, src/vector.jl:10-62): the workgroup reads the caller's
 // (key, value) pairs from a pinned landing area, ranks them (stable: equal keys keep their input order), folds equal keys left to right
 // with `combine` (_prepare_keys_vals!, src/vector.jl:10-36) and writes the packed stream in front of the slot buffers; the number of
@@ -691,129 +655,195 @@ hipError_t launch_build_small_vec(int64_t* io, int n, int cap, int32_t combine, 
     return hipGetLastError();
 }
 
+// ---- host side: launch helpers --------------------------------------------------------------------------------------------
+// The scratch of a build is ONE block from the caching allocator (pool.hip), carved into its arrays (Carver, pairsort.h): a second
+// build of the same size finds it again without a driver call.  The pinned mirror of BuildCtl is a block of pool.hip's pinned list
+// (hipHostMalloc / hipHostFree cost more than a sort pass).
+constexpr size_t CTL_BYTES = 256;                      // BuildCtl in HBM and its pinned mirror, padded
+constexpr size_t MM_BYTES = 4 * MM_BLOCKS * 8;         // k_minmax's partials; its ticket and zero flags are the 8 bytes behind them
+static_assert(sizeof(BuildCtl) <= CTL_BYTES && PAIR_SORT_TILE == RS_TILE && PAIR_SORT_GHIST_BYTES == 8 * RS_BINS * 4 + 64,
+              "pairsort.h sizes the histograms by the tile and the digit of the radix pass");
+
+static void free_scratch(BuildScratch& s) {
+    if (s.base) pool_free(s.base);
+    if (s.base_val) pool_free(s.base_val);
+    if (s.h_ctl) pinned_free(s.h_ctl);
+    s = BuildScratch();
+}
+
+// error path: the scratch comes from the caching allocator (pool.hip), which hands a freed block out again at once — earlier passes
+// may still be in flight on it, so the build stream is drained first (build_abort does the same)
+#define BCHK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { if (s.stream) (void)hipStreamSynchronize(s.stream); free_scratch(s); return _e; } } while (0)
+
+static int bit_width_u64(uint64_t x) { int b = 0; while (x) { ++b; x >>= 1; } return b; }
+
+// one block of the caching allocator for what `layout` takes from a Carver: run once from a null base for the size, once from the block
+template <typename Layout> static hipError_t pool_carve(void** base, Layout layout) {
+    Carver size(nullptr);
+    layout(size);
+    const hipError_t e = pool_alloc(base, size.bytes());
+    if (e != hipSuccess) return e;
+    Carver c(*base);
+    layout(c);
+    return hipSuccess;
+}
+// The three layouts of a build's block over s.n elements.  COMPOSITE: the sort of the caller's triples; DERIVED: the twin's, whose
+// cells are distinct (no scell: mode 0 only); WIDE: the general path, whose pair sort leaves index, keys and partitions and whose
+// flags and their prefix sums are arrays (no min / max partials behind the digit totals, no queue of long runs).
+enum ScratchKind { SCRATCH_COMPOSITE, SCRATCH_DERIVED, SCRATCH_WIDE };
+static void scratch_layout(Carver& c, BuildScratch& s, ScratchKind kind) {
+    const size_t n = (size_t)s.n, nblocks = (n + RS_TILE - 1) / RS_TILE;
+    const bool wide = kind == SCRATCH_WIDE;
+    s.d_ctl = c.take<BuildCtl>(sizeof(BuildCtl));
+    s.ghist = c.take<uint32_t>(PAIR_SORT_GHIST_BYTES + (wide ? 0 : MM_BYTES));
+    s.comp[0] = c.take<uint64_t>(n * 8); s.comp[1] = c.take<uint64_t>(n * 8);
+    if (wide) {
+        s.val[0] = c.take<double>(n * 8); s.val[1] = c.take<double>(n * 8);
+        s.k2 = c.take<int64_t>(n * 8); s.p2 = c.take<int64_t>(n * 8);
+        s.idx2 = c.take<uint32_t>(n * 4); s.fpart = c.take<uint32_t>(n * 4); s.fcell = c.take<uint32_t>(n * 4);
+        s.spart = c.take<uint32_t>(n * 4); s.scell = c.take<uint32_t>(n * 4);
+    }
+    s.hist = c.take<uint32_t>(RS_BINS * nblocks * 4);
+    s.cnt_c = c.take<uint32_t>((nblocks + 1) * 4); s.cnt_p = c.take<uint32_t>((nblocks + 1) * 4);
+    if (!wide) s.queue = c.take<LongRun>((n / FOLD_INLINE + 2) * sizeof(LongRun));
+    if (kind == SCRATCH_COMPOSITE) s.scell = c.take<uint32_t>(n * 4);
+}
+// the pinned mirror and the block of a build over s.n elements
+static hipError_t scratch_alloc(BuildScratch& s, ScratchKind kind) {
+    const hipError_t e = pinned_alloc(&s.h_ctl, CTL_BYTES);
+    return e != hipSuccess ? e : pool_carve(&s.base, [&](Carver& c) { scratch_layout(c, s, kind); });
+}
+// the two value arrays — 16 bytes per element — are a block of their own, taken only when the values really travel with the sorted
+// words: the index-in-word sort of config 3 never touches them, and the block used to be held, untouched, all the same
+static hipError_t scratch_alloc_values(BuildScratch& s) {
+    return pool_carve(&s.base_val, [&](Carver& c) { s.val[0] = c.take<double>((size_t)s.n * 8); s.val[1] = c.take<double>((size_t)s.n * 8); });
+}
+
+// the min / max pass: ticket zeroed, k_minmax over (d_a or nullptr, d_b), BuildCtl copied to `host` (pinned), the stream waited for
+static hipError_t minmax_pass(const int64_t* d_a, const int64_t* d_b, int64_t n, BuildCtl* dctl, long long* partial /*MM_BYTES + 8*/, BuildCtl* host,
+                              hipStream_t stream) {
+    unsigned int* ticket = reinterpret_cast<unsigned int*>(partial + 4 * MM_BLOCKS);
+    hipError_t e = hipMemsetAsync(ticket, 0, 2 * sizeof(unsigned int), stream);
+    if (e != hipSuccess) return e;
+    const int mm_blocks = (int)std::min<int64_t>(MM_BLOCKS, (n + 1023) / 1024);
+    hipLaunchKernelGGL(k_minmax, dim3(mm_blocks), dim3(256), 0, stream, d_a, d_b, n, dctl, partial, ticket);
+    e = hipMemcpyAsync(host, dctl, sizeof(BuildCtl), hipMemcpyDeviceToHost, stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(stream);
+}
+
+// One run of the stable LSD radix sort: ceil(bits / 8) passes — histogram, k_rs_scan, scatter — from bit shift0 on, over the two
+// word buffers and, when the words carry a payload, the two payload buffers; word[cur] / pay[cur] hold the current order and are
+// updated to where the result is.  pay0: where the payload of the FIRST pass is read (the caller's values, never written); without
+// payload buffers it is only handed through to pay_sorted.  comp0: pass 0's histogram is k_comp_hist with these arguments, which also
+// writes the words it counts.  Enqueues only.
+struct CompHist { const int64_t* part; const int64_t* key; int64_t pmin, kmin; int kbits, ibits; };
+struct RadixRun {
+    int64_t n; int shift0, bits;
+    uint64_t* const* word; double* const* pay;      // [2] each; pay == nullptr: 8-byte words alone
+    uint32_t* hist; uint32_t* ghist;                // RS_BINS x tiles counts, one row of RS_BINS digit totals per pass
+    const double* pay0 = nullptr; const CompHist* comp0 = nullptr;
+    int cur = 0; const double* pay_sorted = nullptr;
+};
+static hipError_t radix_run(RadixRun& r, hipStream_t stream) {
+    static PerDeviceOnce once;
+    const size_t lds_words = (size_t)RS_TILE * sizeof(uint64_t), lds_pairs = lds_words + (size_t)RS_TILE * sizeof(double);
+    const hipError_t e = once.run([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pairs); });
+    if (e != hipSuccess) return e;
+    const int64_t n = r.n, nblocks = (n + RS_TILE - 1) / RS_TILE;
+    const dim3 grid((unsigned)nblocks), block(RS_BLOCK);
+    const int npass = (r.bits + 7) / 8;
+    const double* pin = r.pay0 != nullptr || r.pay == nullptr ? r.pay0 : r.pay[r.cur];
+    for (int pass = 0; pass < npass; ++pass) {
+        const int shift = r.shift0 + 8 * pass, cur = r.cur;
+        uint32_t* dtot = r.ghist + pass * RS_BINS;
+        if (pass == 0 && r.comp0 != nullptr) {
+            const CompHist& c = *r.comp0;
+            hipLaunchKernelGGL(k_comp_hist, grid, block, 0, stream, c.part, c.key, n, c.pmin, c.kmin, c.kbits, c.ibits, r.word[cur], shift, r.hist, nblocks);
+        } else hipLaunchKernelGGL(k_rs_hist, grid, block, 0, stream, (const uint64_t*)r.word[cur], n, shift, r.hist, nblocks);
+        hipLaunchKernelGGL(k_rs_scan, dim3(RS_BINS), block, 0, stream, r.hist, dtot, nblocks);
+        if (r.pay == nullptr)
+            hipLaunchKernelGGL(k_rs_scatter<false>, grid, block, lds_words, stream, (const uint64_t*)r.word[cur], (const double*)nullptr, n, shift,
+                               (const uint32_t*)r.hist, (const uint32_t*)dtot, r.word[1 - cur], (double*)nullptr, nblocks);
+        else
+            hipLaunchKernelGGL(k_rs_scatter<true>, grid, block, lds_pairs, stream, (const uint64_t*)r.word[cur], pin, n, shift, (const uint32_t*)r.hist,
+                               (const uint32_t*)dtot, r.word[1 - cur], r.pay[1 - cur], nblocks);
+        r.cur = 1 - cur;
+        if (r.pay != nullptr) pin = r.pay[r.cur];
+    }
+    r.pay_sorted = pin;
+    return hipGetLastError();
+}
+
+// The count tail of a composite sort (s.sorted, s.kbits, s.ibits set): per-tile counts of new cells / new partitions, their prefixes,
+// the totals handed to the pinned mirror by k_bf_scan itself; while_sorting — host work of the caller that does not need the counts
+// (allocations) — runs with everything in flight; then the wait for the hand-over.
+static std::atomic<unsigned long long> g_count_seq{0x5eed0000ull};
+static hipError_t count_tail(BuildScratch& s, bool has_part, int64_t counts[2], const std::function<void()>* while_sorting) {
+    const int64_t nblocks = (s.n + RS_TILE - 1) / RS_TILE;
+    BuildCtl* dctl = static_cast<BuildCtl*>(s.d_ctl);
+    BuildCtl* hctl = static_cast<BuildCtl*>(s.h_ctl);
+    hipLaunchKernelGGL(k_bf_count, dim3((unsigned)nblocks), dim3(RS_BLOCK), 0, s.stream, (const uint64_t*)s.comp[s.sorted], s.n, s.kbits, s.ibits,
+                       has_part ? 1 : 0, s.cnt_c, s.cnt_p);
+    const unsigned long long seq = ++g_count_seq;
+    hctl->zeros = 0;
+    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, s.stream, s.cnt_c, s.cnt_p, nblocks, dctl, reinterpret_cast<unsigned long long*>(hctl), seq);
+    if (while_sorting && *while_sorting) {
+        try { (*while_sorting)(); } catch (...) { (void)hipStreamSynchronize(s.stream); throw; }
+    }
+    BCHK(wait_pinned_seq(&hctl->zeros, seq, s.stream));       // k_bf_scan's hand-over (the word it writes last)
+    counts[0] = (int64_t)hctl->ncells; counts[1] = (int64_t)hctl->nparts;
+    return hipGetLastError();
+}
+
+// the end of both emits: only enqueued (wait_and_free == false: the caller enqueues more behind the emit and calls build_abort(s)
+// after its own stream wait), or waited for and the scratch released
+static hipError_t emit_tail(BuildScratch& s, hipStream_t stream, bool wait_and_free) {
+    hipError_t e = hipGetLastError();
+    if (!wait_and_free) return e;
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    free_scratch(s);
+    return e;
+}
+
+// ---- the composite path -----------------------------------------------------------------------------------------------------
+// value ranges and reserved-key check of two key arrays that are already in HBM (a and b: rows and columns of a triple stream): one
+// pass on the device instead of a host loop over arrays the host would otherwise not touch at all; synchronises the stream
 hipError_t device_key_scan(const int64_t* d_a, const int64_t* d_b, int64_t n, KeyRange* ra, KeyRange* rb, bool* a_zero, bool* b_zero,
                            hipStream_t stream) {
     *ra = KeyRange(); *rb = KeyRange(); *a_zero = *b_zero = false;
     if (n <= 0) return hipSuccess;
     void* base = nullptr; void* pin = nullptr;
-    hipError_t e = pool_alloc(&base, 256 + 4 * MM_BLOCKS * 8 + 64);
+    hipError_t e = pool_alloc(&base, CTL_BYTES + MM_BYTES + 64);
     if (e != hipSuccess) return e;
-    e = pinned_ctl_get(&pin);
+    e = pinned_alloc(&pin, CTL_BYTES);
     if (e != hipSuccess) { pool_free(base); return e; }
-    BuildCtl* dctl = static_cast<BuildCtl*>(base);
-    long long* partial = reinterpret_cast<long long*>(static_cast<char*>(base) + 256);
-    unsigned int* ticket = reinterpret_cast<unsigned int*>(partial + 4 * MM_BLOCKS);
-    e = hipMemsetAsync(ticket, 0, 2 * sizeof(unsigned int), stream);
-    if (e == hipSuccess) {
-        const int mm_blocks = (int)std::min<int64_t>(MM_BLOCKS, (n + 1023) / 1024);
-        hipLaunchKernelGGL(k_minmax, dim3(mm_blocks), dim3(256), 0, stream, d_a, d_b, n, dctl, partial, ticket);
-        e = hipMemcpyAsync(pin, dctl, sizeof(BuildCtl), hipMemcpyDeviceToHost, stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    e = minmax_pass(d_a, d_b, n, static_cast<BuildCtl*>(base), reinterpret_cast<long long*>(static_cast<char*>(base) + CTL_BYTES), static_cast<BuildCtl*>(pin), stream);
     if (e == hipSuccess) {
         const BuildCtl* h = static_cast<const BuildCtl*>(pin);
         ra->lo = h->pmin; ra->hi = h->pmax; rb->lo = h->kmin; rb->hi = h->kmax;
         *a_zero = (h->zeros & 1ull) != 0; *b_zero = (h->zeros & 2ull) != 0;
     }
     if (e != hipSuccess) (void)hipStreamSynchronize(stream);      // a failed copy / wait: the kernel may still be running on the block
-    pinned_ctl_put(pin);
+    pinned_free(pin);
     pool_free(base);
     return e;
 }
 
-// Phase 1: sort + flags + counts.  d_part / d_key / d_val: the nnz input triples in HBM (d_part == nullptr: a plain vector).
-// Returns the number of distinct cells and of partitions through counts[0..1] (host).  The scratch stays alive for phase 2
-// (build_emit), which writes counts[0] + #partitions stream cells.
-hipError_t build_prepare(const int64_t* d_part, const int64_t* d_key, const double* d_val, int64_t nnz, KeyRange part_range, KeyRange key_range,
-                         BuildScratch& s, int64_t counts[2], hipStream_t stream, const std::function<void()>* while_sorting) {
-    s = BuildScratch();
-    s.n = nnz; s.stream = stream;
-    const size_t n = (size_t)nnz;
-    static const bool force_wide = [] { const char* e = dev_env("DSA_BUILD_WIDE"); return e && e[0] == '1'; }();
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const int64_t nblocks = (nnz + RS_TILE - 1) / RS_TILE;
-    BCHK(pinned_ctl_get(&s.h_ctl));
-    const size_t b_ctl = up(sizeof(BuildCtl)), b_gh = up(8 * RS_BINS * 4 + 4 * MM_BLOCKS * 8 + 64), b_comp = up(n * 8),
-                 b_hist = up((size_t)RS_BINS * nblocks * 4), b_cnt = up((size_t)(nblocks + 1) * 4),
-                 b_queue = up((n / FOLD_INLINE + 2) * sizeof(LongRun)), b_scell = up(n * 4);
-    // (the two value arrays — 16 bytes per triple — are a block of their own, taken further down only when the values really travel
-    // with the sorted words: the index-in-word sort of config 3 never touches them, and the block used to be held, untouched, all the same)
-    BCHK(pool_alloc(&s.base, b_ctl + b_gh + 2 * b_comp + b_hist + 2 * b_cnt + b_queue + b_scell));
-    char* q = static_cast<char*>(s.base);
-    auto take = [&q](size_t b) { char* r = q; q += b; return r; };
-    s.d_ctl = take(b_ctl); s.ghist = (uint32_t*)take(b_gh);
-    s.comp[0] = (uint64_t*)take(b_comp); s.comp[1] = (uint64_t*)take(b_comp);
-    s.hist = (uint32_t*)take(b_hist); s.cnt_c = (uint32_t*)take(b_cnt); s.cnt_p = (uint32_t*)take(b_cnt);
-    s.queue = take(b_queue); s.scell = (uint32_t*)take(b_scell);
-    BuildCtl* dctl = static_cast<BuildCtl*>(s.d_ctl);
-    BuildCtl* hctl = static_cast<BuildCtl*>(s.h_ctl);
-    // ---- key ranges: how many bits the composite needs
-    if (!key_range.known() || (d_part != nullptr && !part_range.known())) {
-        long long* partial = reinterpret_cast<long long*>(s.ghist + 8 * RS_BINS);
-        unsigned int* ticket = reinterpret_cast<unsigned int*>(partial + 4 * MM_BLOCKS);
-        BCHK(hipMemsetAsync(ticket, 0, 2 * sizeof(unsigned int), stream));
-        const int mm_blocks = (int)std::min<int64_t>(MM_BLOCKS, (nnz + 1023) / 1024);
-        hipLaunchKernelGGL(k_minmax, dim3(mm_blocks), dim3(256), 0, stream, d_part, d_key, nnz, dctl, partial, ticket);
-        BCHK(hipMemcpyAsync(hctl, dctl, sizeof(BuildCtl), hipMemcpyDeviceToHost, stream));
-        BCHK(hipStreamSynchronize(stream));
-        key_range.lo = hctl->kmin; key_range.hi = hctl->kmax;
-        if (d_part) { part_range.lo = hctl->pmin; part_range.hi = hctl->pmax; }
-    }
-    s.kmin = key_range.lo; s.pmin = d_part ? part_range.lo : 0;
-    s.kbits = std::max(1, bit_width_u64((uint64_t)key_range.hi - (uint64_t)key_range.lo));
-    s.pbits = d_part ? bit_width_u64((uint64_t)part_range.hi - (uint64_t)part_range.lo) : 0;
-    if (s.kbits + s.pbits > 64 || force_wide) {
-        const int64_t kmin = s.kmin, pmin = s.pmin;
-        const int kbits = s.kbits, pbits = s.pbits;
-        free_scratch(s);
-        s.n = nnz; s.stream = stream; s.wide_path = true;
-        return prepare_wide(d_part, d_key, nnz, s, counts, stream, kmin, kbits, pmin, pbits);
-    }
-    // ---- the sort: passes over bits [0, kbits + pbits).  When composite + input index fit one 64-bit word the passes move 8-byte
-    //      words without a payload (half the bytes, half the LDS per tile) and the values are gathered by index at the emit
-    static PerDeviceOnce once;
-    const size_t lds_bytes = (size_t)RS_TILE * (sizeof(uint64_t) + sizeof(double));
-    BCHK(once.run([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }));
+// sort + flags + counts of a scratch whose ranges and bit widths build_prepare (at the end of the file) has fixed: passes over bits
+// [0, kbits + pbits).  When composite + input index fit one 64-bit word the passes move 8-byte words without a payload (half the
+// bytes, half the LDS per tile) and the values are gathered by index at the emit; otherwise the values travel with the words.
+static hipError_t composite_sort(const int64_t* d_part, const int64_t* d_key, const double* d_val, BuildScratch& s, int64_t counts[2],
+                                 const std::function<void()>* while_sorting) {
     const int total_bits = s.kbits + s.pbits;
-    const int ibits_need = std::max(1, bit_width_u64((uint64_t)(nnz - 1)));
+    const int ibits_need = std::max(1, bit_width_u64((uint64_t)(s.n - 1)));
     s.ibits = total_bits + ibits_need <= 64 ? ibits_need : 0;
-    if (s.ibits == 0) {
-        BCHK(pool_alloc(&s.base_val, 2 * b_comp));
-        s.val[0] = static_cast<double*>(s.base_val); s.val[1] = reinterpret_cast<double*>(static_cast<char*>(s.base_val) + b_comp);
-    }
-    const int npass = (total_bits + 7) / 8;
-    const dim3 grid((unsigned)nblocks), block(RS_BLOCK);
-    int cur = 0;                                    // comp[cur] holds the current order; values: d_val before the first scatter
-    const double* vin = d_val;
-    for (int pass = 0; pass < npass; ++pass) {
-        const int shift = s.ibits + 8 * pass;
-        uint32_t* dtot = s.ghist + pass * RS_BINS;
-        if (pass == 0) hipLaunchKernelGGL(k_comp_hist, grid, block, 0, stream, s.pbits > 0 ? d_part : (const int64_t*)nullptr, d_key, nnz, s.pmin, s.kmin, s.kbits, s.ibits, s.comp[0], shift, s.hist, nblocks);
-        else hipLaunchKernelGGL(k_rs_hist, grid, block, 0, stream, (const uint64_t*)s.comp[cur], nnz, shift, s.hist, nblocks);
-        hipLaunchKernelGGL(k_rs_scan, dim3(RS_BINS), block, 0, stream, s.hist, dtot, nblocks);
-        if (s.ibits > 0)
-            hipLaunchKernelGGL(k_rs_scatter<false>, grid, block, (size_t)RS_TILE * sizeof(uint64_t), stream, (const uint64_t*)s.comp[cur], (const double*)nullptr, nnz, shift,
-                               (const uint32_t*)s.hist, (const uint32_t*)dtot, s.comp[1 - cur], (double*)nullptr, nblocks);
-        else
-            hipLaunchKernelGGL(k_rs_scatter<true>, grid, block, lds_bytes, stream, (const uint64_t*)s.comp[cur], vin, nnz, shift, (const uint32_t*)s.hist,
-                               (const uint32_t*)dtot, s.comp[1 - cur], s.val[1 - cur], nblocks);
-        cur = 1 - cur;
-        if (s.ibits == 0) vin = s.val[cur];
-    }
-    s.sorted = cur;
-    s.vsorted = vin;                                // (ibits > 0: still the caller's array)
-    // ---- flags: per-tile counts of new cells / new partitions, their prefixes, the totals
-    hipLaunchKernelGGL(k_bf_count, grid, block, 0, stream, (const uint64_t*)s.comp[cur], nnz, s.kbits, s.ibits, d_part ? 1 : 0, s.cnt_c, s.cnt_p);
-    const unsigned long long seq = ++g_count_seq;
-    hctl->zeros = 0;
-    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, stream, s.cnt_c, s.cnt_p, nblocks, dctl, reinterpret_cast<unsigned long long*>(hctl), seq);
-    // everything above is in flight: host work of the caller that does not need the counts (allocations) goes here
-    if (while_sorting && *while_sorting) {
-        try { (*while_sorting)(); } catch (...) { (void)hipStreamSynchronize(stream); throw; }
-    }
-    BCHK(wait_pinned_seq(&hctl->zeros, seq, stream));       // k_bf_scan's hand-over (the word it writes last)
-    counts[0] = (int64_t)hctl->ncells; counts[1] = (int64_t)hctl->nparts;
-    return hipGetLastError();
+    if (s.ibits == 0) BCHK(scratch_alloc_values(s));
+    const CompHist comp0{s.pbits > 0 ? d_part : nullptr, d_key, s.pmin, s.kmin, s.kbits, s.ibits};
+    RadixRun r{s.n, s.ibits, total_bits, s.comp, s.ibits == 0 ? s.val : nullptr, s.hist, s.ghist, d_val, &comp0};
+    BCHK(radix_run(r, s.stream));
+    s.sorted = r.cur;
+    s.vsorted = r.pay_sorted;                       // (ibits > 0: still the caller's array)
+    return count_tail(s, d_part != nullptr, counts, while_sorting);
 }
 
 // ---- the TWIN orientation of a matrix from the cells its sibling has just emitted (mat_build_both_dev) ------------------------------
@@ -825,65 +855,22 @@ hipError_t build_prepare(const int64_t* d_part, const int64_t* d_key, const doub
 hipError_t build_derived_alloc(BuildScratch& s, int64_t n, int kbits, int pbits, int64_t kmin, int64_t pmin, hipStream_t stream) {
     s = BuildScratch();
     s.n = n; s.stream = stream;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const int64_t nblocks = (n + RS_TILE - 1) / RS_TILE;
-    BCHK(pinned_ctl_get(&s.h_ctl));
-    const size_t nn = (size_t)n;
-    const size_t b_ctl = up(sizeof(BuildCtl)), b_gh = up(8 * RS_BINS * 4 + 4 * MM_BLOCKS * 8 + 64), b_comp = up(nn * 8),
-                 b_hist = up((size_t)RS_BINS * nblocks * 4), b_cnt = up((size_t)(nblocks + 1) * 4), b_queue = up((nn / FOLD_INLINE + 2) * sizeof(LongRun));
-    BCHK(pool_alloc(&s.base, b_ctl + b_gh + 2 * b_comp + b_hist + 2 * b_cnt + b_queue));
-    char* q = static_cast<char*>(s.base);
-    auto take = [&q](size_t b) { char* r = q; q += b; return r; };
-    s.d_ctl = take(b_ctl); s.ghist = (uint32_t*)take(b_gh);
-    s.comp[0] = (uint64_t*)take(b_comp); s.comp[1] = (uint64_t*)take(b_comp);
-    s.hist = (uint32_t*)take(b_hist); s.cnt_c = (uint32_t*)take(b_cnt); s.cnt_p = (uint32_t*)take(b_cnt);
-    s.queue = take(b_queue); s.scell = nullptr;
-    BCHK(pool_alloc(&s.base_val, 2 * b_comp));
-    s.val[0] = static_cast<double*>(s.base_val); s.val[1] = reinterpret_cast<double*>(static_cast<char*>(s.base_val) + b_comp);
+    BCHK(scratch_alloc(s, SCRATCH_DERIVED));
+    BCHK(scratch_alloc_values(s));
     s.kmin = kmin; s.pmin = pmin; s.kbits = kbits; s.pbits = pbits; s.ibits = 0;
     return hipSuccess;
 }
 hipError_t build_derived_sort(BuildScratch& s, int64_t counts[2], hipStream_t stream, const std::function<void()>* while_sorting) {
-    const int64_t n = s.n;
-    const int64_t nblocks = (n + RS_TILE - 1) / RS_TILE;
-    BuildCtl* dctl = static_cast<BuildCtl*>(s.d_ctl);
-    BuildCtl* hctl = static_cast<BuildCtl*>(s.h_ctl);
-    static PerDeviceOnce once;
-    const size_t lds_bytes = (size_t)RS_TILE * (sizeof(uint64_t) + sizeof(double));
-    BCHK(once.run([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); }));
-    const int npass = (s.pbits + 7) / 8;
-    const dim3 grid((unsigned)nblocks), block(RS_BLOCK);
-    int cur = 0;
-    for (int pass = 0; pass < npass; ++pass) {
-        const int shift = s.kbits + 8 * pass;
-        uint32_t* dtot = s.ghist + pass * RS_BINS;
-        hipLaunchKernelGGL(k_rs_hist, grid, block, 0, stream, (const uint64_t*)s.comp[cur], n, shift, s.hist, nblocks);
-        hipLaunchKernelGGL(k_rs_scan, dim3(RS_BINS), block, 0, stream, s.hist, dtot, nblocks);
-        hipLaunchKernelGGL(k_rs_scatter<true>, grid, block, lds_bytes, stream, (const uint64_t*)s.comp[cur], (const double*)s.val[cur], n, shift, (const uint32_t*)s.hist,
-                           (const uint32_t*)dtot, s.comp[1 - cur], s.val[1 - cur], nblocks);
-        cur = 1 - cur;
-    }
-    s.sorted = cur;
-    s.vsorted = s.val[cur];
-    hipLaunchKernelGGL(k_bf_count, grid, block, 0, stream, (const uint64_t*)s.comp[cur], n, s.kbits, 0, 1, s.cnt_c, s.cnt_p);
-    const unsigned long long seq = ++g_count_seq;
-    hctl->zeros = 0;
-    hipLaunchKernelGGL(k_bf_scan, dim3(1), dim3(1024), 0, stream, s.cnt_c, s.cnt_p, nblocks, dctl, reinterpret_cast<unsigned long long*>(hctl), seq);
-    if (while_sorting && *while_sorting) {
-        try { (*while_sorting)(); } catch (...) { (void)hipStreamSynchronize(stream); throw; }
-    }
-    BCHK(wait_pinned_seq(&hctl->zeros, seq, stream));       // k_bf_scan's hand-over (the word it writes last)
-    counts[0] = (int64_t)hctl->ncells; counts[1] = (int64_t)hctl->nparts;
-    return hipGetLastError();
+    RadixRun r{s.n, s.kbits, s.pbits, s.comp, s.val, s.hist, s.ghist};
+    BCHK(radix_run(r, stream));
+    s.sorted = r.cur;
+    s.vsorted = r.pay_sorted;
+    return count_tail(s, true, counts, while_sorting);
 }
 
-static hipError_t emit_wide(const double* d_val, int32_t combine, BuildScratch& s, KeyArr out_keys, double* out_vals, int64_t* part_keys, int mode,
-                            int64_t nparts_explicit, hipStream_t stream, bool wait_and_free);
-
-hipError_t build_emit(const double* d_val, int32_t combine, BuildScratch& s, KeyArr out_keys, double* out_vals,
-                      int64_t* part_keys, int mode, int64_t nparts_explicit, hipStream_t stream, bool wait_and_free,
-                      uint64_t* der_comp, double* der_val) {
-    if (s.wide_path) return emit_wide(d_val, combine, s, out_keys, out_vals, part_keys, mode, nparts_explicit, stream, wait_and_free);
+static hipError_t composite_emit(const double* d_val, int32_t combine, BuildScratch& s, KeyArr out_keys, double* out_vals,
+                                 int64_t* part_keys, int mode, int64_t nparts_explicit, hipStream_t stream, bool wait_and_free,
+                                 uint64_t* der_comp, double* der_val) {
     const int64_t nblocks = (s.n + RS_TILE - 1) / RS_TILE;
     BuildCtl* dctl = static_cast<BuildCtl*>(s.d_ctl);
     const uint64_t* comp = s.comp[s.sorted];
@@ -895,79 +882,36 @@ hipError_t build_emit(const double* d_val, int32_t combine, BuildScratch& s, Key
     if (mode == 2 && nparts_explicit > 0)
         hipLaunchKernelGGL(k_emit_sems, dim3((unsigned)((nparts_explicit + 255) / 256)), dim3(256), 0, stream, comp, s.kbits, s.ibits, s.pmin,
                            (const uint32_t*)s.scell, s.n, nparts_explicit, out_keys, out_vals);
-    hipError_t e = hipGetLastError();
-    if (!wait_and_free) return e;            // the caller enqueues more behind the emit and calls build_abort(s) after its own stream wait
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    free_scratch(s);
-    return e;
+    return emit_tail(s, stream, wait_and_free);
 }
 
-void build_abort(BuildScratch& s) {
-    if (s.stream) (void)hipStreamSynchronize(s.stream);
-    free_scratch(s);
-}
-
-// ---- general path, host side ----
-// one stable LSD sort of (comp, payload) over `bits` bits with the kernels of the composite path; returns the buffer index of the result
-static_assert(PAIR_SORT_TILE == RS_TILE, "pair_sort_bytes sizes the histogram by the tile of the radix pass");
-static hipError_t wide_sort(const PairSort& w, int64_t n, int& cur, int bits, int64_t nblocks, hipStream_t stream) {
-    const size_t lds_bytes = (size_t)RS_TILE * (sizeof(uint64_t) + sizeof(double));
-    const dim3 grid((unsigned)nblocks), block(RS_BLOCK);
-    const int npass = (bits + 7) / 8;
-    for (int pass = 0; pass < npass; ++pass) {
-        const int shift = 8 * pass;
-        uint32_t* dtot = w.ghist + pass * RS_BINS;
-        hipLaunchKernelGGL(k_rs_hist, grid, block, 0, stream, (const uint64_t*)w.comp[cur], n, shift, w.hist, nblocks);
-        hipLaunchKernelGGL(k_rs_scan, dim3(RS_BINS), block, 0, stream, w.hist, dtot, nblocks);
-        hipLaunchKernelGGL(k_rs_scatter<true>, grid, block, lds_bytes, stream, (const uint64_t*)w.comp[cur], (const double*)w.pay[cur], n, shift,
-                           (const uint32_t*)w.hist, (const uint32_t*)dtot, w.comp[1 - cur], w.pay[1 - cur], nblocks);
-        cur = 1 - cur;
-    }
-    return hipGetLastError();
-}
-
+// ---- the general path -------------------------------------------------------------------------------------------------------
 // the two runs and the gather behind them (pairsort.h): what the general path of the builder and the batched insert share
 hipError_t launch_pair_sort(const int64_t* d_part, const int64_t* d_key, int64_t n, int64_t pmin, int pbits, int64_t kmin, int kbits,
                             const PairSort& w, uint32_t* idx, int64_t* k2, int64_t* p2, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     if (n < 0 || n > (int64_t)UINT32_MAX || kbits < 0 || kbits > 64 || pbits < 0 || pbits > 64) return hipErrorInvalidValue;
-    const int64_t nblocks = (n + RS_TILE - 1) / RS_TILE;
-    static PerDeviceOnce once;
-    const size_t lds_bytes = (size_t)RS_TILE * (sizeof(uint64_t) + sizeof(double));
-    hipError_t e = once.run([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(k_rs_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); });
-    if (e != hipSuccess) return e;
     const unsigned gs = (unsigned)std::min<int64_t>((n + 255) / 256, 65535 * 4);
-    int cur = 0;
+    RadixRun r{n, 0, kbits, w.comp, w.pay, w.hist, w.ghist};
     hipLaunchKernelGGL(k_wide_key0, dim3(gs), dim3(256), 0, stream, d_key, kmin, w.comp[0], w.pay[0], n);
-    e = wide_sort(w, n, cur, kbits, nblocks, stream);                                                       // by key
+    hipError_t e = radix_run(r, stream);                                                                    // by key
     if (e != hipSuccess) return e;
     if (d_part != nullptr) {
-        hipLaunchKernelGGL(k_wide_part, dim3(gs), dim3(256), 0, stream, d_part, pmin, (const double*)w.pay[cur], w.comp[cur], n);
-        e = wide_sort(w, n, cur, std::max(pbits, 1), nblocks, stream);                                      // then by partition (stable)
+        hipLaunchKernelGGL(k_wide_part, dim3(gs), dim3(256), 0, stream, d_part, pmin, (const double*)w.pay[r.cur], w.comp[r.cur], n);
+        r.bits = std::max(pbits, 1);
+        e = radix_run(r, stream);                                                                           // then by partition (stable)
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_wide_finish, dim3(gs), dim3(256), 0, stream, d_part, d_key, (const double*)w.pay[cur], idx, k2, p2, n);
+    hipLaunchKernelGGL(k_wide_finish, dim3(gs), dim3(256), 0, stream, d_part, d_key, (const double*)w.pay[r.cur], idx, k2, p2, n);
     return hipGetLastError();
 }
 
+// The counts of the general path keep their own hand-over — k_bf_scan without a host pointer, a copy command and a stream wait, no
+// while_sorting — instead of count_tail's: taking the pinned hand-over here would change what this path enqueues.
 static hipError_t prepare_wide(const int64_t* d_part, const int64_t* d_key, int64_t nnz, BuildScratch& s, int64_t counts[2], hipStream_t stream,
                                int64_t kmin, int kbits, int64_t pmin, int pbits) {
-    const size_t n = (size_t)nnz;
     const int64_t nblocks = (nnz + RS_TILE - 1) / RS_TILE;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    BCHK(pinned_ctl_get(&s.h_ctl));
-    {
-        const size_t a4 = up(n * 4), a8 = up(n * 8), b_ctl = up(sizeof(BuildCtl)), b_gh = up(8 * RS_BINS * 4 + 64),
-                     b_hist = up((size_t)RS_BINS * nblocks * 4), b_cnt = up((size_t)(nblocks + 1) * 4);
-        BCHK(pool_alloc(&s.base, b_ctl + b_gh + 6 * a8 + 5 * a4 + b_hist + 2 * b_cnt));
-        char* q = static_cast<char*>(s.base);
-        auto take = [&q](size_t b) { char* r = q; q += b; return r; };
-        s.d_ctl = take(b_ctl); s.ghist = (uint32_t*)take(b_gh);
-        s.comp[0] = (uint64_t*)take(a8); s.comp[1] = (uint64_t*)take(a8); s.val[0] = (double*)take(a8); s.val[1] = (double*)take(a8);
-        s.k2 = (int64_t*)take(a8); s.p2 = (int64_t*)take(a8);
-        s.idx2 = (uint32_t*)take(a4); s.fpart = (uint32_t*)take(a4); s.fcell = (uint32_t*)take(a4); s.spart = (uint32_t*)take(a4); s.scell = (uint32_t*)take(a4);
-        s.hist = (uint32_t*)take(b_hist); s.cnt_c = (uint32_t*)take(b_cnt); s.cnt_p = (uint32_t*)take(b_cnt);
-    }
+    BCHK(scratch_alloc(s, SCRATCH_WIDE));
     BuildCtl* dctl = static_cast<BuildCtl*>(s.d_ctl);
     BuildCtl* hctl = static_cast<BuildCtl*>(s.h_ctl);
     const PairSort w{{s.comp[0], s.comp[1]}, {s.val[0], s.val[1]}, s.hist, s.ghist};
@@ -992,11 +936,48 @@ static hipError_t emit_wide(const double* d_val, int32_t combine, BuildScratch& 
     if (mode == 2 && nparts_explicit > 0)
         hipLaunchKernelGGL(k_emit_sems_wide, dim3((unsigned)((nparts_explicit + 255) / 256)), dim3(256), 0, stream, s.p2, s.scell, s.n,
                            nparts_explicit, out_keys, out_vals);
-    hipError_t e = hipGetLastError();
-    if (!wait_and_free) return e;            // (enqueue only, like the composite path: the caller waits and calls build_abort)
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    return emit_tail(s, stream, wait_and_free);
+}
+
+// ---- entry points: the path is chosen by the width of the composite ---------------------------------------------------------
+// Phase 1: sort + flags + counts.  d_part / d_key / d_val: the nnz input triples in HBM (d_part == nullptr: a plain vector).
+// Returns the number of distinct cells and of partitions through counts[0..1] (host).  The scratch stays alive for phase 2
+// (build_emit), which writes counts[0] + #partitions stream cells.
+hipError_t build_prepare(const int64_t* d_part, const int64_t* d_key, const double* d_val, int64_t nnz, KeyRange part_range, KeyRange key_range,
+                         BuildScratch& s, int64_t counts[2], hipStream_t stream, const std::function<void()>* while_sorting) {
+    s = BuildScratch();
+    s.n = nnz; s.stream = stream;
+    static const bool force_wide = [] { const char* e = dev_env("DSA_BUILD_WIDE"); return e && e[0] == '1'; }();
+    BCHK(scratch_alloc(s, SCRATCH_COMPOSITE));
+    // ---- key ranges: how many bits the composite needs
+    if (!key_range.known() || (d_part != nullptr && !part_range.known())) {
+        const BuildCtl* hctl = static_cast<BuildCtl*>(s.h_ctl);
+        BCHK(minmax_pass(d_part, d_key, nnz, static_cast<BuildCtl*>(s.d_ctl), reinterpret_cast<long long*>(s.ghist + 8 * RS_BINS), static_cast<BuildCtl*>(s.h_ctl), stream));
+        key_range.lo = hctl->kmin; key_range.hi = hctl->kmax;
+        if (d_part) { part_range.lo = hctl->pmin; part_range.hi = hctl->pmax; }
+    }
+    const int64_t kmin = key_range.lo, pmin = d_part ? part_range.lo : 0;
+    const int kbits = std::max(1, bit_width_u64((uint64_t)key_range.hi - (uint64_t)key_range.lo));
+    const int pbits = d_part ? bit_width_u64((uint64_t)part_range.hi - (uint64_t)part_range.lo) : 0;
+    if (kbits + pbits > 64 || force_wide) {
+        free_scratch(s);
+        s.n = nnz; s.stream = stream; s.wide_path = true;
+        return prepare_wide(d_part, d_key, nnz, s, counts, stream, kmin, kbits, pmin, pbits);
+    }
+    s.kmin = kmin; s.pmin = pmin; s.kbits = kbits; s.pbits = pbits;
+    return composite_sort(d_part, d_key, d_val, s, counts, while_sorting);
+}
+
+hipError_t build_emit(const double* d_val, int32_t combine, BuildScratch& s, KeyArr out_keys, double* out_vals,
+                      int64_t* part_keys, int mode, int64_t nparts_explicit, hipStream_t stream, bool wait_and_free,
+                      uint64_t* der_comp, double* der_val) {
+    if (s.wide_path) return emit_wide(d_val, combine, s, out_keys, out_vals, part_keys, mode, nparts_explicit, stream, wait_and_free);
+    return composite_emit(d_val, combine, s, out_keys, out_vals, part_keys, mode, nparts_explicit, stream, wait_and_free, der_comp, der_val);
+}
+
+void build_abort(BuildScratch& s) {
+    if (s.stream) (void)hipStreamSynchronize(s.stream);
     free_scratch(s);
-    return e;
 }
 
 }  // namespace dsa

@@ -14,6 +14,6 @@ from .api import (  # noqa: F401
     addrow, closefillmode, deletecolumn, deletecolumns, deletepartition, deleterow, deleterows, droptol, dropzeros, dynamicsparse,
     dynamicsparse_compressed_dev, dynamicsparse_dev, from_torch, hcat, vcat, blockdiag,
     dynamicsparsevec, import_packedcsc_layout, import_vector_layout, nbpartitions, nnz, packedcsc, packedcsc_empty, pool_idle_bytes,
-    pool_trim, shrink_size, dev_switches, insert_values, upsert,
+    pool_trim, shrink_size, dev_switches, insert_values, upsert, assemble,
 )
 from .binding import Binding, DsaArgumentError, DsaBoundsError, DsaError, DsaErrorException, product  # noqa: F401

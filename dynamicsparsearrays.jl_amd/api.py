@@ -415,6 +415,10 @@ class Transposed:
     def upsert(self, I, J, V):
         return self.array.upsert(J, I, V)
 
+    def assemble(self, I, J, V, op="add"):
+        """transpose(mat)[I[k], J[k]] += V[k] (or = V[k]) for any triples: assemble of the matrix with the sides swapped"""
+        return self.array.assemble(J, I, V, op=op)
+
 
 class DynamicSparseMatrix(_Handle):
     """DynamicSparseMatrix{Int64,Int64,Float64}  (src/matrix.jl:1-8)."""
@@ -1327,6 +1331,40 @@ class DynamicSparseMatrix(_Handle):
             self.insert_values(i[miss], j[miss], v[miss])
         return updated, int(miss.sum())
 
+    # ---- the general write from triples, in place (include/dsa.h: dsa_mat_assemble[_dev]; HIP library only) -------------------------
+    _ASSEMBLE_NEEDS = "assemble needs the HIP product library"
+
+    def assemble(self, I, J, V, op="add"):
+        """A[I[k], J[k]] += V[k] (op "add") or = V[k] ("set") for ANY triples — cells stored or not, repeated or not, in any order —
+        in place on the device.  The ops are folded to distinct cells first: "add" sums a cell's values one after the other in the
+        order of the batch (the left fold of dynamicsparse over duplicates), "set" keeps the last, bit for bit.  Stored cells are
+        then written as by update_values ("add": stored + sum), the others created as by insert_values, with its layout and its
+        limit: a new column / row must lie behind the last live entry of its table, else DsaErrorException with code EMODE (use
+        set_batch).  A zero, or a sum that cancels, is a stored zero (dropzeros() removes it).  "add" is A + sparse(I, J, V) in
+        place.  I, J, V: sequences or numpy arrays, or tensors on the GPU (int64, int64, float64; all three of the same kind), which
+        are used where they are.  An error and an empty batch change nothing and keep the cached SpMV plans.  Returns (distinct,
+        updated, inserted): the distinct cells, those written in place, those created."""
+        self._require("mat_assemble", self._ASSEMBLE_NEEDS)
+        opc = self._update_op(op)
+        dev, (i, j, v, n, _), _mask, _keep = _triple(I, J, V, False)
+        if dev:
+            out = self.assemble_dev(i, j, v, n, opc)
+            self.sync()
+            return out
+        d, u, ins = C.c_int64(), C.c_int64(), C.c_int64()
+        self.b.call("mat_assemble", self.h, opc, i, j, v, n, C.byref(d), C.byref(u), C.byref(ins))
+        return d.value, u.value, ins.value
+
+    def assemble_dev(self, d_I, d_J, d_V, n, op=UPD_ADD):
+        """assemble with the triples in HBM (device addresses of n int64, int64, float64 entries, complete at the call and unchanged
+        until it returns); op UPD_SET | UPD_ADD.  When only stored cells are written the stores may still be enqueued (sync());
+        when cells are created the call returns with both streams drained.  Returns (distinct, updated, inserted)."""
+        self._require("mat_assemble", self._ASSEMBLE_NEEDS)
+        d, u, ins = C.c_int64(), C.c_int64(), C.c_int64()
+        self.b.call("mat_assemble_dev", self.h, int(op), _dptr(d_I), _dptr(d_J), _dptr(d_V), int(n),
+                    C.byref(d), C.byref(u), C.byref(ins))
+        return d.value, u.value, ins.value
+
 
 def dynamicsparse(I=None, J=None, V=None, m=None, n=None, fill_mode=True,
                   binding: Binding | None = None) -> DynamicSparseMatrix:
@@ -1479,6 +1517,11 @@ def insert_values(mat, I, J, V, existing="error"):
 
 def upsert(mat, I, J, V):
     return mat.upsert(I, J, V)
+
+
+def assemble(mat, I, J, V, op="add"):
+    """assemble!(A, I, J, V; op): any triples folded, stored cells written, the others created (DynamicSparseMatrix.assemble)"""
+    return mat.assemble(I, J, V, op=op)
 
 
 def droptol(mat, tol, rows=None, cols=None):

@@ -179,6 +179,8 @@ _PRODUCT_ONLY_SIGS = {
     "mat_get_batch_dev": [VP, VP, VP, I64, VP, VP],
     "mat_insert_batch_dev": [VP, VP, VP, VP, I64, I32, VP],
     "mat_insert_batch": [VP, P_I64, P_I64, P_F64, I64, I32, P_U8],
+    "mat_assemble_dev": [VP, I32, VP, VP, VP, I64, P_I64, P_I64, P_I64],
+    "mat_assemble": [VP, I32, P_I64, P_I64, P_F64, I64, P_I64, P_I64, P_I64],
     "mat_select_compressed_dev": [VP, I32, I32, I32, VP, I64, VP, VP, VP, I64, P_I64],
     "mat_select_compressed": [VP, I32, I32, P_I64, I64, P_I64, P_I64, P_F64, I64, P_I64],
     "mat_submatrix_compressed_dev": [VP, I32, I32, I32, VP, I64, VP, I64, VP, VP, VP, I64, P_I64],

@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, fill_host.hip, matwrite_host.hip, pma_host.hip,
-// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, mutate_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, insert_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
+// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, mutate_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, insert_host.hip, assemble_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // seq_dev.h, export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -20,8 +20,12 @@
 namespace dsa {
 namespace host {
 
-struct Fail { int32_t code; std::string msg; };
+struct Fail { int32_t code; std::string msg; long long op = -1; };
 [[noreturn]] inline void fail(int32_t code, const std::string& msg) { throw Fail{code, msg}; }
+// a failure whose message names op `op` of the batch the callee was given, as op_text(op): a caller that handed on a batch it derived
+// (assemble_host.hip) puts the op of ITS caller's batch in its place
+inline std::string op_text(unsigned long long k) { return "op " + std::to_string(k) + " (0-based)"; }
+[[noreturn]] inline void fail_op(int32_t code, unsigned long long op, const std::string& msg) { throw Fail{code, msg, (long long)op}; }
 
 #define HIPCHK(expr)                                                                               \
     do {                                                                                           \
@@ -188,6 +192,11 @@ struct Pma {
     // insert_batch (insert.hip): the sorted ops, their predecessor slots, item counts and prefixes, the tile counts of the array; the
     // pinned words of the orientation's hand-over
     ExportArea ins;
+    // assemble (assemble.hip; colmajor only): the sort, the flag words and tile counts, the long-run queue, the folded and the compacted
+    // triples, update's miss mask; the pinned {distinct cells, sequence number}; the event that lets the rowmajor stream go on behind
+    // the fold and the compaction
+    ExportArea asmb;
+    hipEvent_t ev_asm = nullptr;
     // combine (combine.hip): the tile arrays, range words and last-semaphore ids of a pass over this orientation; the pinned words of
     // the two roles an operand can have (2 x {error word, four range words, sequence number})
     ExportArea cmb;
@@ -430,6 +439,20 @@ struct InsertCounts { int64_t ops = 0, existing = 0, items[2] = {0, 0}, parts[2]
 InsertCounts insert_prepare(dsa_mat* h, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int32_t flags, uint8_t* d_existing);
 void insert_apply(dsa_mat* h, const InsertCounts& c, const double* d_V, int64_t n);
 void insert_check_args(dsa_mat* h, const void* I, const void* J, const void* V, int64_t n, int32_t flags);
+
+// ---- assemble_host.hip: ANY triples in HBM (stored or not, repeated or not) folded to distinct cells on the device, the stored ones
+// written by the update, the others created by the insert.  Two steps so that the entry point can bump the content epoch between
+// them: assemble_prepare (flush, checks, key scan, sort + fold, update_prepare on the folded cells, then compaction + insert_prepare
+// on its misses: every error with nothing modified) and assemble_apply (update_apply, then insert_apply when cells are created).
+struct AssembleCounts {
+    int64_t distinct = 0, updated = 0, missing = 0;
+    InsertCounts ins;
+    KeyRange rows, cols;                                                      // of every op: size(m) covers them afterwards, as after setindex!
+    const double* folded_V = nullptr; const double* missing_V = nullptr;      // in the scratch: what the two applies store
+};
+AssembleCounts assemble_prepare(dsa_mat* h, int32_t op, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n);
+void assemble_apply(dsa_mat* h, int32_t op, const AssembleCounts& c);
+void assemble_check_args(dsa_mat* h, int32_t op, const void* I, const void* J, const void* V, int64_t n);
 
 // Buffer  src/buffer.jl:1-4 — the fill-mode write buffer, DEVICE-RESIDENT: appended triples are staged in two pinned host chunks
 // and uploaded asynchronously as a chunk fills (the copy of chunk k overlaps the caller's appends into chunk k+1), so that

@@ -13,12 +13,6 @@
 namespace dsa {
 namespace host {
 
-namespace {
-
-std::string op_text(unsigned long long k) { return "op " + std::to_string(k) + " (0-based)"; }
-
-}  // namespace
-
 // what both forms check before anything is staged or launched (I, J, V: host or device addresses)
 void insert_check_args(dsa_mat* h, const void* I, const void* J, const void* V, int64_t n, int32_t flags) {
     if (h->fillmode || !h->has_major) fail(DSA_EMODE, "Cannot insert cells in fill mode");
@@ -111,18 +105,19 @@ InsertCounts insert_prepare(dsa_mat* h, const int64_t* d_I, const int64_t* d_J, 
     const unsigned long long* pr = R.ins.pin;
     const unsigned long long ec = __atomic_load_n(pc, __ATOMIC_ACQUIRE), er = __atomic_load_n(pr, __ATOMIC_ACQUIRE);
     const bool strict = (flags & DSA_INS_SKIP_EXISTING) == 0;
+    const auto first = [&](unsigned bit, int word) { return (ec & bit) ? pc[word] : pr[word]; };      // the op an error bit names
     if ((ec | er) & INS_E_BROKEN)
-        fail(DSA_EASSERT, "insert_batch: the partition of " + op_text((ec & INS_E_BROKEN) ? pc[4] : pr[4]) + " has no semaphore, or its slots are out of step with the tables");
+        fail_op(DSA_EASSERT, first(INS_E_BROKEN, 4), "insert_batch: the partition of " + op_text(first(INS_E_BROKEN, 4)) + " has no semaphore, or its slots are out of step with the tables");
     if ((ec | er) & INS_E_DUP)
-        fail(DSA_EARG, "insert_batch: " + op_text((ec & INS_E_DUP) ? pc[1] : pr[1]) + " addresses a cell that an earlier op of the batch creates");
+        fail_op(DSA_EARG, first(INS_E_DUP, 1), "insert_batch: " + op_text(first(INS_E_DUP, 1)) + " addresses a cell that an earlier op of the batch creates");
     if (pc[5] != pr[5])
         fail(DSA_EASSERT, "insert_batch: the two orientations disagree about the ops that are already stored (" + std::to_string(pc[5]) + " / " +
                               std::to_string(pr[5]) + ")");
     if (strict && ((ec | er) & INS_E_EXISTS))
-        fail(DSA_EARG, "insert_batch: " + op_text((ec & INS_E_EXISTS) ? pc[2] : pr[2]) + " addresses a cell that is already stored");
+        fail_op(DSA_EARG, first(INS_E_EXISTS, 2), "insert_batch: " + op_text(first(INS_E_EXISTS, 2)) + " addresses a cell that is already stored");
     if ((ec | er) & INS_E_MIDDLE) {
         const bool col = (ec & INS_E_MIDDLE) != 0;
-        fail(DSA_EMODE, std::string("insert_batch: ") + op_text(col ? pc[3] : pr[3]) + " creates a " + (col ? "column" : "row") +
+        fail_op(DSA_EMODE, col ? pc[3] : pr[3], std::string("insert_batch: ") + op_text(col ? pc[3] : pr[3]) + " creates a " + (col ? "column" : "row") +
                             " that is not behind the last entry of its table (or that entry is deleted): use set_batch");
     }
     if ((int64_t)pc[8] != C.h_ctl->nb_elements || (int64_t)pr[8] != R.h_ctl->nb_elements)

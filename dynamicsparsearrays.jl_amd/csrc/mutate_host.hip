@@ -1,7 +1,7 @@
 // csrc/mutate_host.hip — the entry points that change a matrix in place from whole operand arrays: scale, the batched delete, droptol,
-// update_values and insert_batch, each with operands in HBM (dsa_mat_X_dev) or in host memory (dsa_mat_X).  Every one is the same
+// update_values, insert_batch and assemble, each with operands in HBM (dsa_mat_X_dev) or in host memory (dsa_mat_X).  Every one is the same
 // protocol around the two steps of its engine unit (scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip,
-// insert_host.hip): X_prepare — flush, checks and the passes that decide what changes, every error and every call that changes
+// insert_host.hip, assemble_host.hip): X_prepare — flush, checks and the passes that decide what changes, every error and every call that changes
 // nothing with layouts and cached SpMV plans as they were — then mat_commit around X_apply.  One body per mutator (mat_X) serves both
 // forms; the host form is stage, mat_X, copy back, sync.
 #include "host.h"
@@ -84,6 +84,17 @@ void mat_update_values(dsa_mat* h, int32_t op, int32_t flags, const int64_t* d_I
 void mat_insert_batch(dsa_mat* h, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int32_t flags, uint8_t* d_existing) {
     const InsertCounts c = insert_prepare(h, d_I, d_J, d_V, n, flags, d_existing);
     if (c.ops > 0) mat_commit(h, true, [&] { insert_apply(h, c, d_V, n); });
+}
+
+// ---- the general write (assemble.hip): any triples folded to distinct cells, the stored ones updated, the others inserted, under one
+// commit.  The SpMV meta is prefetched only when a cell is created: a call that only updates moves no cell
+void mat_assemble(dsa_mat* h, int32_t op, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n, int64_t* distinct_out,
+                  int64_t* updated_out, int64_t* inserted_out) {
+    const AssembleCounts c = assemble_prepare(h, op, d_I, d_J, d_V, n);
+    if (c.updated > 0 || c.missing > 0) mat_commit(h, c.missing > 0, [&] { assemble_apply(h, op, c); });
+    if (distinct_out) *distinct_out = c.distinct;
+    if (updated_out) *updated_out = c.updated;
+    if (inserted_out) *inserted_out = c.missing;
 }
 
 }  // namespace
@@ -183,6 +194,28 @@ int32_t dsa_mat_insert_batch(dsa_mat_t* h, const int64_t* I, const int64_t* J, c
         stage_triples(st, I, J, V, n, existing != nullptr);
         mat_insert_batch(h, st.at<int64_t>(0), st.at<int64_t>(1), st.at<double>(2), n, flags, st.at<uint8_t>(3));
         if (existing) st.down(existing, st.p[3], (size_t)n);
+        st.sync_both();
+    }
+    API_CATCH
+}
+
+int32_t dsa_mat_assemble_dev(dsa_mat_t* h, int32_t op, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n,
+                             int64_t* distinct_out, int64_t* updated_out, int64_t* inserted_out) {
+    API_TRY
+    for (int64_t* out : {distinct_out, updated_out, inserted_out}) if (out) *out = 0;
+    mat_assemble(h, op, d_I, d_J, d_V, n, distinct_out, updated_out, inserted_out);
+    API_CATCH
+}
+int32_t dsa_mat_assemble(dsa_mat_t* h, int32_t op, const int64_t* I, const int64_t* J, const double* V, int64_t n, int64_t* distinct_out,
+                         int64_t* updated_out, int64_t* inserted_out) {
+    API_TRY
+    for (int64_t* out : {distinct_out, updated_out, inserted_out}) if (out) *out = 0;
+    mat_flush(h);
+    assemble_check_args(h, op, I, J, V, n);
+    MatStaging st(h);
+    if (n > 0) {
+        stage_triples(st, I, J, V, n, false);
+        mat_assemble(h, op, st.at<int64_t>(0), st.at<int64_t>(1), st.at<double>(2), n, distinct_out, updated_out, inserted_out);
         st.sync_both();
     }
     API_CATCH

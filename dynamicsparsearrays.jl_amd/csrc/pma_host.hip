@@ -73,6 +73,8 @@ void pma_destroy(Pma& P) {
     P.drp.release();
     P.upd.release();
     P.ins.release();
+    P.asmb.release();
+    if (P.ev_asm) (void)hipEventDestroy(P.ev_asm);
     if (P.ev_upd) (void)hipEventDestroy(P.ev_upd);
     P.cmb.release();
     P.spg.release();

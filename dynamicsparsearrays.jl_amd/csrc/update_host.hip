@@ -19,8 +19,6 @@ void stream_after(Pma& rec, hipStream_t from, hipStream_t to) {
     HIPCHK(hipStreamWaitEvent(to, rec.ev_upd, 0));
 }
 
-std::string op_text(unsigned long long k) { return "op " + std::to_string(k) + " (0-based)"; }
-
 }  // namespace
 
 // what both forms check before anything is staged or launched (I, J, V: host or device addresses)
@@ -55,11 +53,11 @@ UpdateCounts update_prepare(dsa_mat* h, int32_t op, int32_t flags, const int64_t
     wait_handover(C, C.upd.pin + UPD_PIN_WORDS - 1, seq, "update (resolve)");
     const unsigned long long* pin = C.upd.pin;
     const unsigned long long err = __atomic_load_n(pin, __ATOMIC_ACQUIRE);
-    if (err & UPD_E_ZERO) fail(DSA_EKEY, "update_values: " + op_text(pin[1]) + " has the key 0, the reserved semaphore key (src/pcsr.jl:23)");
+    if (err & UPD_E_ZERO) fail_op(DSA_EKEY, pin[1], "update_values: " + op_text(pin[1]) + " has the key 0, the reserved semaphore key (src/pcsr.jl:23)");
     if (err & UPD_E_BROKEN)
-        fail(DSA_EASSERT, "update_values: the two orientations disagree about " + op_text(pin[2]) + ", or its partition has no semaphore");
-    if (err & UPD_E_MISS) fail(DSA_EARG, "update_values: " + op_text(pin[3]) + " addresses a cell that is not stored");
-    if (err & UPD_E_DUP) fail(DSA_EARG, "update_values: " + op_text(pin[4]) + " adds to a cell that a later op addresses again");
+        fail_op(DSA_EASSERT, pin[2], "update_values: the two orientations disagree about " + op_text(pin[2]) + ", or its partition has no semaphore");
+    if (err & UPD_E_MISS) fail_op(DSA_EARG, pin[3], "update_values: " + op_text(pin[3]) + " addresses a cell that is not stored");
+    if (err & UPD_E_DUP) fail_op(DSA_EARG, pin[4], "update_values: " + op_text(pin[4]) + " adds to a cell that a later op addresses again");
     return UpdateCounts{(int64_t)pin[6], (int64_t)pin[5]};
 }
 

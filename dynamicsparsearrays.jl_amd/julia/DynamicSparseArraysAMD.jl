@@ -26,7 +26,7 @@ export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
        keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev,
        scale!, reduce_rows, reduce_cols, mul_rows, mul_cols, mul_sparse, dropzeros!, droptol!, count_droptol,
-       update_values!, add_values!, getstored, insert_values!, upsert!
+       update_values!, add_values!, getstored, insert_values!, upsert!, assemble!
 
 const libdsa = get(ENV, "DSA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libdsa_hip.so"))
 
@@ -775,6 +775,22 @@ function upsert!(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector, V
     updated, miss = update_values!(a, I, J, V; skip_missing = true)
     any(miss) && insert_values!(a, I[miss], J[miss], V[miss])
     return updated, count(miss)
+end
+# The general write from triples (include/dsa.h: dsa_mat_assemble): ANY triples — cells stored or not, repeated or not, in any order —
+# folded to distinct cells on the device (op = +: the values of a cell summed one after the other in the order of the batch, the
+# left fold of dynamicsparse over duplicates; op = :set: the last value, bit for bit), the stored cells written in place as by
+# update_values! / add_values!, the others created as by insert_values!, with its layout and its limit on new columns / rows.
+# op = + is A + sparse(I, J, V) in place.  Any other op is an ArgumentError.  Returns (distinct cells, cells updated, cells inserted).
+function assemble!(a::DynamicSparseMatrix, I::AbstractVector, J::AbstractVector, V::AbstractVector; op = +)
+    opc = op === (+) ? Int32(1) : op === :set ? Int32(0) :      # DSA_UPD_ADD, DSA_UPD_SET
+          throw(ArgumentError("assemble!: op must be + or :set"))
+    Ii = _in(a.rows, I); Ji = _in(a.cols, J); Vf = Vector{Float64}(V)
+    length(Ii) == length(Ji) == length(Vf) || throw(ArgumentError("rows, columns, and nonzeros do not have same length."))
+    distinct = Ref{Int64}(0); updated = Ref{Int64}(0); inserted = Ref{Int64}(0)
+    GC.@preserve Ii Ji Vf _check(ccall((:dsa_mat_assemble, libdsa), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+        a.h, opc, Ii, Ji, Vf, length(Ii), distinct, updated, inserted))
+    return distinct[], updated[], inserted[]
 end
 "n getindex calls with every operand in HBM (device pointers; mapped key integers): d_out[k] = A[d_I[k], d_J[k]], d_found[k] (n bytes, or
 C_NULL) = 1 iff the cell is stored, which tells a stored zero from an absent cell; enqueued on the colmajor stream, no host wait —

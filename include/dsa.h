@@ -502,7 +502,7 @@ int32_t dsa_mat_droptol(dsa_mat_t* h, double tol, const double* rtol, int64_t nr
  * SET stores V[k] bit for bit (NaN payloads and -0.0 are kept).  V[k] == 0.0 leaves a STORED zero, as dsa_mat_scale does — NOT the
  * reference's delete-on-zero: nnz is unchanged and the cell is still exported; dsa_mat_droptol removes such cells.  A cell addressed
  * by several ops of a SET ends with the value of the LAST of them (the largest k), which is what the ops one after the other leave.
- * ADD must address a stored cell at most once: a second op on it is DSA_EARG (an ordered sum of duplicates is not offered).
+ * ADD must address a stored cell at most once: a second op on it is DSA_EARG (the ordered sum of duplicates is dsa_mat_assemble's).
  * Both orientations end with identical bits in every cell, and the same call on the same state gives the same bits.  Only values
  * are written: keys, occupancy, tables, counts, capacity and the rebalance / extend statistics stay as they are.  Cached SpMV plans
  * are dropped iff at least one value is written.
@@ -563,6 +563,40 @@ int32_t dsa_mat_insert_batch_dev(dsa_mat_t* h, const int64_t* d_I, const int64_t
                                  uint8_t* d_existing);
 int32_t dsa_mat_insert_batch(dsa_mat_t* h, const int64_t* I, const int64_t* J, const double* V, int64_t n, int32_t flags,
                              uint8_t* existing);
+/* The general write from triples (csrc/assemble.hip): ANY n triples — cells stored or not, repeated or not, in any order — in three
+ * steps that never leave HBM.  op is DSA_UPD_SET or DSA_UPD_ADD.
+ * 1. FOLD to the distinct cells (I[k], J[k]).  SET: the cell's value is the V of the op with the largest k, bit for bit (NaN payloads,
+ *    -0.0).  ADD: s = V[k1]; s = s + V[k2]; ... over the cell's ops in ascending k, one IEEE add each — no FMA, no tree, no atomics:
+ *    the left fold of dynamicsparse over duplicates (src/pcsr.jl:374-375).  A cell with one op keeps the bits of its V.
+ * 2. STORED cells are written in place as by dsa_mat_update_values: SET stores the folded value, ADD stores stored + s (one more
+ *    IEEE add).  No slot moves.
+ * 3. Cells that are NOT STORED are created with the folded value as by dsa_mat_insert_batch: its layout (merged and spread as
+ *    dsa_mat_rebalance_root spreads, never shrunk), its capacity rule, its table rules.  A zero, or a sum that cancels, is a STORED
+ *    zero as everywhere in these calls; dsa_mat_droptol removes it.
+ * As algebra: ADD is A <- A + sparse(I, J, V) in place; SET is dsa_mat_set_batch of nonzero triples with the layout of
+ * dsa_mat_insert_batch.  *distinct_out = *updated_out + *inserted_out (host pointers, may be NULL): the distinct cells, those written
+ * in place, those created.  Both orientations end with identical bits per cell; the same call on the same state gives the same
+ * bytes.  The content epoch moves once, and cached SpMV plans are dropped, iff something is written; the layout epoch moves iff a
+ * cell is created.  size(m) covers every cell of the batch afterwards, a stored one too, as after setindex!.  n = 0 changes nothing.
+ * Queued single writes are applied first.
+ * Every error is found before the first write — layouts, tables, epochs and plans stay as they were: DSA_EMODE in fill mode;
+ * DSA_EARG: op invalid, n < 0, an operand NULL with n > 0, n > 2^31 - 1; DSA_EKEY: an I[k] or J[k] below 1, in any op, also one that
+ * a later op overrides; DSA_EMODE: a new column or row that is not behind the last live entry of its table (dsa_mat_insert_batch's
+ * limit: "use set_batch"); DSA_EASSERT: the two halves disagree about what is stored.  Where dsa_last_error names an op it is an op
+ * of THIS batch — the last one on the cell, which is named too — never an index into the folded list.
+ * Scratch: one block on the handle, grown on demand and kept until the handle is destroyed: about 82 bytes per op (the pair sort 32,
+ * the sorted index and keys 20, the folded cells with the index of their last op 28, flags, queue, tile counts and mask 2; the
+ * compacted misses take the place of the sort's buffers), besides the scratch of the two halves for the distinct cells.  The number
+ * of launches does not depend on n; the host waits for the key scan, the distinct-cell count, the update's verdict and, when cells
+ * are created, the insert's key scan and verdicts.
+ * _dev: d_I / d_J / d_V are device arrays, read only by the fold, on the colmajor stream: they must hold their final contents when
+ * the call is made and stay unchanged until it returns (it does not return before the fold has finished).  When only stored cells are
+ * written the stores may still be enqueued (dsa_mat_sync); when cells are created the call returns with both streams drained.  The
+ * host form stages the triples through pooled device memory and waits for both streams. */
+int32_t dsa_mat_assemble_dev(dsa_mat_t* h, int32_t op, const int64_t* d_I, const int64_t* d_J, const double* d_V, int64_t n,
+                             int64_t* distinct_out, int64_t* updated_out, int64_t* inserted_out);
+int32_t dsa_mat_assemble(dsa_mat_t* h, int32_t op, const int64_t* I, const int64_t* J, const double* V, int64_t n,
+                         int64_t* distinct_out, int64_t* updated_out, int64_t* inserted_out);
 /* ---- column-range shards. No reference counterpart: the reference is single-process.  One PROCESS per GPU:
  * each process selects its device (dsa_set_device), builds ITS shard and runs the local SpMV; the single data-path collective —
  * the all-reduce (sum) of the partial y — is dsa_shard_allreduce_dev below (RCCL behind this ABI), or whatever the host layer has

@@ -13,7 +13,7 @@ from .api import (  # noqa: F401
     COLMAJOR, ROWMAJOR, UPD_SET, UPD_ADD, UPD_SKIP_MISSING, INS_SKIP_EXISTING, DynamicSparseMatrix, DynamicSparseVector, PackedCSC, Transposed,
     addrow, closefillmode, deletecolumn, deletecolumns, deletepartition, deleterow, deleterows, droptol, dropzeros, dynamicsparse,
     dynamicsparse_compressed_dev, dynamicsparse_dev, from_torch, hcat, vcat, blockdiag,
-    dynamicsparsevec, import_packedcsc_layout, import_vector_layout, nbpartitions, nnz, packedcsc, packedcsc_empty, pool_idle_bytes,
+    dynamicsparsevec, dynamicsparsevec_dev, import_packedcsc_layout, import_vector_layout, nbpartitions, nnz, packedcsc, packedcsc_empty, pool_idle_bytes,
     pool_trim, shrink_size, dev_switches, insert_values, upsert, assemble,
 )
 from .binding import Binding, DsaArgumentError, DsaBoundsError, DsaError, DsaErrorException, product  # noqa: F401

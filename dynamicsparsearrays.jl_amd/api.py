@@ -242,7 +242,133 @@ class DynamicSparseVector(_Handle):
         sel = np.fromiter((bool(f((int(a), float(b)))) for a, b in zip(k, v)), dtype=bool, count=len(k))
         return dynamicsparsevec(k[sel], v[sel], binding=self.b)
 
+    # ---- the vector as a device operand (include/dsa.h: dsa_vec_*_dev, dsa_vec_reduce, dsa_vec_dot, dsa_vec_axpby_vec; HIP library only) ----
+    _DEV_NEEDS = "dynamic vectors as device operands need the HIP product library"
+    RED_KINDS = {"sum": 0, "abssum": 1, "sqsum": 2, "absmax": 3}
+
+    def _require(self, symbol, message):
+        """DsaArgumentError(message) on a binding that does not have `symbol`"""
+        if not self.b.has(symbol):
+            raise B.DsaArgumentError(B.EARG, message)
+
+    def sync(self):                                   # dsa_vec_sync: everything enqueued on the vector's stream has finished
+        self.b.call("vec_sync", self.h)
+
+    def nonzeros_dev(self, d_keys, d_vals, cap):
+        """the stored (key, value) pairs in ascending key order into device memory (addresses of `cap` int64 / float64 entries); returns
+        their number.  More than `cap` pairs: DsaErrorException with code ECAP, nothing written.  Stream-ordered on the vector's
+        stream (sync())."""
+        self._require("vec_nonzeros_dev", self._DEV_NEEDS)
+        out = C.c_int64()
+        self.b.call("vec_nonzeros_dev", self.h, _dptr(d_keys), _dptr(d_vals), int(cap), C.byref(out))
+        return out.value
+
+    def to_torch(self, device=None):
+        """(int64 tensor of the keys, float64 tensor of the values) of the stored pairs, ascending, on the GPU: they never leave HBM"""
+        self._require("vec_nonzeros_dev", self._DEV_NEEDS)
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        n = self.nnz()
+        k = torch.empty(n, dtype=torch.int64, device=dev)
+        v = torch.empty(n, dtype=torch.float64, device=dev)
+        # the library writes on the vector's stream: torch's pending work on the fresh blocks first, torch's readers after the copy
+        torch.cuda.current_stream(dev).synchronize()
+        got = self.nonzeros_dev(k.data_ptr(), v.data_ptr(), n)
+        self.sync()
+        return k[:got], v[:got]
+
+    def to_dense_dev(self, d_x, nx):
+        """d_x[0:nx] = 0, then d_x[key - 1] = value for every stored pair (device address of nx doubles): the vector as an operand of
+        matmul_dev and of torch.  DsaBoundsError, with d_x untouched, when a stored key lies outside 1..nx.  Stream-ordered (sync())."""
+        self._require("vec_to_dense_dev", self._DEV_NEEDS)
+        self.b.call("vec_to_dense_dev", self.h, _dptr(d_x), int(nx))
+
+    def reduce(self, kind):
+        """"sum", "abssum" (sum of |v|), "sqsum" (sum of v * v) or "absmax" (max |v|, NaN propagates) over the stored values; an empty
+        vector gives 0.0.  The bits depend on the stored pairs only, not on the layout."""
+        self._require("vec_reduce", self._DEV_NEEDS)
+        if kind not in self.RED_KINDS:
+            raise B.DsaArgumentError(B.EARG, "kind must be one of %s" % ", ".join(sorted(self.RED_KINDS)))
+        out = C.c_double()
+        self.b.call("vec_reduce", self.h, self.RED_KINDS[kind], C.byref(out))
+        return out.value
+
+    def sum(self):
+        return self.reduce("sum")
+
+    def norm(self, p=2):
+        """the p-norm of the stored values, p in {1, 2, inf} (the 2-norm is sqrt of the "sqsum" reduction, taken here)"""
+        if p == 1:
+            return self.reduce("abssum")
+        if p == 2:
+            return float(np.sqrt(self.reduce("sqsum")))
+        if p in (np.inf, "inf"):
+            return self.reduce("absmax")
+        raise B.DsaArgumentError(B.EARG, "p must be 1, 2 or inf")
+
+    def dot(self, other):
+        """dot(v, w): `other` is a DynamicSparseVector (the sum over the keys both store) or a 1-D float64 tensor on the GPU (the sum
+        of v[k] * other[k - 1]; DsaBoundsError when a stored key lies outside 1..len(other)).  Only the scalar leaves HBM."""
+        self._require("vec_dot", self._DEV_NEEDS)
+        out = C.c_double()
+        if isinstance(other, DynamicSparseVector):
+            if other.b is not self.b:
+                raise B.DsaArgumentError(B.EARG, "vectors of two different libraries")
+            self.b.call("vec_dot", self.h, other.h, C.byref(out))
+            return out.value
+        if not _is_tensor(other):
+            raise B.DsaArgumentError(B.EARG, "other must be a DynamicSparseVector or a float64 tensor on the GPU")
+        import torch
+        if other.dtype != torch.float64 or not other.is_cuda or other.dim() != 1:
+            raise B.DsaArgumentError(B.EARG, "other must be a 1-D float64 tensor on the GPU")
+        x = other.contiguous()
+        torch.cuda.current_stream(x.device).synchronize()      # the library reads x on the vector's stream; the call waits for the scalar
+        self.b.call("vec_dot_dense_dev", self.h, _dptr(x.data_ptr()), x.numel(), C.byref(out))
+        return out.value
+
+    def axpby_vec(self, alpha, other, beta):
+        """alpha*self + beta*other as a NEW DynamicSparseVector of length max(len(self), len(other)): the pairs of axpby, built on the
+        device (they never leave HBM).  `other` may be `self`."""
+        self._require("vec_axpby_vec", self._DEV_NEEDS)
+        if other.b is not self.b:
+            raise B.DsaArgumentError(B.EARG, "vectors of two different libraries")
+        h = VP()
+        self.b.call("vec_axpby_vec", self.h, float(alpha), other.h, float(beta), C.byref(h))
+        return DynamicSparseVector(self.b, h)
+
     __hash__ = None
+
+
+def dynamicsparsevec_dev(d_keys, d_vals, n=None, combine="+", len=None, binding: Binding | None = None) -> DynamicSparseVector:
+    """dynamicsparsevec(I, V, [combine, n]) with I and V in HBM: device addresses of `n` int64 keys / float64 values (e.g.
+    tensor.data_ptr()), or 1-D int64 / float64 tensors on the GPU (then n defaults to their length).  Any order, duplicates folded by
+    `combine`; `len` = length of the vector (None: the largest key).  The arrays must be complete at the call (torch's current stream
+    is synchronised for tensors) and are the caller's again when it returns."""
+    b = _bind(binding)
+    if not b.has("vec_create_dev"):
+        raise B.DsaArgumentError(B.EARG, DynamicSparseVector._DEV_NEEDS)
+    keep = None
+    if _is_tensor(d_keys) or _is_tensor(d_vals):
+        import torch
+        if not (_is_tensor(d_keys) and _is_tensor(d_vals)):
+            raise B.DsaArgumentError(B.EARG, "keys and values must both be device addresses or both be tensors on the GPU")
+        if d_keys.dtype != torch.int64 or d_vals.dtype != torch.float64 or not d_keys.is_cuda or not d_vals.is_cuda or \
+                d_keys.dim() != 1 or d_vals.dim() != 1:
+            raise B.DsaArgumentError(B.EARG, "keys and values must be 1-D int64 / float64 tensors on the GPU")
+        if d_keys.numel() != d_vals.numel():
+            raise B.DsaArgumentError(B.EARG, "keys & nonzeros vectors must have same length.")
+        keep = (d_keys.contiguous(), d_vals.contiguous())
+        if n is None:
+            n = keep[0].numel()
+        if int(n) > keep[0].numel():
+            raise B.DsaArgumentError(B.EARG, "n exceeds the length of the tensors")
+        torch.cuda.current_stream(keep[0].device).synchronize()
+        d_keys, d_vals = keep[0].data_ptr(), keep[1].data_ptr()
+    if n is None:
+        raise B.DsaArgumentError(B.EARG, "n is required with device addresses")
+    h = VP()
+    b.call("vec_create_dev", _dptr(d_keys), _dptr(d_vals), int(n), COMBINE[combine], -1 if len is None else int(len), C.byref(h))
+    return DynamicSparseVector(b, h)
 
 
 def dynamicsparsevec(I, V, combine="+", n=None, binding: Binding | None = None) -> DynamicSparseVector:
@@ -380,6 +506,9 @@ class Transposed:
 
     def mul(self, x, **kw):
         return self.array.mul(x, transpose=True, **kw)
+
+    def mul_vec(self, x):
+        return self.array.mul_vec(x, transpose=True)
 
     def matmul(self, X):
         return self.array.matmul(X, transpose=True)
@@ -879,6 +1008,18 @@ class DynamicSparseMatrix(_Handle):
         yv = np.empty(cap, dtype=np.float64)
         self.b.call("mat_spmv_sparse", self.h, tr, xip, xvp, len(xi), yi.ctypes.data_as(P_I64), yv.ctypes.data_as(P_F64), cap, C.byref(n_out))
         return yi[:n_out.value].copy(), yv[:n_out.value].copy()
+
+    def mul_vec(self, x, transpose=False):
+        """mat * v / transpose(mat) * v for a DynamicSparseVector, as a NEW DynamicSparseVector of length size(mat, 1 | 2): the vector
+        dynamicsparsevec(*mul(x), n=size) would build, with x, the product and the result never leaving HBM."""
+        self._require("mat_mul_vec", "mul_vec needs the HIP product library")
+        if not isinstance(x, DynamicSparseVector):
+            raise B.DsaArgumentError(B.EARG, "x must be a DynamicSparseVector (mul takes pairs and dense arrays)")
+        if x.b is not self.b:
+            raise B.DsaArgumentError(B.EARG, "operands of two different libraries")
+        h = VP()
+        self.b.call("mat_mul_vec", self.h, 1 if transpose else 0, x.h, C.byref(h))
+        return DynamicSparseVector(self.b, h)
 
     def mul_dev(self, d_xi, d_xv, nx, d_yi, d_yv, cap, d_count, transpose=False):
         """the sparse product with every operand in HBM (device addresses, e.g. tensor.data_ptr()); stream-ordered, no host wait"""

@@ -189,6 +189,15 @@ _PRODUCT_ONLY_SIGS = {
     "mat_create_from_compressed_dev": [I32, I32, I32, VP, VP, VP, I64, I64, I64, C.POINTER(VP)],
     "mat_combine": [VP, F64, VP, F64, I64, I64, I64, I64, C.POINTER(VP)],
     "pcsc_check": [VP, P_I64],
+    # DynamicSparseVector as a device operand (csrc/vecops_host.hip)
+    "vec_nonzeros_dev": [VP, VP, VP, I64, P_I64],
+    "vec_create_dev": [VP, VP, I64, I32, I64, C.POINTER(VP)],
+    "mat_mul_vec": [VP, I32, VP, C.POINTER(VP)],
+    "vec_axpby_vec": [VP, F64, VP, F64, C.POINTER(VP)],
+    "vec_reduce": [VP, I32, P_F64],
+    "vec_dot": [VP, VP, P_F64],
+    "vec_dot_dense_dev": [VP, VP, I64, P_F64],
+    "vec_to_dense_dev": [VP, VP, I64],
 }
 
 

@@ -6,10 +6,11 @@
 // units of its own: the fill-mode buffer in fill_host.hip, every write to a matrix (the builds of both orientations, the set batch
 // and its strategies, the flush of queued writes, the delete of one column or row) in matwrite_host.hip; the exports, the products,
 // the device import and the reductions in export_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, ingest_host.hip and
-// scale_host.hip; the in-place mutators (scale, batched delete, droptol, update, insert), the sparse-x product and the parity hooks
-// have entry points of their own in mutate_host.hip, sparsex_host.hip and raw_host.hip.  Everything that works on ONE packed-memory
-// array (the Pma of host.h) is in the engine units pma_host.hip (lifecycle, geometry, rebalances, reads), writes_host.hip (yield loop
-// around the sequencer, batch-parallel rounds), build_host.hip (K-build) and spmv_host.hip (SpMV meta and plan).
+// scale_host.hip; the in-place mutators (scale, batched delete, droptol, update, insert), the sparse-x product, the vector as a device
+// operand and the parity hooks have entry points of their own in mutate_host.hip, sparsex_host.hip, vecops_host.hip and raw_host.hip.
+// Everything that works on ONE packed-memory array (the Pma of host.h) is in the engine units pma_host.hip (lifecycle, geometry,
+// rebalances, reads), writes_host.hip (yield loop around the sequencer, batch-parallel rounds), build_host.hip (K-build) and
+// spmv_host.hip (SpMV meta and plan).
 //
 // Everything that touches slots runs on the GPU (rebalance.hip, sequencer.hip, spmv.hip).  The host
 // keeps only: the control scalars of each PMA (mirrored from the device control block), the integer
@@ -135,34 +136,6 @@ void vec_apply(dsa_vec_t* h, const int64_t* keys, const double* vals, int64_t n)
     for (int64_t i = 0; i < upto; ++i) if (vals[i] != 0.0) h->n = std::max(h->n, keys[i]);
     if (err) fail(err, err_text(err));
 }
-void vec_flush(dsa_vec_t* h) {
-    bind_device(h->P);
-    if (h->pk.empty()) return;
-    std::vector<int64_t> k; std::vector<double> v;
-    k.swap(h->pk); v.swap(h->pv);                      // the queue is empty even if the apply fails
-    vec_apply(h, k.data(), v.data(), (int64_t)k.size());
-}
-
-// K-pack of the whole vector into its alternate slot buffer (free between rebalances); returns the number of stored cells.
-// The count is known on return, the packed cells are still being written on the vector's OWN stream: a consumer on another stream
-// (the other operand of == / +) must wait for it (wait_for_pack).
-int64_t vec_pack_alt(dsa_vec_t* h) {
-    Pma& P = h->P;
-    int64_t cnt = 0;
-    const int alt = 1 - P.cur;
-    {
-        const int64_t c = pack_small(P, P.K(), P.V(), P.O(), 1, P.capacity(), P.KA(alt), P.vals[alt], P.cap_alloc);
-        if (c >= 0) return c;
-    }
-    LAUNCH("compact", launch_compact_range(P.K(), P.V(), P.O(), 1, P.capacity(), P.KA(alt), P.vals[alt], P.cap_alloc, &P.work, &cnt, P.stream));
-    return cnt;
-}
-// the packed cells of `producer` (vec_pack_alt) are complete before anything enqueued on `consumer`'s stream afterwards runs
-void wait_for_pack(dsa_vec_t* producer, dsa_vec_t* consumer) {
-    if (producer->P.stream == consumer->P.stream) return;
-    HIPCHK(hipStreamSynchronize(producer->P.stream));
-}
-
 // PackedMemoryArray(elements) (src/pma.jl:69-84) of the n cells packed at the front of S's alternate buffer (view_dev: ascending,
 // distinct keys — nothing to sort or fold): geometry on the host, then ONE k_move2<PACKED> from S's buffer straight into the new
 // vector's slot array.  The cells never leave HBM.  Everything is enqueued on S's stream (the pack that produced the cells runs
@@ -205,9 +178,37 @@ dsa_vec* vec_from_packed_dev(Pma& S, int64_t n, int64_t len) {
 
 }  // namespace
 
-// what sparsex_host.hip calls as well (declared in host.h)
+// what sparsex_host.hip and vecops_host.hip call as well (declared in host.h)
 namespace dsa {
 namespace host {
+
+void vec_flush(dsa_vec_t* h) {
+    bind_device(h->P);
+    if (h->pk.empty()) return;
+    std::vector<int64_t> k; std::vector<double> v;
+    k.swap(h->pk); v.swap(h->pv);                      // the queue is empty even if the apply fails
+    vec_apply(h, k.data(), v.data(), (int64_t)k.size());
+}
+
+// K-pack of the whole vector into its alternate slot buffer (free between rebalances); returns the number of stored cells.
+// The count is known on return, the packed cells are still being written on the vector's OWN stream: a consumer on another stream
+// (the other operand of == / +) must wait for it (wait_for_pack).
+int64_t vec_pack_alt(dsa_vec_t* h) {
+    Pma& P = h->P;
+    int64_t cnt = 0;
+    const int alt = 1 - P.cur;
+    {
+        const int64_t c = pack_small(P, P.K(), P.V(), P.O(), 1, P.capacity(), P.KA(alt), P.vals[alt], P.cap_alloc);
+        if (c >= 0) return c;
+    }
+    LAUNCH("compact", launch_compact_range(P.K(), P.V(), P.O(), 1, P.capacity(), P.KA(alt), P.vals[alt], P.cap_alloc, &P.work, &cnt, P.stream));
+    return cnt;
+}
+// the packed cells of `producer` (vec_pack_alt) are complete before anything enqueued on `consumer`'s stream afterwards runs
+void wait_for_pack(dsa_vec_t* producer, dsa_vec_t* consumer) {
+    if (producer->P.stream == consumer->P.stream) return;
+    HIPCHK(hipStreamSynchronize(producer->P.stream));
+}
 
 void ensure_xy(dsa_mat* h, int64_t nx, int64_t ny) {
     if (nx > h->x_cap) { if (h->d_x) hipFree(h->d_x); h->x_cap = std::max<int64_t>(nx, 1024); HIPCHK(hipMalloc(&h->d_x, (size_t)h->x_cap * sizeof(double))); }

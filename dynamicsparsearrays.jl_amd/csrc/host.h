@@ -1,7 +1,7 @@
 // csrc/host.h — what the host units of libdsa_hip.so share (dsa_host.hip and the *_host.hip engine units): the error and launch
 // checks, the roctx range of an ABI entry point, the Pma engine struct with the declarations of the engine functions that cross a
 // unit boundary, and the handle structs.  The host units are dsa_host.hip, fill_host.hip, matwrite_host.hip, pma_host.hip,
-// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, mutate_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, insert_host.hip, assemble_host.hip, sparsex_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
+// writes_host.hip, build_host.hip, spmv_host.hip, spmm_host.hip, selprod_host.hip, spgemm_host.hip, mutate_host.hip, scale_host.hip, delbatch_host.hip, droptol_host.hip, update_host.hip, insert_host.hip, assemble_host.hip, sparsex_host.hip, vecops_host.hip, export_host.hip, ingest_host.hip, combine_host.hip and raw_host.hip.  Host units only: a kernel unit
 // (rebalance.hip, spmv.hip, sequencer.hip, ...) never includes it; what kernel units share is in dsa_dev.h, find_dev.h, wave_dev.h,
 // seq_dev.h, export_dev.h and spmm_dev.h.  Everything declared here lives in dsa::host with hidden visibility — none of it is part of the shared object's
 // dynamic symbol table (the definitions in the units inherit the visibility of their declaration here).
@@ -178,6 +178,8 @@ struct Pma {
     ExportArea sub, subi;
     // reduce / scale (scale.hip): per-span records, and the pinned {error word, sequence number} of their bounds checks
     ExportArea sc;
+    // whole-vector operations (vecops.hip; vectors only): the partials and the scalar of a reduction, the pinned words of vecops.h
+    ExportArea vo;
     // batched sparse-x product (spgemm.hip): per-entry spans and per-column counts, and the slabs of the long columns (all zero
     // between two calls)
     ExportArea spg, spgs;
@@ -322,10 +324,23 @@ bool spmv_plan_shape_ok(const Pma& P, int64_t nx, int64_t ny);
 void spmv_plan_build(Pma& P, int64_t nx, int64_t ny, hipStream_t s);
 bool spmv_plan_product(Pma& P, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s);
 
-// ---- dsa_host.hip: what sparsex_host.hip needs of the handle layer
+// ---- dsa_host.hip: what sparsex_host.hip and vecops_host.hip need of the handle layer
 void ensure_xy(dsa_mat* h, int64_t nx, int64_t ny);
 void spmv_dev(dsa_mat* h, int32_t transpose, int32_t algo, const double* d_x, int64_t nx, double* d_y, int64_t ny, hipStream_t s,
               int pattern = 0);
+// a vector's queued single writes applied; K-pack of the whole vector into its alternate slot buffer (returns the number of stored
+// cells; the cells are still being written on the vector's own stream); the wait of `consumer`'s stream for `producer`'s pack
+void vec_flush(dsa_vec* h);
+int64_t vec_pack_alt(dsa_vec* h);
+void wait_for_pack(dsa_vec* producer, dsa_vec* consumer);
+
+// ---- sparsex_host.hip: the parts of the sparse-x product dsa_mat_mul_vec (vecops_host.hip) runs with x in HBM: the scratch of the
+// handle (ny result rows, nx_upload x entries in Spx::dx), the strategy rule, and the product itself enqueued on the walked
+// structure's stream (returned); host != nullptr: {count, sequence number, the first pin_cells pairs} go to that pinned area
+void spx_ensure(dsa_mat* h, int64_t ny, int64_t nx_upload, hipStream_t s);
+bool spx_xdriven(int64_t nx, int64_t ncols);
+hipStream_t spx_enqueue(dsa_mat* h, int32_t transpose, bool xdriven, const int64_t* d_xi, const double* d_xv, int64_t nx, int64_t ny, int64_t ncols,
+                        int64_t* out_i, double* out_v, int64_t cap, int64_t* d_count, long long* host, unsigned long long seq, int64_t pin_cells);
 
 // ---- matwrite_host.hip: the writes in terms of dsa_mat.  The builds of both orientations of a fresh handle from 1-based int64 triples
 // (a constructor hands a handle whose build, or the SpMV meta prefetch behind it, threw to mat_discard: structures and handle go)

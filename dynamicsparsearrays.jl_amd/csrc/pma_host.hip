@@ -69,6 +69,7 @@ void pma_destroy(Pma& P) {
     P.sub.release();
     P.subi.release();
     P.sc.release();
+    P.vo.release();
     P.del.release();
     P.drp.release();
     P.upd.release();

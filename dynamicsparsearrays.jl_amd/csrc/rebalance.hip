@@ -484,15 +484,7 @@ hipError_t launch_packed_equal(KeyArr ka, const double* va, KeyArr kb, const dou
 // x[i] at i + lower_bound(y, key) and y[j] at j + upper_bound(x, key).  A key stored in both operands keeps ONE cell (x's slot,
 // value alpha*x + beta*y, dropped when that is zero — the both-stored rule of the sparse-vector +/- the reference falls back
 // to, test/functional/math.jl:53-94); one-sided cells carry alpha*x or beta*y.  `keep` is the occupancy bitmap K-pack consumes.
-static __device__ __forceinline__ int64_t packed_bound(KeyArr k, int64_t n, int64_t key, bool upper) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int64_t c = k[mid];
-        if (c < key || (upper && c == key)) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// (packed_bound, the bisection over a packed key stream, is in wave_dev.h: vecops.hip looks keys up with it as well)
 __global__ __launch_bounds__(256) void k_merge_axpby(KeyArr ka, const double* __restrict__ va, int64_t na, double alpha,
                                                      KeyArr kb, const double* __restrict__ vb, int64_t nb, double beta,
                                                      int64_t* __restrict__ mk, double* __restrict__ mv, uint64_t* __restrict__ keep) {

@@ -47,6 +47,11 @@ void par_memcpy(void* dst, const void* src, size_t bytes) {
     std::memcpy(dst, src, std::min(part, bytes));
     for (int t = 0; t < started; ++t) th[t].join();
 }
+}  // namespace
+
+// what vecops_host.hip (dsa_mat_mul_vec) calls as well (declared in host.h)
+namespace dsa {
+namespace host {
 void spx_ensure(dsa_mat* h, int64_t ny, int64_t nx_upload, hipStream_t s) {
     dsa_mat::Spx& x = h->spx;
     if (ny > x.rows_cap) {
@@ -80,15 +85,6 @@ void spx_ensure(dsa_mat* h, int64_t ny, int64_t nx_upload, hipStream_t s) {
         x.x_cap = c;
     }
 }
-void spx_stage(dsa_mat* h, size_t bytes, hipStream_t s) {
-    dsa_mat::Spx& x = h->spx;
-    if (bytes <= x.stage_bytes) return;
-    if (x.stage) { HIPCHK(hipStreamSynchronize(s)); if (x.res_stream && x.res_stream != s) HIPCHK(hipStreamSynchronize(x.res_stream)); HIPCHK(hipHostFree(x.stage)); }
-    x.stage = nullptr; x.stage_bytes = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 1u << 16);
-    HIPCHK(hipHostMalloc(&x.stage, want, hipHostMallocDefault));
-    x.stage_bytes = want;
-}
 // which strategy: the x-driven kernel costs ~ the stored entries (a handful of dependent round trips per entry, one wave each), the
 // gather kernel ~ the slot array (twice: values, pattern).  DSA_SPX_XDRIVEN=0/1 forces one (A/B, coverage).
 bool spx_xdriven(int64_t nx, int64_t ncols) {
@@ -97,9 +93,10 @@ bool spx_xdriven(int64_t nx, int64_t ncols) {
     return nx * 8 < std::max<int64_t>(ncols, 1);
 }
 // enqueues the whole product on the walked structure's stream; x entries at (d_xi, d_xv): HBM, or pinned host memory for the
-// x-driven kernel.  Result: out_i / out_v / d_count (HBM) and, when `host`, the landing area + sequence number.
+// x-driven kernel.  Result: out_i / out_v / d_count (HBM) and, when `host`, the landing area (the count, the first pin_cells pairs)
+// + sequence number.
 hipStream_t spx_enqueue(dsa_mat* h, int32_t transpose, bool xdriven, const int64_t* d_xi, const double* d_xv, int64_t nx, int64_t ny, int64_t ncols,
-                        int64_t* out_i, double* out_v, int64_t cap, int64_t* d_count, long long* host, unsigned long long seq) {
+                        int64_t* out_i, double* out_v, int64_t cap, int64_t* d_count, long long* host, unsigned long long seq, int64_t pin_cells) {
     dsa_mat::Spx& x = h->spx;
     Pma& P = xdriven ? (transpose ? h->row : h->col) : (transpose ? h->col : h->row);      // the structure that is walked
     hipStream_t s = P.stream;
@@ -108,7 +105,7 @@ hipStream_t spx_enqueue(dsa_mat* h, int32_t transpose, bool xdriven, const int64
     hipError_t e;
     if (xdriven) {
         LAUNCH("sparse-x accumulate", launch_spx_accum(P.view(), d_xi, d_xv, nx, x.acc, x.bm, ny, s));
-        e = launch_spx_finish(x.bm, ny, x.tile_cnt, x.tile_off, x.ticket, x.acc, 1, out_i, out_v, cap, d_count, host, SPX_PIN_CELLS, seq, s);
+        e = launch_spx_finish(x.bm, ny, x.tile_cnt, x.tile_off, x.ticket, x.acc, 1, out_i, out_v, cap, d_count, host, pin_cells, seq, s);
     } else {
         ensure_xy(h, std::max<int64_t>(2 * ncols, 1), 2 * ny);
         double* d_xd = h->d_x; double* d_xf = h->d_x + ncols;
@@ -119,10 +116,23 @@ hipStream_t spx_enqueue(dsa_mat* h, int32_t transpose, bool xdriven, const int64
         // reference never computes — the touched rows that came out non-finite are summed again without those cells
         LAUNCH("repair", launch_spx_repair(P.view(), d_xd, d_xf, ncols, h->d_y + ny, h->d_y, ny, s));
         LAUNCH("pattern", launch_spx_pattern_bits(h->d_y + ny, ny, x.bm, s));
-        e = launch_spx_finish(x.bm, ny, x.tile_cnt, x.tile_off, x.ticket, h->d_y, 0, out_i, out_v, cap, d_count, host, SPX_PIN_CELLS, seq, s);
+        e = launch_spx_finish(x.bm, ny, x.tile_cnt, x.tile_off, x.ticket, h->d_y, 0, out_i, out_v, cap, d_count, host, pin_cells, seq, s);
     }
     launch_check(e, "sparse-x finish launch: ");
     return s;
+}
+}  // namespace host
+}  // namespace dsa
+
+namespace {
+void spx_stage(dsa_mat* h, size_t bytes, hipStream_t s) {
+    dsa_mat::Spx& x = h->spx;
+    if (bytes <= x.stage_bytes) return;
+    if (x.stage) { HIPCHK(hipStreamSynchronize(s)); if (x.res_stream && x.res_stream != s) HIPCHK(hipStreamSynchronize(x.res_stream)); HIPCHK(hipHostFree(x.stage)); }
+    x.stage = nullptr; x.stage_bytes = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 2, 1u << 16);
+    HIPCHK(hipHostMalloc(&x.stage, want, hipHostMallocDefault));
+    x.stage_bytes = want;
 }
 // a long result (more pairs than the landing area holds) starts its way down as soon as its size is known: DMA into pinned staging in
 // up to 8 pieces, an event behind each; dsa_mat_spmv_sparse_fetch copies a piece to the caller's arrays (four threads for long ones)
@@ -215,7 +225,7 @@ int32_t dsa_mat_spmv_sparse_begin(dsa_mat_t* h, int32_t transpose, const int64_t
     const unsigned long long seq = ++x.seq;
     __atomic_thread_fence(__ATOMIC_RELEASE);
     tq("x staged");
-    spx_enqueue(h, transpose, xdriven, d_xi, d_xv, nx, ny, ncols, x.oi, x.ov, x.out_cap, x.d_count, x.pin, seq);
+    spx_enqueue(h, transpose, xdriven, d_xi, d_xv, nx, ny, ncols, x.oi, x.ov, x.out_cap, x.d_count, x.pin, seq, SPX_PIN_CELLS);
     x.res_stream = s;
     tq("enqueued");
     // the count (and a short result) arrive in the landing area (s is P's stream)
@@ -304,7 +314,7 @@ int32_t dsa_mat_spmv_sparse_dev(dsa_mat_t* h, int32_t transpose, const int64_t* 
     if (ny <= 0 || nx <= 0) { HIPCHK(hipMemsetAsync(d_count, 0, sizeof(int64_t), P.stream)); return DSA_OK; }
     spx_ensure(h, ny, 0, P.stream);
     h->spx.res_count = -1; h->spx.dl_started = false;
-    h->spx.res_stream = spx_enqueue(h, transpose, xdriven, d_xi, d_xv, nx, ny, ncols, d_yi, d_yv, cap, d_count, nullptr, 0ull);
+    h->spx.res_stream = spx_enqueue(h, transpose, xdriven, d_xi, d_xv, nx, ny, ncols, d_yi, d_yv, cap, d_count, nullptr, 0ull, 0);
     API_CATCH
 }
 

@@ -1,6 +1,6 @@
 // csrc/wave_dev.h — the wave-level primitives and the pinned hand-over that more than one kernel unit uses.  Device code only: a
 // kernel unit includes it, a host unit never does.  A wave is 64 lanes; every function here is called by a whole wave (the
-// hand-over by the one thread that publishes).
+// hand-over by the one thread that publishes, the bisection by one thread).
 #pragma once
 #include "dsa_dev.h"
 
@@ -62,6 +62,19 @@ __device__ __forceinline__ uint64_t readfirstlane64(uint64_t w) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w >> 32));
     return ((uint64_t)hi << 32) | lo;
+}
+
+// ---- bisection over a packed key stream (ascending, distinct keys: the output of K-pack): the first index whose key is >= `key`
+// (upper: > `key`), n when there is none.  One thread, log2(n) dependent loads.  The merge of k_merge_axpby (rebalance.hip) and the
+// lookups of the dot product (vecops.hip) share it.
+__device__ __forceinline__ int64_t packed_bound(KeyArr k, int64_t n, int64_t key, bool upper) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        const int64_t c = k[mid];
+        if (c < key || (upper && c == key)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
 }
 
 // ---- the pinned hand-over: a result goes to PINNED HOST memory without a copy command, an event or a stream sync.  The publishing

@@ -20,13 +20,15 @@ module DynamicSparseArraysAMD
 
 using SparseArrays
 using LinearAlgebra: Transpose
+import LinearAlgebra
 
 export DynamicSparseVector, DynamicSparseMatrix, DynamicMatrixColView, PackedCSC, dynamicsparsevec, dynamicsparse, nbpartitions,
        deletecolumn!, deleterow!, deletecolumns!, deleterows!, deletepartition!, addrow!, closefillmode!, shrink_size!, set_device!, shard_range, dynamicsparse_shard, comm_unique_id, ShardComm, shard_allreduce!,
        shard_spmv_allreduce!, set_wait_policy!, WAIT_SPIN, WAIT_BLOCK, pool_idle_bytes, pool_trim!,
        keyint, keyfrom, col_view_dev!, row_view_dev!, spmv_sparse_dev!, dynamicsparse_dev, dynamicsparse_compressed_dev,
        scale!, reduce_rows, reduce_cols, mul_rows, mul_cols, mul_sparse, dropzeros!, droptol!, count_droptol,
-       update_values!, add_values!, getstored, insert_values!, upsert!, assemble!
+       update_values!, add_values!, getstored, insert_values!, upsert!, assemble!,
+       mul_vec, axpby_vec, dynamicsparsevec_dev, nonzeros_dev!, to_dense_dev!
 
 const libdsa = get(ENV, "DSA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libdsa_hip.so"))
 
@@ -210,6 +212,61 @@ function _axpby(a::DynamicSparseVector{K}, alpha::Float64, b::DynamicSparseVecto
 end
 Base.:(+)(a::DynamicSparseVector{K}, b::DynamicSparseVector{K}) where {K<:Integer} = _axpby(a, 1.0, b, 1.0)
 Base.:(-)(a::DynamicSparseVector{K}, b::DynamicSparseVector{K}) where {K<:Integer} = _axpby(a, 1.0, b, -1.0)
+# ---- the vector as a device operand (include/dsa.h: csrc/vecops_host.hip; Integer keys: a device array holds the mapped integers)
+"alpha * a + beta * b as a NEW DynamicSparseVector of length max(length(a), length(b)), built on the device from the pairs a + b / a - b
+deliver — dsa_vec_axpby_vec"
+function axpby_vec(a::DynamicSparseVector{K}, alpha::Real, b::DynamicSparseVector{K}, beta::Real) where {K<:Integer}
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _check(ccall((:dsa_vec_axpby_vec, libdsa), Int32, (Ptr{Cvoid}, Float64, Ptr{Cvoid}, Float64, Ref{Ptr{Cvoid}}),
+                 a.h, Float64(alpha), b.h, Float64(beta), out))
+    return DynamicSparseVector{K}(out[])
+end
+function _vec_reduce(v::DynamicSparseVector, kind::Integer)
+    out = Ref{Float64}(0.0)
+    _check(ccall((:dsa_vec_reduce, libdsa), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}), v.h, kind, out))
+    return out[]
+end
+# sum(v), norm(v, p) and dot(v, w) over the stored values, reduced on the device in a fixed order (the bits depend on the stored
+# pairs only); only the scalar comes back
+Base.sum(v::DynamicSparseVector) = _vec_reduce(v, 0)
+function LinearAlgebra.norm(v::DynamicSparseVector, p::Real = 2)
+    p == 1 && return _vec_reduce(v, 1)
+    p == 2 && return sqrt(_vec_reduce(v, 2))
+    p == Inf && return _vec_reduce(v, 3)
+    throw(ArgumentError("p must be 1, 2 or Inf"))
+end
+function LinearAlgebra.dot(a::DynamicSparseVector{K}, b::DynamicSparseVector{K}) where {K}
+    out = Ref{Float64}(0.0)
+    _check(ccall((:dsa_vec_dot, libdsa), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{Float64}), a.h, b.h, out))
+    return out[]
+end
+"dot(v, x) with a dense x of nx Float64 in HBM (device pointer); BoundsError when v stores a key outside 1..nx — dsa_vec_dot_dense_dev"
+function LinearAlgebra.dot(v::DynamicSparseVector, d_x::Ptr{Cvoid}, nx::Integer)
+    out = Ref{Float64}(0.0)
+    _check(ccall((:dsa_vec_dot_dense_dev, libdsa), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ref{Float64}), v.h, d_x, nx, out))
+    return out[]
+end
+"the stored pairs in ascending key order into device arrays of `cap` Int64 / Float64; returns their number, stream-ordered on the
+vector's stream — dsa_vec_nonzeros_dev"
+function nonzeros_dev!(v::DynamicSparseVector, d_keys::Ptr{Cvoid}, d_vals::Ptr{Cvoid}, cap::Integer)
+    n = Ref{Int64}(0)
+    _check(ccall((:dsa_vec_nonzeros_dev, libdsa), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ref{Int64}), v.h, d_keys, d_vals, cap, n))
+    return n[]
+end
+"d_x[1:nx] = Vector(v) in HBM (device pointer); BoundsError, d_x untouched, when v stores a key outside 1..nx — dsa_vec_to_dense_dev"
+function to_dense_dev!(v::DynamicSparseVector, d_x::Ptr{Cvoid}, nx::Integer)
+    _check(ccall((:dsa_vec_to_dense_dev, libdsa), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64), v.h, d_x, nx))
+    return v
+end
+"dynamicsparsevec(I, V, combine, n) with I (Int64) and V (Float64) in HBM (device pointers): + , * and \"last\" (any other function)
+fold duplicates in the library — dsa_vec_create_dev"
+function dynamicsparsevec_dev(d_keys::Ptr{Cvoid}, d_vals::Ptr{Cvoid}, n::Integer, combine::Function = +, len::Integer = -1)
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _check(ccall((:dsa_vec_create_dev, libdsa), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int64, Ref{Ptr{Cvoid}}),
+                 d_keys, d_vals, n, get(COMBINE, combine, COMBINE_LAST), len, out))
+    return DynamicSparseVector{Int64}(out[])
+end
+
 # filter(f, v)  (src/vector.jl:83 -> src/pma.jl:224-234): the predicate runs in Julia on the packed entries, the result is a new vector
 function Base.filter(f, v::DynamicSparseVector{K}) where {K}
     ks, vs = _stored(v)
@@ -602,6 +659,15 @@ function spmv_sparse_dev!(a::DynamicSparseMatrix, tr::Bool, d_xi::Ptr{Cvoid}, d_
                  a.h, tr ? 1 : 0, d_xi, d_xv, nx, d_yi, d_yv, cap, d_count))
     return a
 end
+"mat * v / transpose(mat) * v for a DynamicSparseVector as a NEW DynamicSparseVector of length size(mat, 1 | 2): x, the product and the
+result stay in HBM (Integer keys) — dsa_mat_mul_vec"
+function _mul_vec(a::DynamicSparseMatrix, tr::Bool, v::DynamicSparseVector, ::Type{KO}) where {KO<:Integer}
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _check(ccall((:dsa_mat_mul_vec, libdsa), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ref{Ptr{Cvoid}}), a.h, tr ? 1 : 0, v.h, out))
+    return DynamicSparseVector{KO}(out[])
+end
+mul_vec(a::DynamicSparseMatrix{K,L}, v::DynamicSparseVector) where {K,L} = _mul_vec(a, false, v, K)
+mul_vec(t::Transposed{DynamicSparseMatrix{K,L}}, v::DynamicSparseVector) where {K,L} = _mul_vec(t.array, true, v, L)
 _entries(km::KeyMap, v::DynamicSparseVector) = _stored_int(v)
 _entries(km::KeyMap, v::SparseVector) = (_in(km, rowvals(v)), Vector{Float64}(nonzeros(v)))
 const SpVec = Union{DynamicSparseVector,SparseVector}

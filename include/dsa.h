@@ -128,6 +128,39 @@ int32_t dsa_vec_rebalance_root(dsa_vec_t* h);
  * 3 and 4 ignore the density thresholds; 1 and 2 leave a layout that violates them until the next root rebalance. */
 int32_t dsa_vec_dev_relayout(dsa_vec_t* h, int32_t mode);
 
+/* ---- DynamicSparseVector as a device operand (csrc/vecops.hip, csrc/vecops_host.hip; HIP library only).  d_* are DEVICE arrays; every
+ * call applies the queued writes of its vector operands first and works on their packed cells, on the vector's own stream.
+ *
+ * nonzeroinds(v) / nonzeros(v) (src/vector.jl:93-109) delivered into HBM: the stored pairs in ascending key order, keys as int64
+ * whatever the physical key width.  *n_out = nnz(v) on return, also with DSA_ECAP (cap < nnz: nothing is written).  The copy is
+ * enqueued on the vector's stream (dsa_vec_set_stream / dsa_vec_sync); the host does not wait for it. */
+int32_t dsa_vec_nonzeros_dev(dsa_vec_t* h, int64_t* d_keys, double* d_vals, int64_t cap, int64_t* n_out);
+/* dynamicsparsevec(I, V, combine, n) (src/vector.jl:44-62) with I and V in HBM: any order, duplicates folded by combine_op as
+ * dsa_vec_create folds them; len < 0 => _guess_length(I) (:6), found on the device.  The result is slot for slot the vector
+ * dsa_vec_create builds from the same arrays.  The arrays are read on the new vector's stream and are the caller's again on return. */
+int32_t dsa_vec_create_dev(const int64_t* d_keys, const double* d_vals, int64_t n, int32_t combine_op, int64_t len, dsa_vec_t** out);
+/* v1 + v2 (1, 1), v1 - v2 (1, -1), -v (-1, 0, b = a) — the AbstractSparseVector fallbacks dsa_vec_axpby serves — as a NEW dynamic
+ * vector of length max(length(a), length(b)): *out = dynamicsparsevec of exactly the pairs dsa_vec_axpby delivers (same merge, same
+ * both-stored rule, same bits), built from the compacted pairs in HBM.  b == a is allowed.  The operands are only read. */
+int32_t dsa_vec_axpby_vec(dsa_vec_t* a, double alpha, dsa_vec_t* b, double beta, dsa_vec_t** out);
+/* sum(v), sum(abs, v), sum(abs2, v), maximum(abs, v) over the stored values (the generic AbstractArray fallbacks the reference leaves
+ * to Base; norm(v, 1 | 2 | Inf) are these): kind = DSA_RED_SUM, _ABSSUM, _SQSUM or _ABSMAX (DSA_RED_COUNT is DSA_EARG: dsa_vec_nnz).
+ * Two stages over the packed cells in a fixed order, products and sums rounded separately, no floating-point atomics: the bits depend
+ * on the stored pairs only (not on the layout) and repeat from call to call.  Every sum starts at +0.0 (an empty vector: +0.0; a sum
+ * of negative zeros: +0.0).  DSA_RED_ABSMAX propagates NaN. */
+int32_t dsa_vec_reduce(dsa_vec_t* h, int32_t kind, double* out);
+/* dot(v, w) (the AbstractSparseVector fallback): the sum over the keys stored in BOTH operands of the rounded products a_k * b_k, in
+ * the same two stages (driven by the operand with fewer stored cells, ties by a; the other one is bisected).  Empty or disjoint
+ * operands: +0.0.  dsa_vec_dot(a, a) is bit for bit dsa_vec_reduce(a, DSA_RED_SQSUM). */
+int32_t dsa_vec_dot(dsa_vec_t* a, dsa_vec_t* b, double* out);
+/* dot(v, x) with a dense x of nx entries in HBM: the sum of the rounded products v_k * x[k - 1].  DSA_EBOUNDS when v stores a key
+ * outside 1..nx (checked in the same pass; *out is then +0.0). */
+int32_t dsa_vec_dot_dense_dev(dsa_vec_t* h, const double* d_x, int64_t nx, double* out);
+/* Vector(v) into HBM: d_x[0 .. nx) = 0, then d_x[k - 1] = v_k — a dynamic vector as an operand of dsa_mat_spmm_dense_dev.  DSA_EBOUNDS
+ * when v stores a key outside 1..nx, found before the first write (d_x is untouched).  The writes are enqueued on the vector's stream
+ * (dsa_vec_sync); the host waits for the bounds verdict only. */
+int32_t dsa_vec_to_dense_dev(dsa_vec_t* h, double* d_x, int64_t nx);
+
 /* ---------------- PackedCSC (integer-indexed partitions) ---------------- */
 /* PackedCSC(row_keys::Vector{Vector}, values::Vector{Vector}, combine)  src/pcsr.jl:26-63
  * given CSC-style: partition p holds entries [colptr[p], colptr[p+1]) (0-based offsets, nparts+1 entries) */
@@ -334,6 +367,15 @@ int32_t dsa_mat_spmv_sparse_fetch(dsa_mat_t* h, int64_t* yi, double* yv, int64_t
  * twin orientation) entries of x outside 1..n are ignored — column keys below 1 need the host entry point or fewer entries. */
 int32_t dsa_mat_spmv_sparse_dev(dsa_mat_t* h, int32_t transpose, const int64_t* d_xi, const double* d_xv, int64_t nx,
                                 int64_t* d_yi, double* d_yv, int64_t cap, int64_t* d_count);
+/* mat * v / transpose(mat) * v for a DynamicSparseVector (src/operations.jl:14-36, the method whose operand is a dynamic vector) with a
+ * dynamic vector as the result: *out = dynamicsparsevec(rows, values, +, size(mat, 1 | 2)) of the pairs dsa_mat_spmv_sparse returns for
+ * x's stored pairs — same touched rows, same rule for a stored Inf / NaN, keys of x below 1 or beyond the dimension included; what the
+ * builder does with a stored zero of the result is what dsa_vec_create does with it.  x is packed and widened on the device, the
+ * product runs by the strategy rule of dsa_mat_spmv_sparse (few stored entries: driven by x; many: gather over the twin — then the
+ * first packed key of x comes back, and a key below 1 hands the product to the x-driven kernel), the result is built from the packed
+ * pairs in HBM: only counts and that one key cross PCIe.  x is only read (its next write is ordered behind the product).  Replaces
+ * the result a dsa_mat_spmv_sparse_begin left with the handle.  DSA_EMODE in fill mode.  HIP library only. */
+int32_t dsa_mat_mul_vec(dsa_mat_t* h, int32_t transpose, dsa_vec_t* x, dsa_vec_t** out);
 /* same as dsa_mat_spmv_dense with x, y resident in HBM; asynchronous on the handle's stream.
  * algo: 0 = gather over the twin orientation (default), 1 = scatter over the reference's own
  * orientation with fp64 atomics (the literal _mul loop nest) */

@@ -20,6 +20,9 @@ import numpy as np
 
 from . import binding as B
 from .binding import Binding, INFO, INFO_COUNT, P_F64, P_I64, P_U8, VP, _f64, _i64
+from .operands import (  # noqa: F401
+    _dense_operand, _dense_tensor_device, _dptr, _factor_pair, _host_triple, _is_tensor, _key_tensor, _to_library, _triple,
+)
 
 COMBINE = {"+": 0, "add": 0, "*": 1, "mul": 1, "last": 2}
 COLMAJOR, ROWMAJOR = 0, 1
@@ -30,82 +33,6 @@ UPD_SKIP_MISSING = 1                     # ... and its flag
 
 def _bind(b):
     return b if b is not None else B.product()
-
-
-def _dptr(x):
-    """a device address as a C argument: 0 and None are NULL"""
-    return C.c_void_p(int(x)) if x else None
-
-
-def _is_tensor(x):
-    return type(x).__module__.split(".")[0] == "torch"
-
-
-def _factor_pair(rows, cols):
-    """A (rows, cols) factor pair, None = absent, in the form the library takes it: (True, (d_r, nr, d_c, nc), keep) for float64
-    tensors on the GPU (device addresses of contiguous tensors, 0 = absent; torch's current stream synchronised), else
-    (False, (r, nr, c, nc), keep) with pointers to float64 host arrays.  `keep` holds what the addresses point into."""
-    ops = [x for x in (rows, cols) if x is not None]
-    is_t = [_is_tensor(x) for x in ops]
-    if any(is_t):
-        import torch
-        if not all(is_t):
-            raise B.DsaArgumentError(B.EARG, "rows and cols must both be numpy arrays or both be tensors on the GPU")
-        for x in ops:
-            if x.dtype != torch.float64 or not x.is_cuda or x.dim() != 1:
-                raise B.DsaArgumentError(B.EARG, "rows and cols must be 1-D float64 tensors on the GPU")
-        keep = [None if x is None else x.contiguous() for x in (rows, cols)]
-        # the library reads the factors on its own two streams: torch's pending work on them must be over first, and they must
-        # stay as they are until the call has finished
-        torch.cuda.current_stream(ops[0].device).synchronize()
-        (r, nr), (c, nc) = ((0, 0) if x is None else (x.data_ptr(), x.numel()) for x in keep)
-        return True, (r, nr, c, nc), keep
-    keep = [np.zeros(1, dtype=np.float64)]
-    args = []
-    for x in (rows, cols):
-        a, p = (None, None) if x is None else _f64(np.asarray(x, dtype=np.float64))
-        # a factor of length 0 is still "given": a non-NULL pointer that is never read
-        if a is not None and len(a) == 0:
-            p = keep[0].ctypes.data_as(P_F64)
-        keep.append(a)
-        args += [p, 0 if a is None else len(a)]
-    return False, tuple(args), keep
-
-
-def _host_triple(I, J, V):
-    """(I, J, V) as flat contiguous int64, int64, float64 arrays of one length"""
-    i, j = (_i64(np.asarray(x, dtype=np.int64).reshape(-1))[0] for x in (I, J))
-    v = _f64(np.asarray(V, dtype=np.float64).reshape(-1))[0]
-    if not (len(i) == len(j) == len(v)):
-        raise B.DsaArgumentError(B.EARG, "rows, columns, and nonzeros do not have same length.")
-    return i, j, v
-
-
-def _triple(I, J, V, want_mask):
-    """An (I, J, V) triple in the form the library takes it, with a uint8 mask of one byte per op if one is wanted:
-    (True, (d_I, d_J, d_V, n, d_mask), mask, keep) for int64, int64, float64 tensors on the GPU (device addresses of contiguous
-    tensors; torch's current stream synchronised), else (False, (I, J, V, n, mask), mask, keep) with pointers to host arrays.
-    An absent mask, and the device mask of an empty batch, is None.  `keep` holds what the addresses point into."""
-    ops = (I, J, V)
-    is_t = [_is_tensor(x) for x in ops]
-    if any(is_t):
-        import torch
-        if not all(is_t):
-            raise B.DsaArgumentError(B.EARG, "I, J and V must all be numpy arrays or all be tensors on the GPU")
-        for x, dt in zip(ops, (torch.int64, torch.int64, torch.float64)):
-            if x.dtype != dt or not x.is_cuda or x.dim() != 1 or x.numel() != I.numel():
-                raise B.DsaArgumentError(B.EARG, "I, J, V must be 1-D int64, int64, float64 tensors of one length on the GPU")
-        keep = [x.contiguous() for x in ops]
-        n = keep[0].numel()
-        mask = torch.zeros(n, dtype=torch.uint8, device=keep[0].device) if want_mask else None
-        # the library reads the triples on its own two streams: torch's pending work on them must be over first, and they must
-        # stay as they are until the call has finished
-        torch.cuda.current_stream(keep[0].device).synchronize()
-        return True, (*(x.data_ptr() for x in keep), n, mask.data_ptr() if want_mask and n else None), mask, keep
-    i, j, v = keep = _host_triple(I, J, V)
-    mask = np.zeros(len(i), dtype=np.uint8) if want_mask else None
-    return False, (i.ctypes.data_as(P_I64), j.ctypes.data_as(P_I64), v.ctypes.data_as(P_F64), len(i),
-                   mask.ctypes.data_as(P_U8) if want_mask else None), mask, keep
 
 
 class _Handle:
@@ -119,6 +46,11 @@ class _Handle:
         if self.h is not None:
             self.b.call(self._destroy, self.h)
             self.h = None
+
+    def _require(self, symbol, message):
+        """DsaArgumentError(message) on a binding that does not have `symbol`"""
+        if not self.b.has(symbol):
+            raise B.DsaArgumentError(B.EARG, message)
 
     def __del__(self):
         try:
@@ -246,11 +178,6 @@ class DynamicSparseVector(_Handle):
     _DEV_NEEDS = "dynamic vectors as device operands need the HIP product library"
     RED_KINDS = {"sum": 0, "abssum": 1, "sqsum": 2, "absmax": 3}
 
-    def _require(self, symbol, message):
-        """DsaArgumentError(message) on a binding that does not have `symbol`"""
-        if not self.b.has(symbol):
-            raise B.DsaArgumentError(B.EARG, message)
-
     def sync(self):                                   # dsa_vec_sync: everything enqueued on the vector's stream has finished
         self.b.call("vec_sync", self.h)
 
@@ -271,8 +198,7 @@ class DynamicSparseVector(_Handle):
         n = self.nnz()
         k = torch.empty(n, dtype=torch.int64, device=dev)
         v = torch.empty(n, dtype=torch.float64, device=dev)
-        # the library writes on the vector's stream: torch's pending work on the fresh blocks first, torch's readers after the copy
-        torch.cuda.current_stream(dev).synchronize()
+        _to_library(dev)
         got = self.nonzeros_dev(k.data_ptr(), v.data_ptr(), n)
         self.sync()
         return k[:got], v[:got]
@@ -322,7 +248,7 @@ class DynamicSparseVector(_Handle):
         if other.dtype != torch.float64 or not other.is_cuda or other.dim() != 1:
             raise B.DsaArgumentError(B.EARG, "other must be a 1-D float64 tensor on the GPU")
         x = other.contiguous()
-        torch.cuda.current_stream(x.device).synchronize()      # the library reads x on the vector's stream; the call waits for the scalar
+        _to_library(x.device)
         self.b.call("vec_dot_dense_dev", self.h, _dptr(x.data_ptr()), x.numel(), C.byref(out))
         return out.value
 
@@ -362,7 +288,7 @@ def dynamicsparsevec_dev(d_keys, d_vals, n=None, combine="+", len=None, binding:
             n = keep[0].numel()
         if int(n) > keep[0].numel():
             raise B.DsaArgumentError(B.EARG, "n exceeds the length of the tensors")
-        torch.cuda.current_stream(keep[0].device).synchronize()
+        _to_library(keep[0].device)
         d_keys, d_vals = keep[0].data_ptr(), keep[1].data_ptr()
     if n is None:
         raise B.DsaArgumentError(B.EARG, "n is required with device addresses")
@@ -678,11 +604,6 @@ class DynamicSparseMatrix(_Handle):
         self.b.call("mat_rebalance_root", self.h, orientation)
 
     # ---- what the HIP-only calls below share ---------------------------------------------------------------------------------------
-    def _require(self, symbol, message):
-        """DsaArgumentError(message) on a binding that does not have `symbol`"""
-        if not self.b.has(symbol):
-            raise B.DsaArgumentError(B.EARG, message)
-
     def _fits(self, name, *args):
         """`name`(h, *args, &total) -> (total, fits): with DSA_ECAP the total is known and the arrays of `cap` entries are untouched"""
         got = C.c_int64()
@@ -695,7 +616,8 @@ class DynamicSparseMatrix(_Handle):
         return got.value, True
 
     def _two_calls(self, name, head, nouter, count_only):
-        """the host form `name`(h, *head, ptr, idx, vals, cap, &total) of a key-list export: the count-only call, then the one that fits"""
+        """the host form `name`(h, *head, ptr, idx, vals, cap, &total) of a key-list export or sparse product: the count-only call,
+        then, if it said DSA_ECAP, the one into arrays of `total` entries, whose errors are the caller's"""
         ptr = np.empty(nouter + 1, dtype=np.int64)
         total, fits = self._fits(name, *head, ptr.ctypes.data_as(P_I64), None, None, 0)
         if count_only and not fits:
@@ -721,31 +643,20 @@ class DynamicSparseMatrix(_Handle):
         return (ROWMAJOR if layout == torch.sparse_csr else COLMAJOR, index_dtype, 32 if index_dtype == torch.int32 else 64,
                 torch.device("cuda", torch.cuda.current_device()))
 
-    @staticmethod
-    def _torch_keys(keys, dev):
-        """a key list as a one-dimensional int64 CUDA tensor (a tensor is used in place)"""
-        import torch
-        if isinstance(keys, torch.Tensor):
-            if keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1:
-                raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 CUDA tensor")
-            return keys.contiguous()
-        return torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)).to(dev)
-
     def _torch_arrays(self, dev, index_dtype, nouter, call, what, total=None):
-        """(ptr[nouter + 1], idx, vals) of a device export of `what` as tensors.  call(d_ptr, d_idx, d_vals, cap) -> (total, fits):
-        the count-only call (cap = 0, 0 for idx / vals) unless the total is given, then the call into arrays of `total` entries"""
+        """(ptr[nouter + 1], idx, vals) of a device export or sparse product `what` as tensors.  call(d_ptr, d_idx, d_vals, cap) ->
+        (total, fits): the count-only call (cap = 0, 0 for idx / vals) unless the total is given, then the call into arrays of `total`
+        entries, each behind a hand-over of its own, for each has fresh blocks"""
         import torch
         ptr = torch.empty(nouter + 1, dtype=index_dtype, device=dev)
         fits = False
-        # the library works on the orientation's stream: the keys and the fresh blocks must be free of torch's pending work first, and
-        # torch's consumers of the result must start after the export has finished
         if total is None:
-            torch.cuda.current_stream(dev).synchronize()
+            _to_library(dev)
             total, fits = call(ptr.data_ptr(), 0, 0, 0)
         idx = torch.empty(max(total, 1), dtype=index_dtype, device=dev)
         val = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
         if not fits:
-            torch.cuda.current_stream(dev).synchronize()
+            _to_library(dev)
             total, fits = call(ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), total)
             if not fits:
                 raise B.DsaErrorException(B.ECAP, "the %s grew between the count and the emit" % what)
@@ -846,7 +757,7 @@ class DynamicSparseMatrix(_Handle):
         an int64 CUDA tensor (used in place); the arrays never leave HBM."""
         self._require("mat_select_compressed", "the selected export needs the HIP product library")
         orientation, index_dtype, bits, dev = self._torch_format(layout, index_dtype)
-        sel = self._torch_keys(keys, dev)
+        sel = _key_tensor(keys, dev)
         nsel = sel.numel()
         m, n = self.size()
         arrays = self._torch_arrays(dev, index_dtype, nsel, what="selection", call=lambda d_ptr, d_idx, d_vals, cap: (
@@ -896,7 +807,7 @@ class DynamicSparseMatrix(_Handle):
         for CSR, rows for CSC) must ascend strictly, because torch expects sorted indices within a slice."""
         self._require("mat_submatrix_compressed", "the submatrix export needs the HIP product library")
         orientation, index_dtype, bits, dev = self._torch_format(layout, index_dtype)
-        d_rows, d_cols = self._torch_keys(rows, dev), self._torch_keys(cols, dev)
+        d_rows, d_cols = _key_tensor(rows, dev), _key_tensor(cols, dev)
         outer, inner = (d_rows, d_cols) if orientation == ROWMAJOR else (d_cols, d_rows)
         nouter, ninner = outer.numel(), inner.numel()
         if ninner > 1 and not bool((inner[1:] > inner[:-1]).all()):
@@ -1037,34 +948,14 @@ class DynamicSparseMatrix(_Handle):
         tr = 1 if transpose else 0
         m, n = self.size()
         ny = n if transpose else m
-        if isinstance(X, np.ndarray):
-            one_d = X.ndim == 1
-            xx = np.ascontiguousarray(X.reshape(-1, 1) if one_d else X, dtype=np.float64)
-            if xx.ndim != 2:
-                raise B.DsaArgumentError(B.EARG, "X must have one or two dimensions")
-            nx, k = xx.shape
-            y = np.empty((ny, k), dtype=np.float64)
-            self.b.call("mat_spmm_dense", self.h, tr, xx.ctypes.data_as(P_F64), nx, k, k, y.ctypes.data_as(P_F64), ny, k)
-            return y[:, 0] if one_d else y
-        import torch
-        if not isinstance(X, torch.Tensor):
-            raise B.DsaArgumentError(B.EARG, "X must be a numpy array or a torch tensor")
-        if X.dtype != torch.float64 or not X.is_cuda or X.dim() not in (1, 2):
-            raise B.DsaArgumentError(B.EARG, "X must be a 1-D or 2-D float64 tensor on the GPU")
-        one_d = X.dim() == 1
-        xx = X.unsqueeze(1) if one_d else X
-        nx, k = xx.shape
-        if k < 1:
-            raise B.DsaArgumentError(B.EARG, "X has no columns")
-        if xx.stride(1) != 1 or (nx > 1 and xx.stride(0) < k):
-            xx = xx.contiguous()
-        ldx = xx.stride(0) if nx > 1 else k
-        y = torch.empty((ny, k), dtype=torch.float64, device=X.device)
-        # the library works on the orientation's stream: torch's pending work on X and on the fresh block must be over first, and
-        # torch's consumers of the result must start after the product has finished (as in to_torch)
-        torch.cuda.current_stream(X.device).synchronize()
-        self.matmul_dev(xx.data_ptr(), nx, k, y.data_ptr(), ny, ldx=ldx, ldy=k, transpose=transpose)
-        self.sync()
+        dev, xp, nx, k, ldx, one_d, device, xx = _dense_operand(X)
+        y = xx.new_empty((ny, k)) if dev else np.empty((ny, k), dtype=np.float64)
+        if dev:
+            _to_library(device)
+            self.matmul_dev(xp, nx, k, y.data_ptr(), ny, ldx=ldx, ldy=k, transpose=transpose)
+            self.sync()
+        else:
+            self.b.call("mat_spmm_dense", self.h, tr, xp, nx, k, ldx, y.ctypes.data_as(P_F64), ny, k)
         return y[:, 0] if one_d else y
 
     def __matmul__(self, X):
@@ -1092,40 +983,19 @@ class DynamicSparseMatrix(_Handle):
             sel, sp = _i64(keys)
             if sel.ndim != 1:
                 raise B.DsaArgumentError(B.EARG, "the selection must be one-dimensional")
-            one_d = X.ndim == 1
-            xx = np.ascontiguousarray(X.reshape(-1, 1) if one_d else X, dtype=np.float64)
-            if xx.ndim != 2:
-                raise B.DsaArgumentError(B.EARG, "X must have one or two dimensions")
-            nx, k = xx.shape
-            y = np.empty((len(sel), k), dtype=np.float64)
-            self.b.call("mat_spmm_selected", self.h, tr, sp, len(sel), xx.ctypes.data_as(P_F64), nx, k, k, y.ctypes.data_as(P_F64), k)
-            return y[:, 0] if one_d else y
-        import torch
-        if not isinstance(X, torch.Tensor):
-            raise B.DsaArgumentError(B.EARG, "X must be a numpy array or a torch tensor")
-        if X.dtype != torch.float64 or not X.is_cuda or X.dim() not in (1, 2):
-            raise B.DsaArgumentError(B.EARG, "X must be a 1-D or 2-D float64 tensor on the GPU")
-        if isinstance(keys, torch.Tensor):
-            if keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1:
-                raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 CUDA tensor")
-            sel = keys.contiguous()
+            nsel, device = len(sel), None
         else:
-            sel = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)).to(X.device)
-        nsel = sel.numel()
-        one_d = X.dim() == 1
-        xx = X.unsqueeze(1) if one_d else X
-        nx, k = xx.shape
-        if k < 1:
-            raise B.DsaArgumentError(B.EARG, "X has no columns")
-        if xx.stride(1) != 1 or (nx > 1 and xx.stride(0) < k):
-            xx = xx.contiguous()
-        ldx = xx.stride(0) if nx > 1 else k
-        y = torch.empty((nsel, k), dtype=torch.float64, device=X.device)
-        # the stream discipline of matmul and select_torch: torch's pending work on the keys, X and the fresh block is over before the
-        # library starts on the orientation's stream, and torch's consumers of the result start after the product has finished
-        torch.cuda.current_stream(X.device).synchronize()
-        self.matmul_selected_dev(sel.data_ptr(), nsel, xx.data_ptr(), nx, k, y.data_ptr(), ldx=ldx, ldy=k, transpose=transpose)
-        self.sync()
+            device = _dense_tensor_device(X)                     # the keys are judged after the kind of X and before its shape
+            sel = _key_tensor(keys, device)
+            nsel = sel.numel()
+        dev, xp, nx, k, ldx, one_d, device, xx = _dense_operand(X, device)
+        y = xx.new_empty((nsel, k)) if dev else np.empty((nsel, k), dtype=np.float64)
+        if dev:
+            _to_library(device)
+            self.matmul_selected_dev(sel.data_ptr(), nsel, xp, nx, k, y.data_ptr(), ldx=ldx, ldy=k, transpose=transpose)
+            self.sync()
+        else:
+            self.b.call("mat_spmm_selected", self.h, tr, sp, nsel, xp, nx, k, ldx, y.ctypes.data_as(P_F64), k)
         return y[:, 0] if one_d else y
 
     def matmul_selected_dev(self, d_sel, nsel, d_x, nx, k, d_y, ldx=None, ldy=None, transpose=False):
@@ -1173,25 +1043,7 @@ class DynamicSparseMatrix(_Handle):
             k = len(xptr) - 1
             if int(xptr[k]) - int(base) != len(xidx):
                 raise B.DsaArgumentError(B.EARG, "indptr[k] - base must be the number of stored entries")
-            yptr = np.empty(k + 1, dtype=np.int64)
-            got = C.c_int64()
-            yidx = yval = None
-            for _ in range(2):              # the count-only call, then the one that fits
-                cap = 0 if yidx is None else len(yidx)
-                try:
-                    self.b.call("mat_spgemm_csc", self.h, tr, int(base), xpp, xip, xvp, k, yptr.ctypes.data_as(P_I64),
-                                yidx.ctypes.data_as(P_I64) if cap else None, yval.ctypes.data_as(P_F64) if cap else None, cap,
-                                C.byref(got))
-                except B.DsaError as e:
-                    if e.code != B.ECAP or yidx is not None:
-                        raise
-                    yidx = np.empty(got.value, dtype=np.int64)
-                    yval = np.empty(got.value, dtype=np.float64)
-                    continue
-                break
-            if yidx is None:
-                yidx, yval = np.empty(0, dtype=np.int64), np.empty(0, dtype=np.float64)
-            return yptr, yidx[:got.value], yval[:got.value]
+            return self._two_calls("mat_spgemm_csc", (tr, int(base), xpp, xip, xvp, k), k, False)
         import torch
         if not isinstance(S, torch.Tensor) or S.layout != torch.sparse_csc:
             raise B.DsaArgumentError(B.EARG, "S must be a CSC triple or a torch.sparse_csc tensor")
@@ -1202,22 +1054,10 @@ class DynamicSparseMatrix(_Handle):
             raise B.DsaArgumentError(B.EARG, "the indices of S must be int32 or int64")
         bits = 32 if xptr.dtype == torch.int32 else 64
         k, nnzx = S.shape[1], xidx.numel()
-        dev = S.device
-        yptr = torch.empty(k + 1, dtype=xptr.dtype, device=dev)
-        # the stream discipline of select_torch: S and the fresh blocks free of torch's pending work first, torch's consumers of the
-        # result behind the product
-        torch.cuda.current_stream(dev).synchronize()
-        args = (xptr.data_ptr(), xidx.data_ptr(), xval.data_ptr(), k, nnzx, yptr.data_ptr())
-        total, fits = self.matmul_sparse_dev(*args, 0, 0, 0, index_bits=bits, transpose=transpose)
-        yidx = torch.empty(max(total, 1), dtype=xptr.dtype, device=dev)
-        yval = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
-        if not fits:
-            torch.cuda.current_stream(dev).synchronize()
-            total, fits = self.matmul_sparse_dev(*args, yidx.data_ptr(), yval.data_ptr(), total, index_bits=bits, transpose=transpose)
-            if not fits:
-                raise B.DsaErrorException(B.ECAP, "the product grew between the count and the emit")
-        self.sync()
-        return torch.sparse_csc_tensor(yptr, yidx[:total], yval[:total], size=(ny, k))
+        arrays = self._torch_arrays(S.device, xptr.dtype, k, what="product", call=lambda d_ptr, d_idx, d_vals, cap: (
+            self.matmul_sparse_dev(xptr.data_ptr(), xidx.data_ptr(), xval.data_ptr(), k, nnzx, d_ptr, d_idx, d_vals, cap, index_bits=bits,
+                                   transpose=transpose)))
+        return self._torch_tensor(COLMAJOR, arrays, k, ny)
 
     # ---- reductions per row / column and in-place scaling (include/dsa.h: dsa_mat_reduce[_dev], dsa_mat_scale[_dev]; HIP library only)
     RED_KINDS = {"sum": 0, "abssum": 1, "sqsum": 2, "absmax": 3, "count": 4}
@@ -1247,8 +1087,7 @@ class DynamicSparseMatrix(_Handle):
         if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda or out.dim() != 1 or \
                 not out.is_contiguous() or out.numel() != cnt:
             raise B.DsaArgumentError(B.EARG, "out must be a contiguous 1-D float64 tensor on the GPU with one element per %s" % per)
-        # the library works on the orientation's stream (as in matmul): torch's pending work on out first, torch's readers after
-        torch.cuda.current_stream(out.device).synchronize()
+        _to_library(out.device)
         self.reduce_dev(kind, per, out.data_ptr(), cnt)
         self.sync()
         return out
@@ -1303,8 +1142,7 @@ class DynamicSparseMatrix(_Handle):
                 raise B.DsaArgumentError(B.EARG, "a key tensor must be a one-dimensional int64 tensor")
             if keys.is_cuda:
                 k = keys.contiguous()
-                # the library reads the keys on its own streams: torch's pending work on them must be over first
-                torch.cuda.current_stream(k.device).synchronize()
+                _to_library(k.device)
                 return self.delete_batch_dev(orientation, k.data_ptr(), k.numel())
             keys = keys.numpy()
         k, kp = _i64(np.asarray(keys, dtype=np.int64).reshape(-1))
@@ -1585,9 +1423,7 @@ def from_torch(t, binding: Binding | None = None) -> DynamicSparseMatrix:
     val = val.to(torch.float64).contiguous()
     bits = 32 if ptr.dtype == torch.int32 else 64
     nnz = int(val.numel())
-    # the library reads on streams of its own: what torch has enqueued for these arrays must have finished first; when the call
-    # returns nothing reads them any more
-    torch.cuda.current_stream(t.device).synchronize()
+    _to_library(t.device)
     if t.layout == torch.sparse_coo:
         return dynamicsparse_dev(ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), nnz, m, n, index_bits=bits, index_base=0, binding=b)
     if t.layout == torch.sparse_csr:

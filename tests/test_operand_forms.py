@@ -102,3 +102,126 @@ def test_triple_errors(api, dsa):
             api._triple(*ops, False)
         with raises(dsa, SAME_LENGTH):
             api._host_triple(*ops)
+
+
+# ---- the read-only side: dense right-hand sides, key tensors, the count-then-emit protocol --------------------------------------
+X_DIMS = "X must have one or two dimensions"
+X_KIND = "X must be a numpy array or a torch tensor"
+X_TENSOR = "X must be a 1-D or 2-D float64 tensor on the GPU"
+KEY_TENSOR = "a key tensor must be a one-dimensional int64 CUDA tensor"
+
+
+def test_dense_operand_numpy(api, dsa):
+    dev, p, nx, k, ldx, one_d, device, keep = api._dense_operand(np.array([1.0, 2.0, 3.0]))
+    assert dev is False and device is None and (nx, k, ldx, one_d) == (3, 1, 1, True)
+    assert [p[i] for i in range(3)] == [1.0, 2.0, 3.0]
+    x = np.arange(12.0).reshape(4, 3)
+    dev, p, nx, k, ldx, one_d, device, keep = api._dense_operand(x)
+    assert (nx, k, ldx, one_d) == (4, 3, 3, False) and address(p) == x.ctypes.data       # C-contiguous float64: used where it is
+    for other in (np.asfortranarray(x), x.astype(np.int32)):                             # copied into row-major float64
+        dev, p, nx, k, ldx, one_d, device, keep = api._dense_operand(other)
+        assert (nx, k, ldx, one_d) == (4, 3, 3, False) and address(p) != other.ctypes.data
+        assert [p[i] for i in range(12)] == x.reshape(-1).tolist()
+    with raises(dsa, X_DIMS):
+        api._dense_operand(np.zeros((2, 2, 2)))
+    dev, p, nx, k, ldx, one_d, device, keep = api._dense_operand(np.zeros((0, 3)))
+    assert (nx, k, one_d) == (0, 3, False)
+    assert api._dense_operand(np.zeros((3, 0)))[2:4] == (3, 0)                           # no columns: left to the library
+
+
+def test_dense_operand_tensor_errors(api, dsa):
+    for bad in (torch.ones(3, 2, dtype=torch.float64),                   # not on the GPU
+                torch.ones(3, 2, dtype=torch.float32),                   # wrong dtype
+                torch.ones(2, 2, 2, dtype=torch.float64)):               # 3-D
+        with raises(dsa, X_TENSOR):
+            api._dense_operand(bad)
+    with raises(dsa, X_KIND):
+        api._dense_operand([[1.0, 2.0], [3.0, 4.0]])
+
+
+def test_key_tensor_errors(api, dsa):
+    for bad in (torch.tensor([1, 2]),                                    # int64, but not on the GPU
+                torch.tensor([1, 2], dtype=torch.int32),
+                torch.tensor([[1, 2]])):                                 # 2-D
+        with raises(dsa, KEY_TENSOR):
+            api._key_tensor(bad, "cpu")
+
+
+class FakeLibrary:
+    """Stands in for a Binding under one matrix handle: an export whose total is `total` at the count-only call and `later` (default:
+    the same) afterwards.  It writes the total, fills what fits, and answers DSA_ECAP where the library would; the calls are recorded
+    as (name, cap)."""
+
+    def __init__(self, dsa, total, later=None):
+        self.dsa, self.totals, self.calls = dsa, [total, total if later is None else later], []
+
+    def has(self, name):
+        return True
+
+    def call(self, name, h, *args):
+        if name in ("mat_destroy", "mat_sync"):
+            return
+        *_, idx, val, cap, got = args
+        total = self.totals[min(len(self.calls), 1)]
+        self.calls.append((name, cap))
+        got._obj.value = total
+        if cap < total:
+            raise self.dsa.DsaErrorException(self.dsa.binding.ECAP, "the arrays are too short")
+        for k in range(total):
+            idx[k], val[k] = k + 1, 0.5 * k
+
+
+def test_two_calls_count_then_emit(api, dsa):
+    lib = FakeLibrary(dsa, 0)
+    ptr, idx, val = api.DynamicSparseMatrix(lib, 1)._two_calls("export", (7,), 3, False)
+    assert lib.calls == [("export", 0)] and ptr.shape == (4,) and ptr.dtype == np.int64
+    assert (idx.dtype, idx.shape, val.dtype, val.shape) == (np.int64, (0,), np.float64, (0,))
+    lib = FakeLibrary(dsa, 5)
+    ptr, idx, val = api.DynamicSparseMatrix(lib, 1)._two_calls("export", (7,), 3, False)
+    assert lib.calls == [("export", 0), ("export", 5)]
+    assert idx.tolist() == [1, 2, 3, 4, 5] and val.tolist() == [0.0, 0.5, 1.0, 1.5, 2.0]
+    lib = FakeLibrary(dsa, 5, later=3)                                   # fewer at the emit: sliced to what was delivered
+    ptr, idx, val = api.DynamicSparseMatrix(lib, 1)._two_calls("export", (), 3, False)
+    assert idx.tolist() == [1, 2, 3] and val.shape == (3,)
+    lib = FakeLibrary(dsa, 5, later=6)                                   # more at the emit: the library's own error
+    with pytest.raises(dsa.DsaErrorException, match="^ECAP: the arrays are too short$") as e:
+        api.DynamicSparseMatrix(lib, 1)._two_calls("export", (), 3, False)
+    assert e.value.code == dsa.binding.ECAP and lib.calls == [("export", 0), ("export", 5)]
+    lib = FakeLibrary(dsa, 5)
+    ptr, idx, val = api.DynamicSparseMatrix(lib, 1)._two_calls("export", (), 3, True)
+    assert lib.calls == [("export", 0)] and ptr.shape == (4,) and idx is None and val is None
+    lib = FakeLibrary(dsa, 0)                                            # count_only with a total that fits: the empty arrays
+    ptr, idx, val = api.DynamicSparseMatrix(lib, 1)._two_calls("export", (), 3, True)
+    assert lib.calls == [("export", 0)] and idx.shape == (0,) and val.shape == (0,)
+
+
+def test_torch_arrays_count_then_emit(api, dsa, monkeypatch):
+    """the device helper on CPU tensors: only the hand-over to the library, which needs a GPU, is replaced — and counted"""
+    waits = []
+    monkeypatch.setattr(api, "_to_library", waits.append)
+    a = api.DynamicSparseMatrix(FakeLibrary(dsa, 0), 1)
+    totals, caps = [], []
+
+    def call(d_ptr, d_idx, d_vals, cap):
+        caps.append((cap, bool(d_idx), bool(d_vals)))
+        total = totals.pop(0)
+        return total, cap >= total
+
+    totals[:] = [0]
+    ptr, idx, val = a._torch_arrays("cpu", torch.int32, 3, call, "thing")
+    assert caps == [(0, False, False)] and len(waits) == 1
+    assert ptr.dtype == torch.int32 and ptr.shape == (4,) and idx.dtype == torch.int32 and idx.shape == (0,) and val.shape == (0,)
+    del caps[:], waits[:]
+    totals[:] = [5, 5]
+    ptr, idx, val = a._torch_arrays("cpu", torch.int64, 3, call, "thing")
+    assert caps == [(0, False, False), (5, True, True)] and len(waits) == 2      # each call behind a hand-over of its own
+    assert idx.dtype == torch.int64 and idx.shape == (5,) and val.dtype == torch.float64 and val.shape == (5,)
+    del caps[:], waits[:]
+    totals[:] = [5]                                                      # the total is known: the emit alone
+    ptr, idx, val = a._torch_arrays("cpu", torch.int64, 3, call, "thing", total=5)
+    assert caps == [(5, True, True)] and len(waits) == 1 and idx.shape == (5,)
+    del caps[:], waits[:]
+    totals[:] = [5, 6]
+    with pytest.raises(dsa.DsaErrorException, match="^ECAP: the product grew between the count and the emit$"):
+        a._torch_arrays("cpu", torch.int64, 3, call, "product")
+    assert caps == [(0, False, False), (5, True, True)]

@@ -147,7 +147,12 @@ int32_t dsa_dbg_raw_rebalance(int64_t* keys, double* vals, uint8_t* occ, int64_t
     for (int64_t i = ws - 1; i < we; ++i) m += occ[i] ? 1 : 0;
     RawGuard g;
     raw_load(g.P, keys, vals, occ, len, sems, nsems, 0);
-    if (engine == DSA_DBG_ENGINE_GRID) {
+    if (engine == DSA_DBG_ENGINE_GRID_WINDOW) {
+        // what the write path calls for a window too wide for the LDS paths: pack launch + packed-spread launch for an interior
+        // window, root_rebalance for the whole array, the bitmap clear for m == 0
+        if (!aligned) fail(DSA_EARG, "the grid-wide rebalance takes windows of whole occupancy words");
+        window_rebalance(g.P, ws, we, m);
+    } else if (engine == DSA_DBG_ENGINE_GRID) {
         // k_move2 reads whole occupancy words and writes whole destination words: windows of whole words
         if (!aligned) fail(DSA_EARG, "the grid-wide rebalance takes windows of whole occupancy words");
         if (m > 0) {

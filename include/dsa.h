@@ -708,9 +708,12 @@ int32_t dsa_dev_switches(char* buf, int64_t cap, int32_t* enabled);
  *                         blk_rebalance_small: windows <= 8192 slots)
  *   DSA_DBG_ENGINE_WAVE   the wave-level primitives of the batch-parallel rounds (pb_shift_*, pb_wave_rebalance: windows <= 2048 slots)
  *   DSA_DBG_ENGINE_GRID   the grid-wide rebalance kernel k_move2 (dsa_dbg_raw_rebalance only; windows of whole 64-slot words)
+ *   DSA_DBG_ENGINE_GRID_WINDOW  the same kernel as the write path launches it (dsa_dbg_raw_rebalance only; windows of whole 64-slot
+ *                         words): an interior window is packed into the scratch buffer and spread back from there (two launches, the
+ *                         second on a packed source), the window [1, len] is rebalanced at the root, an empty window has its bitmap cleared
  * fast = 0: K-find replays the reference bisection probe for probe; fast = 1: its wave-parallel 64-ary form, which the write paths
  * use wherever the searched range is key-partitioned (only then are the two required to agree). */
-enum { DSA_DBG_ENGINE_BLOCK = 0, DSA_DBG_ENGINE_WAVE = 1, DSA_DBG_ENGINE_GRID = 2 };
+enum { DSA_DBG_ENGINE_BLOCK = 0, DSA_DBG_ENGINE_WAVE = 1, DSA_DBG_ENGINE_GRID = 2, DSA_DBG_ENGINE_GRID_WINDOW = 3 };
 /* find(array, key, from, to)  src/finds.jl:29-57 -> (pos, elem) ; *has = 0 <=> elem === nothing */
 int32_t dsa_dbg_raw_find(const int64_t* keys, const double* vals, const uint8_t* occ, int64_t len, int64_t key, int64_t from, int64_t to,
                          int32_t engine, int32_t fast, int64_t* pos, int32_t* has, int64_t* fkey, double* fval);

@@ -9,8 +9,8 @@ P_I64 = C.POINTER(C.c_int64)
 P_F64 = C.POINTER(C.c_double)
 P_U8 = C.POINTER(C.c_uint8)
 
-BLOCK, WAVE, GRID = 0, 1, 2
-ENGINE_NAMES = {BLOCK: "block", WAVE: "wave", GRID: "grid"}
+BLOCK, WAVE, GRID, GRID_WINDOW = 0, 1, 2, 3
+ENGINE_NAMES = {BLOCK: "block", WAVE: "wave", GRID: "grid", GRID_WINDOW: "grid-window"}
 
 
 def to_arrays(slots):
